@@ -20,6 +20,11 @@ N ways (what `metric` literally says; `--scaling strong` makes that one `value`)
 job, several grid rounds of the entropy kernel; `--config 5 --job` likewise (Ns=4e6).
 
 Prints ONE JSON line on rank 0.  No PyTorch anywhere in the measured path.
+
+A plain run sets up, warms up (the W warm-up steps, repeated until they have lasted 1 s), times
+exactly K steps and prints the line.  `--full` adds everything else the line can carry: the CPU
+baseline, the main kernel's duration and the roofline (HIP events on every 128th timed step), the
+secondary figures and, with N > 1, the other scaling reading.  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float64).
 """
 import argparse
 import json
@@ -41,17 +46,19 @@ HBM_PEAK_GBS = 8000.0    # /opt/skills/guides/MI355X_MICROARCH.md
 # config 3's shape on 8 GPUs, config 5 is quoted on 8 GPUs: its per-GPU share is Ns/8)
 PER_GPU_NS = {2: 100_000, 3: 1_000_000, 4: 1_000_000, 5: 4_000_000 // 8}
 JOB_NS = {2: 100_000, 3: 1_000_000, 4: 8_000_000, 5: 4_000_000}  # BASELINE.json `configs`
-# The timed region repeats its K steps until it is at least this long.  The headline line's is
-# long enough for the driver's 5-second GPU-activity sampler to land inside it.
-MIN_TIMED_S = 6.0
-MIN_TIMED_SECONDARY_S = 0.5
+MIN_WARMUP_S = 1.0  # the warm-up repeats its W steps until it has lasted this long (W = 0: no warm-up)
 
 
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=50)
+    p.add_argument("--steps", type=int, default=50, help="timed steps (exactly this many)")
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="measure more than the headline: CPU baseline, kernel duration and roofline, secondary figures, "
+                        "the other scaling reading (N > 1)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (F, dF, G, H, varF) as DIR/<name>.npy in float64")
     p.add_argument("--config", type=int, default=3, choices=sorted(PER_GPU_NS),
                    help="BASELINE config whose per-GPU shape is run (3 = the headline metric's; 4 = config 4's "
                         "job, Ns = 8e6, split over the ranks)")
@@ -67,20 +74,21 @@ def parse():
     p.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                    help="N > 1, config 3: what `value` is -- weak: Ns = N x 1e6 (config 4's reading; the default), "
                         "strong: Ns = 1e6 split N ways.  The other one is reported beside it.")
-    p.add_argument("--min-timed-s", type=float, default=None,
-                   help=f"minimum length of the timed region (default {MIN_TIMED_S} s for the headline line, "
-                        f"{MIN_TIMED_SECONDARY_S} s for secondary lines)")
     p.add_argument("--spawn", action="store_true",
                    help="start the ranks from this process even for --gpus 1 (what --gpus N > 1 does when it is not "
                         "already running under a launcher)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--no-secondary", action="store_true",
-                   help="skip the secondary figures (predict roofline, device-resident loop, reference stream)")
+                   help="with --full: skip the secondary figures (predict roofline, device-resident loop, reference "
+                        "stream, S = 4 / 8, full ELCBO)")
     p.add_argument("--cpu-sample-nsk", type=int, default=0,
                    help="per-component samples of the CPU-baseline run (0 = a sample sized for ~10-30 s of "
                         "host work: the whole workload at configs 2 and 3, a fifth of it at config 5)")
     p.add_argument("--cpu-reps", type=int, default=3, help="CPU-baseline runs; the MEDIAN is reported (SURVEY 8d: median of >= 3)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def algorithmic_flops(D, K, ns_rows_total, grad=True):
@@ -181,7 +189,7 @@ def main():
     cpu_res = None
     ns_gpu = (JOB_NS[a.config] // world) if job_mode else PER_GPU_NS[a.config]
     wl = synthetic.make_workload(a.config, Ns_total=ns_gpu, S=a.S)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         # ~10-30 s of host work: the whole workload at configs 2 and 3, a bounded part of it otherwise
         div = {2: 1, 3: 1, 4: 8, 5: 5 if not job_mode else 40}[a.config]
         nsk_cpu = a.cpu_sample_nsk or max(2, (wl.NsK // div) // 2 * 2)
@@ -215,7 +223,7 @@ def main():
         sys.exit("bench.py: fewer antithetic rows per component than ranks")
 
     def make_step(nsk_job, rng):
-        step_no = [0]
+        """step(i): evaluation number i (1, 2, ...): its parameter vector and draws depend on i alone."""
         if rng == "philox":
 
             # a different parameter vector every call, as in Adam: seven of them, made outside the timed loop (the metric is
@@ -223,9 +231,8 @@ def main():
             # variational_optimization.py:1082-1085, is idempotent on them)
             ths = [theta + 1e-9 * i for i in range(7)]
 
-            def step():
-                step_no[0] += 1
-                return _neg_elcbo(ths[step_no[0] % 7], gp, vp, 0.0, nsk_job, True, False, bnd, rng="philox", seed=step_no[0])
+            def step(i):
+                return _neg_elcbo(ths[i % 7], gp, vp, 0.0, nsk_job, True, False, bnd, rng="philox", seed=i)
 
             return step
         # HBM-resident draws, uploaded once and reused by every evaluation: the fused
@@ -252,9 +259,8 @@ def main():
         dF = np.empty(theta.size)
         th = theta.copy()
 
-        def step(_keep=(lb, ub)):  # (the bounds' buffers live as long as the closure)
-            step_no[0] += 1
-            th[:] = theta + 1e-9 * (step_no[0] % 7)  # a different parameter vector every call
+        def step(i, _keep=(lb, ub)):  # (the bounds' buffers live as long as the closure)
+            th[:] = theta + 1e-9 * (i % 7)  # a different parameter vector every call
             ctx.check(ctx._lib.vbmc_neg_elcbo(ctx._h, _lib.ptr(th), th.size, C.byref(opts),
                                               C.byref(Fc), _lib.ptr(dF), C.byref(Gc), C.byref(Hc),
                                               None, None, None, None, None))
@@ -262,64 +268,58 @@ def main():
 
         return step
 
-    def measure(nsk_job, min_timed_s, rng):
-        """W warm-up steps, a calibration, then the timed region: R x K steps back to back between
+    # --full: the main kernel's duration comes from HIP events carried by its own dispatch packet
+    # (hipExtLaunchKernel: no barrier packet in the queue), read back on every SAMPLE_EVERY-th step
+    # of the timed region together with the library's host-side breakdown; the other steps run
+    # without any instrumentation call.
+    SAMPLE_EVERY = 128  # (a sampled step is not armed, api_elbo.hip: every 32nd cost the mean 0.3 us)
+
+    def measure(nsk_job, rng):
+        """The warm-up, then the timed region: the K requested steps back to back between
         barrier + synchronize on both sides, the maximum over the ranks."""
         step = make_step(nsk_job, rng)
-        for _ in range(a.warmup):
-            out = step()
-        ctx.synchronize()
-        # a short calibration run (after the warm-up, so first-call allocations are out of it) sizes
-        # the timed region
-        n_cal = max(3, min(20, a.steps))
+        # W warm-up steps, repeated (same inputs) until the warm-up has lasted MIN_WARMUP_S, so that the timed steps
+        # start at steady clocks whatever W is; every rank stops after the same number of rounds (comm_max)
         t_w = time.perf_counter()
-        for _ in range(n_cal):
-            out = step()
-        ctx.synchronize()
-        est = (time.perf_counter() - t_w) / n_cal
-        # The timed region is R back-to-back repetitions of the K requested steps, R chosen so that it
-        # lasts >= min_timed_s whatever K is (a 20-step region is 3 ms: too short to mean anything).
-        # All ranks must agree on R: take the maximum estimate.
-        est = ctx.comm_max(est)
-        repeats = max(1, int(np.ceil(1.15 * min_timed_s / max(a.steps * est, 1e-9))))
-        n_timed = repeats * a.steps
+        while a.warmup:
+            for i in range(1, a.warmup + 1):
+                step(i)
+            ctx.synchronize()
+            if ctx.comm_max(time.perf_counter() - t_w) >= MIN_WARMUP_S:
+                break
         ctx.comm_barrier()
         ctx.synchronize()
-        # The main kernel's duration comes from HIP events carried by its own dispatch packet
-        # (hipExtLaunchKernel: no barrier packet in the queue), read back on every SAMPLE_EVERY-th step
-        # of the timed region together with the library's host-side breakdown; the other steps run
-        # without any instrumentation call.
-        SAMPLE_EVERY = 128  # (a sampled step is not armed, api_elbo.hip: every 32nd cost the mean 0.3 us)
         kern_ms = []
         host_us = np.zeros(5)
-        n_host = 0
         t0 = time.perf_counter()
-        for i in range(n_timed):
-            if i % SAMPLE_EVERY <= 1:
-                ctx.set_timing(i % SAMPLE_EVERY == 0)  # on for the sampled step, off again after it
-            out = step()
-            if i % SAMPLE_EVERY == 0:
-                kern_ms.append(ctx.last_kernel_ms(0))
-                host_us += ctx.last_host_us()
-                n_host += 1
-        ctx.set_timing(False)
+        if a.full:
+            for i in range(a.steps):
+                if i % SAMPLE_EVERY <= 1:
+                    ctx.set_timing(i % SAMPLE_EVERY == 0)  # on for the sampled step, off again after it
+                out = step(a.warmup + 1 + i)
+                if i % SAMPLE_EVERY == 0:
+                    kern_ms.append(ctx.last_kernel_ms(0))
+                    host_us += ctx.last_host_us()
+            ctx.set_timing(False)
+        else:
+            for i in range(a.steps):
+                out = step(a.warmup + 1 + i)
         ctx.synchronize()
         ctx.comm_barrier()
         dt = time.perf_counter() - t0
         dt = ctx.comm_max(dt)
         if not np.isfinite(out[0]):
             sys.exit("non-finite objective")
-        return {"dt": dt, "n_timed": n_timed, "repeats": repeats, "F": out[0], "kern_ms": float(np.mean(kern_ms)),
-                "n_kern": len(kern_ms), "host_us": host_us / max(n_host, 1), "plan": ctx.last_entmc_plan(),
-                "sample_every": SAMPLE_EVERY, "nsk_job": nsk_job}
+        return {"dt": dt, "n_timed": a.steps, "out": out, "F": out[0],
+                "kern_ms": float(np.mean(kern_ms)) if kern_ms else None, "n_kern": len(kern_ms),
+                "host_us": host_us / max(len(kern_ms), 1), "plan": ctx.last_entmc_plan(), "nsk_job": nsk_job}
 
     nsk_job = nsk_of[scaling]
     ns_job = nsk_job * K
     headline = a.config == 3 and not job_mode and a.S == 1
-    min_timed = a.min_timed_s if a.min_timed_s is not None else (MIN_TIMED_S if headline else MIN_TIMED_SECONDARY_S)
 
     predict_roofline = adam_loop = reference_stream = None
-    if not a.no_secondary:
+    if a.full and not a.no_secondary:
         # Secondary roofline (SURVEY 8d, third way): gp.predict at the acquisition batch size,
         # its GEMM flops against the FP64 matrix-core peak.  Timed with HIP events around the
         # variance product alone (`frac`) and around the three predict launches (K*, product, finish).
@@ -433,7 +433,7 @@ def main():
             }
 
     gp_samples = full_elcbo = None
-    if not a.no_secondary and world == 1 and not job_mode and a.rng == "philox":
+    if a.full and not a.no_secondary and world == 1 and not job_mode and a.rng == "philox":
         # Secondary figures ("S = 1 (also S = 8)"): the same step with S = 4 (the reference's default at
         # N = 400) and S = 8 GP hyper-parameter samples -- step time, where the GP sums ran and when their word and
         # the entropy's reached the host (vbmc_last_step_marks: the GP word must arrive first, or the sums are
@@ -490,9 +490,9 @@ def main():
 
     # the other reading of "N GPUs" first (a short region), then the line's own
     other = None
-    if world > 1 and not job_mode and a.rng == "philox":
+    if a.full and world > 1 and not job_mode and a.rng == "philox":
         o = "strong" if scaling == "weak" else "weak"
-        mo = measure(nsk_of[o], MIN_TIMED_SECONDARY_S, a.rng)
+        mo = measure(nsk_of[o], a.rng)
         ev = mo["n_timed"] / mo["dt"]
         other = {"scaling": o, "value": ev * (nsk_of[o] * K / PER_GPU_NS[a.config]), "evals_per_s_job": ev,
                  "unit": "evals/s (1e6-sample-equivalent)", "job_Ns": nsk_of[o] * K, "ms_per_step": 1e3 / ev,
@@ -501,8 +501,8 @@ def main():
                  "what": ("the SAME Ns=1e6 job split over the ranks (what `metric` literally says): per-rank entropy "
                           "kernel ~1/N of the single-GPU one, prep / finish / all-reduce / host turnaround unchanged"
                           if o == "strong" else "Ns = N x 1e6: every rank keeps config 3's per-GPU share (config 4's shape)")}
-    m = measure(nsk_job, min_timed, a.rng)
-    dt, n_timed, repeats, F, k_ms, plan = m["dt"], m["n_timed"], m["repeats"], m["F"], m["kern_ms"], m["plan"]
+    m = measure(nsk_job, a.rng)
+    dt, n_timed, F, k_ms, plan = m["dt"], m["n_timed"], m["F"], m["kern_ms"], m["plan"]
     host_us = m["host_us"]
 
     ms_per_step = 1e3 * dt / n_timed
@@ -510,27 +510,6 @@ def main():
     # `value`: the headline counts evaluations in units of the per-GPU share (1e6 samples at config 3),
     # so that N ranks at weak scaling report N x the single-GPU rate; job lines count whole-job evaluations
     value = evals_per_s * (1.0 if job_mode else ns_job / PER_GPU_NS[a.config])
-    flops = algorithmic_flops(D, K, ns_job / world, grad=True)  # per launch (this rank's rows)
-    achieved = flops / (k_ms * 1e-3) / 1e12
-    achieved_e2e = flops / (ms_per_step * 1e-3) / 1e12
-    # Algorithmic HBM bytes of the entropy launch: the antithetic half of the draws when they are INPUT
-    # (--rng resident: parity mode), ~0 with the device generator.  What the step really moves in Philox mode is reported
-    # beside it (step_hbm_bytes): the generator writes the draws into HBM one evaluation ahead and the kernel reads them
-    # back -- traffic the implementation adds, hidden behind a compute-bound kernel but not algorithmic.
-    draws_bytes = (ns_job / world / 2) * D * 8
-    eps_bytes = draws_bytes if (plan["resident_draws"] and a.rng == "resident") else 0.0
-    step_hbm_bytes = {"generator_writes": draws_bytes if a.rng == "philox" and plan["resident_draws"] else 0.0,
-                      "entropy_kernel_reads": draws_bytes if plan["resident_draws"] else 0.0}
-    traffic, traffic_from = None, None
-    try:  # PMC-measured HBM bytes per launch (separate rocprofv3 --pmc passes, see profiles/README.md)
-        tj = json.load(open(ROOT / "profiles" / "traffic.json"))
-        ent = tj.get(f"config{a.config}" + ("_job" if job_mode and a.config == 5 else ""), {}).get(a.rng)
-        if ent and world == 1:
-            traffic = ent["hbm_bytes_per_launch"]
-            traffic_from = {"file": "profiles/traffic.json", "source": ent.get("source"),
-                            "collected": ent.get("collected"), "how": tj.get("_comment")}
-    except (OSError, ValueError, KeyError):
-        pass
     if headline:
         metric = "ELBO+entropy evals/sec at D=10, K=50, N=400, Ns=1e6 (1e6-sample-equivalent evals/s)"
     elif a.config == 3 and not job_mode:
@@ -565,52 +544,81 @@ def main():
             "parallelism": f"sample-sharded x{world}, 1 RCCL all-reduce/eval" if world > 1 else "single GPU",
             "host_thread": (lambda b, n: f"{'narrowed to' if b else 'left on'} {n} CPUs "
                             f"({'the device-local NUMA node, by vbmc_ctx_create' if b else 'affinity untouched'})")(*ctx.host_affinity()),
-            "timed_region": f"{repeats} x {a.steps} steps back to back (>= {min_timed} s), one barrier + "
-                            f"synchronize on either side",
+            "timed_region": f"{a.steps} steps back to back, one barrier + synchronize on either side",
             "entropy_launch": plan,
         },
-        "roofline": {
-            "kernel": "entmc main kernel (%s)" % plan["kernel"],
-            "bound": "mfma",
-            "bound_detail": "FP64 arithmetic issue.  The kernel executes NO MFMA instruction: it is bound by the "
-                            "float64 vector FMA pipe, whose peak on MI355X equals the dense FP64 matrix peak "
-                            "(78.6 TFLOP/s) -- the label the contract offers for a compute bound; exp/log not "
-                            "counted as flops",
-            "achieved": achieved,
-            "peak": FP64_PEAK_TFLOPS,
-            "unit": "TFLOP/s",
-            "frac": achieved / FP64_PEAK_TFLOPS,
-            "traffic": traffic,
-            "traffic_from": traffic_from,
-            "kernel_ms": k_ms,
-            "kernel_ms_from": f"HIP events on the kernel's own dispatch, read on every {m['sample_every']}th of the {n_timed} "
-                              f"timed steps ({m['n_kern']} launches)",
-            "algorithmic_flops_per_launch": flops,
-            "hbm_bytes_per_launch_algorithmic": eps_bytes,
-            "step_hbm_bytes": step_hbm_bytes,
-            "hbm_achieved_GBs": (eps_bytes / (k_ms * 1e-3) / 1e9) if eps_bytes else 0.0,
-            "hbm_peak_GBs": HBM_PEAK_GBS,
-        },
-        "roofline_e2e": {
-            "what": "the same algorithmic flops over the whole host-driven step (ms_per_step): upload, prep, "
-                    "entropy, finish, host finalisation and Python included",
-            "achieved": achieved_e2e, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-            "frac": achieved_e2e / FP64_PEAK_TFLOPS,
-        },
-        "predict_roofline": predict_roofline,
-        "device_resident_adam_loop": adam_loop,
-        "reference_stream": reference_stream,
-        "gp_samples": gp_samples,
-        "full_elcbo": full_elcbo,
         "F": F,
-        "host_us_per_step": dict(zip(["pack_upload", "launch", "wait_device", "finalize", "c_total"],
-                                     np.asarray(host_us).round(2).tolist())),
     }
+    if a.full:
+        flops = algorithmic_flops(D, K, ns_job / world, grad=True)  # per launch (this rank's rows)
+        achieved = flops / (k_ms * 1e-3) / 1e12
+        achieved_e2e = flops / (ms_per_step * 1e-3) / 1e12
+        # Algorithmic HBM bytes of the entropy launch: the antithetic half of the draws when they are INPUT
+        # (--rng resident: parity mode), ~0 with the device generator.  What the step really moves in Philox mode is reported
+        # beside it (step_hbm_bytes): the generator writes the draws into HBM one evaluation ahead and the kernel reads them
+        # back -- traffic the implementation adds, hidden behind a compute-bound kernel but not algorithmic.
+        draws_bytes = (ns_job / world / 2) * D * 8
+        eps_bytes = draws_bytes if (plan["resident_draws"] and a.rng == "resident") else 0.0
+        step_hbm_bytes = {"generator_writes": draws_bytes if a.rng == "philox" and plan["resident_draws"] else 0.0,
+                          "entropy_kernel_reads": draws_bytes if plan["resident_draws"] else 0.0}
+        traffic, traffic_from = None, None
+        try:  # PMC-measured HBM bytes per launch (separate rocprofv3 --pmc passes, see profiles/README.md)
+            tj = json.load(open(ROOT / "profiles" / "traffic.json"))
+            ent = tj.get(f"config{a.config}" + ("_job" if job_mode and a.config == 5 else ""), {}).get(a.rng)
+            if ent and world == 1:
+                traffic = ent["hbm_bytes_per_launch"]
+                traffic_from = {"file": "profiles/traffic.json", "source": ent.get("source"),
+                                "collected": ent.get("collected"), "how": tj.get("_comment")}
+        except (OSError, ValueError, KeyError):
+            pass
+        res.update({
+            "roofline": {
+                "kernel": "entmc main kernel (%s)" % plan["kernel"],
+                "bound": "mfma",
+                "bound_detail": "FP64 arithmetic issue.  The kernel executes NO MFMA instruction: it is bound by the "
+                                "float64 vector FMA pipe, whose peak on MI355X equals the dense FP64 matrix peak "
+                                "(78.6 TFLOP/s) -- the label the contract offers for a compute bound; exp/log not "
+                                "counted as flops",
+                "achieved": achieved,
+                "peak": FP64_PEAK_TFLOPS,
+                "unit": "TFLOP/s",
+                "frac": achieved / FP64_PEAK_TFLOPS,
+                "traffic": traffic,
+                "traffic_from": traffic_from,
+                "kernel_ms": k_ms,
+                "kernel_ms_from": f"HIP events on the kernel's own dispatch, read on every {SAMPLE_EVERY}th of the {n_timed} "
+                                  f"timed steps ({m['n_kern']} launches)",
+                "algorithmic_flops_per_launch": flops,
+                "hbm_bytes_per_launch_algorithmic": eps_bytes,
+                "step_hbm_bytes": step_hbm_bytes,
+                "hbm_achieved_GBs": (eps_bytes / (k_ms * 1e-3) / 1e9) if eps_bytes else 0.0,
+                "hbm_peak_GBs": HBM_PEAK_GBS,
+            },
+            "roofline_e2e": {
+                "what": "the same algorithmic flops over the whole host-driven step (ms_per_step): upload, prep, "
+                        "entropy, finish, host finalisation and Python included",
+                "achieved": achieved_e2e, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": achieved_e2e / FP64_PEAK_TFLOPS,
+            },
+            "predict_roofline": predict_roofline,
+            "device_resident_adam_loop": adam_loop,
+            "reference_stream": reference_stream,
+            "gp_samples": gp_samples,
+            "full_elcbo": full_elcbo,
+            "host_us_per_step": dict(zip(["pack_upload", "launch", "wait_device", "finalize", "c_total"],
+                                         np.asarray(host_us).round(2).tolist())),
+        })
     if other is not None:
         res[other["scaling"] + "_scaling"] = other
     if cpu_res is not None:
         res["cpu_baseline"] = cpu_res
         res["speedup_vs_cpu_baseline"] = value / cpu_res["value"]
+    if a.dump_outputs and rank == 0:
+        # what the caller of the timed path received from its last step (F, dF, G, H, varF of _neg_elcbo)
+        out_dir = Path(a.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        for name, v in zip(("F", "dF", "G", "H", "varF"), m["out"]):
+            np.save(out_dir / f"{name}.npy", np.asarray(v, dtype=np.float64))
     if rank == 0:
         print(json.dumps(res))
     ctx.close()

@@ -354,6 +354,22 @@ def misc():
     np.savez_compressed(OUT / "misc.npz", **out)
 
 
+def integration():
+    """The four callables INTEGRATION.md's run-time patch replaces: the reference's parameter names
+    and defaults (repr; has_default False where there is none), which the mirrors must repeat so that
+    the reference's own call sites bind the same way."""
+    import inspect
+
+    out = {}
+    for name, fn in (("entmc_vbmc", entmc_vbmc), ("entlb_vbmc", entlb_vbmc), ("_gp_log_joint", _gp_log_joint),
+                     ("_neg_elcbo", _neg_elcbo)):
+        ps = list(inspect.signature(fn).parameters.values())
+        out[f"{name}_params"] = np.array([p.name for p in ps])
+        out[f"{name}_has_default"] = np.array([p.default is not p.empty for p in ps])
+        out[f"{name}_defaults"] = np.array([repr(p.default) if p.default is not p.empty else "" for p in ps])
+    np.savez_compressed(OUT / "integration.npz", **out)
+
+
 def adam():
     """The reference's minimize_adam (vbmc/minimize_adam.py) on (1) a deterministic,
     box-constrained quadratic with a wiggle and (2) the objective PyVBMC gives it,
@@ -786,6 +802,7 @@ if __name__ == "__main__":
         "gpcov": gpcov,
         "matlab_known": matlab_known,
         "misc": misc,
+        "integration": integration,
         "adam": adam,
         "acq": acq,
         "vpmc": vpmc,

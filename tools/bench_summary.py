@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""One screen of a bench.py line: python tools/bench_summary.py <file with the JSON line>"""
+"""One screen of a `bench.py --full` line: python tools/bench_summary.py <file with the JSON line>"""
 import json
 import sys
 

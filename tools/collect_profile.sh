@@ -11,7 +11,7 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-B="python $REPO/bench.py --no-cpu-baseline --min-timed-s 0.5"
+B="python $REPO/bench.py --full --no-cpu-baseline"
 # kernel-trace summaries of the bench command: the headline config (both draw sources), configs 2 and 5 (per-GPU
 # shapes) and the two JOB sizes on one GPU (config 4: Ns = 8e6; config 5 --job: Ns = 4e6)
 # (the headline pass runs the headline's launches only: the secondary figures launch the same kernel instantiation at
@@ -73,9 +73,9 @@ find $OUT -name "*.db" -delete
 find $OUT -type f -size +8M -delete
 # un-profiled bench lines of the same build
 cd $REPO
-python bench.py --steps 200 --warmup 20 > $OUT/bench_c3_philox.json 2>/dev/null
-python bench.py --config 4 --steps 50 --warmup 5 > $OUT/bench_c4job.json 2>/dev/null
-python bench.py --config 5 --job --steps 50 --warmup 5 > $OUT/bench_c5job.json 2>/dev/null
+python bench.py --full --steps 200 --warmup 20 > $OUT/bench_c3_philox.json 2>/dev/null
+python bench.py --full --config 4 --steps 50 --warmup 5 > $OUT/bench_c4job.json 2>/dev/null
+python bench.py --full --config 5 --job --steps 50 --warmup 5 > $OUT/bench_c5job.json 2>/dev/null
 python tools/ws_k_probe.py 10 > $OUT/ws_k_probe_d10.txt 2>/dev/null
 python tools/mfma_probe.py 10 12 16 20 24 32 > $OUT/mfma_probe.txt 2>/dev/null
 VBMC_MFMA_ANY=1 python tools/mfma_c3_probe.py > $OUT/mfma_c3_probe.txt 2>/dev/null
@@ -86,9 +86,9 @@ python tools/adam_batch_probe.py > $OUT/adam_batch_probe.txt 2>/dev/null
 VBMC_FUSED_TIMES=1 python tools/adam_small_probe.py child 2>&1 | awk '/^fused/ {c[$3]++; if (c[$3] % 4 == 1) {print; getline; print}; next} /phase A of/ {next} {print}' > $OUT/fused_phase_times.txt
 ./tools/ubench_gen2 > $OUT/ubench_gen2.txt 2>/dev/null
 ./tools/ubench_mfma_entropy > $OUT/ubench_mfma_entropy.txt 2>/dev/null
-python bench.py --steps 200 --warmup 20 --rng resident --no-secondary > $OUT/bench_c3_resident.json 2>/dev/null
-python bench.py --config 5 --steps 100 --warmup 10 > $OUT/bench_c5.json 2>/dev/null
-python bench.py --config 2 --steps 200 --warmup 20 > $OUT/bench_c2.json 2>/dev/null
+python bench.py --full --steps 200 --warmup 20 --rng resident --no-secondary > $OUT/bench_c3_resident.json 2>/dev/null
+python bench.py --full --config 5 --steps 100 --warmup 10 > $OUT/bench_c5.json 2>/dev/null
+python bench.py --full --config 2 --steps 200 --warmup 20 > $OUT/bench_c2.json 2>/dev/null
 python tools/bench_rows.py > $OUT/rows.json 2>/dev/null
 python tools/gp_probe.py > $OUT/gp_probe.txt 2>/dev/null
 du -sh $OUT; ls $OUT

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Kernel durations of gp.predict at the acquisition batch size (bench.py's predict section) from rocprofv3.
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/pp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 8 --warmup 2 --no-cpu-baseline "$@" > /tmp/pp.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -o p -- python "$REPO/bench.py" --full --steps 8 --warmup 2 --no-cpu-baseline "$@" > /tmp/pp.log 2>&1
 tail -1 /tmp/pp.log | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['predict_roofline'])"
 python - <<PY
 import csv,glob
