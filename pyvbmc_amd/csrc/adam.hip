@@ -23,6 +23,7 @@
 // The Philox draws of iteration i + 1 are produced by spare workgroups of the three short
 // launches, during which the GPU is otherwise idle.  The host only decides when to stop (every
 // batch_size = 20 iterations, as the reference does) from the y_tab / x_tab rows it copies back.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -478,10 +479,11 @@ struct AdamState {
 // K D shapes whose working set is the largest -- have the CU's LDS to themselves (round 6: config 5's own shape, D = 20,
 // K = 100, N = 800, went from 33 to ~15 us per entropy launch of the four-launch iteration).
 static size_t pre_lds_limit(const vbmc_ctx* ctx, const EntPlan& plan) {
-  if (!plan.ws) return 0;
-  if (plan.a.sp.cus == 0 && !entmc_small_applies(plan.a, plan.DP) && ctx->opt_entmc_mfma && entmc_mfma_applies(plan.a, plan.DP))
-    return 158 * 1024;  // (its static arrays are 1 056 B)
-  return ws_min_waves(plan.DP, ws_ktmax_for(ctx->K), true) >= 2 ? 60 * 1024 : 110 * 1024;  // (the widest build holds 38 KB of static LDS)
+  switch (plan.kernel) {
+    case EntKernel::Valu: return 0;
+    case EntKernel::Mfma: return 158 * 1024;  // (its static arrays are 1 056 B)
+    default: return ws_min_waves(plan.DP, ws_ktmax_for(ctx->K), true) >= 2 ? 60 * 1024 : 110 * 1024;  // (the widest build holds 38 KB of static LDS)
+  }
 }
 
 static size_t fused_backup_len(const AdamDev& a) { return (size_t)a.lay.o_hyp() + 2 * (size_t)a.n_theta + (size_t)a.ml.total; }
@@ -723,7 +725,7 @@ extern "C" int vbmc_adam_begin(vbmc_ctx* ctx, const double* theta0, int n_theta,
     HIP_TRY(ctx, hipMemsetAsync(st->d_sync, 0, 16 * sizeof(unsigned long long), sm));
     st->sync_seq = st->tail_launches = 0;
     st->table_valid = false;
-    const int DPp = [&] { const int dps[] = {2, 4, 6, 8, 10, 12, 16, 20, 24, 32}; for (int dp : dps) if (D <= dp) return dp; return 0; }();
+    const int DPp = std::max(padded_d(D), 0);
     const size_t n_tab = (size_t)ws_table_rows(K) * (size_t)DPp;
     st->tail_lds_bytes = sizeof(double) * ((size_t)L.o_hyp() + K + (size_t)ctx->ml.total + n_tab + 2 * (size_t)n_theta);
     st->tail_ok = DPp > 0 && K <= 128 && st->tail_lds_bytes <= 150 * 1024;
@@ -749,7 +751,7 @@ extern "C" int vbmc_adam_begin(vbmc_ctx* ctx, const double* theta0, int n_theta,
     f.a = a;
     f.N = ctx->gp.N;
     f.rows = (int)st->row_count;
-    f.cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+    f.cus = ctx_cus(ctx);
     // (up to 160 rows per component: beyond that the lane-per-component row loop of the fused kernel loses to the wave-split
     // kernel's 64 rows per instruction -- K = 50, D = 10, NsK = 130 / 256 / 1 024 / 4 096: 22.5 / 27.0 / 38.0 / 100 us per
     // iteration against 33.3 / 33.3 / 34.5 / 46.8 with four launches, tools/adam_d20_probe.py)
@@ -815,12 +817,21 @@ static int enqueue_batch(vbmc_ctx* ctx, AdamState* st, int i0, int n_iters, bool
     glj_fill_prep(ctx, 1, st->state + st->lay.o_res(), nullptr, pa);
     EntPlan plan;
     int rc = entmc_plan(ctx, st->ns, use_gen ? VBMC_EPS_RESIDENT : st->eps_mode, st->seed + (uint64_t)(i0 + it),
-                        st->row_begin, st->row_count, 1, plan, try_tail ? pa.n_glj : 0, true, try_tail ? tail_gp_per_slot : 0);
+                        st->row_begin, st->row_count, 1, plan, try_tail ? pa.n_glj : 0, try_tail ? tail_gp_per_slot : 0);
     if (rc) return rc;
     // ---- two launches per iteration (adam_tail_kernel): the wave-split kernel in span mode with the GP sums and the
     // pre workgroup in its free slots, then everything up to the next table in one launch ----
-    if (try_tail && plan.ws && plan.a.sp.cus > 0 && plan.gp_in_ws && pa.n_glj > 0 &&
-        (use_gen || st->eps_mode == VBMC_EPS_RESIDENT)) {
+    PrepArgs gp = pa;
+    gp.n_table = 0;
+    gp.gen = GenSlice();
+    gp.mix = ctx->d_mix;
+    gp.done = DoneSignal();
+    gp.done.cnt = (int*)(st->d_sync + 8);
+    gp.done.flag = (uint64_t*)st->d_sync;
+    gp.done.seq = st->sync_seq + 1;
+    gp.done.dev = 1;
+    if (try_tail && plan.kernel == EntKernel::WsSpan && (use_gen || st->eps_mode == VBMC_EPS_RESIDENT) &&
+        entmc_take_gp(ctx, plan, gp)) {
       if (use_gen) {
         plan.a.eps = st->d_eps1;
         plan.a.eps_rows = st->row_count;
@@ -838,17 +849,6 @@ static int enqueue_batch(vbmc_ctx* ctx, AdamState* st, int i0, int n_iters, bool
         if (rc) return rc;
       }
       const unsigned long long seq = ++st->sync_seq;
-      PrepArgs gp = pa;
-      gp.n_table = 0;
-      gp.gen = GenSlice();
-      gp.mix = ctx->d_mix;
-      gp.done = DoneSignal();
-      gp.done.cnt = (int*)(st->d_sync + 8);
-      gp.done.flag = (uint64_t*)st->d_sync;
-      gp.done.seq = seq;
-      gp.done.dev = 1;
-      plan.a.gp = gp;
-      plan.a.gp_items = gp.n_glj;
       plan.a.extra = st->d_args;
       plan.a.extra_lds = (st->pre_lds && st->pre_lds_bytes <= pre_lds_limit(ctx, plan)) ? (int)(st->pre_lds_bytes / sizeof(double)) : 0;
       rc = entmc_launch_main(ctx, plan);
@@ -900,7 +900,7 @@ static int enqueue_batch(vbmc_ctx* ctx, AdamState* st, int i0, int n_iters, bool
       st->table_valid = true;
       st->eps_have = (use_gen && gen_mode != 0) ? 1.0 : 0.0;
       st->last_form = 2;
-      ctx->last_plan[0] = 6;  // vbmc_last_entmc_plan: the wave-split kernel in span mode inside the two-launch iteration
+      ctx->last_plan[0] = (int)EntKernel::AdamTail;  // (vbmc_last_entmc_plan)
       continue;
     }
     st->table_valid = false;
@@ -918,7 +918,7 @@ static int enqueue_batch(vbmc_ctx* ctx, AdamState* st, int i0, int n_iters, bool
     if (rc) return rc;
     // the entropy-free part of dF: an extra row of the entropy launch when that kernel has one
     // (wave-split, draws from memory), otherwise a launch of its own in front of it
-    const bool pre_row = plan.ws && plan.a.eps_mode != VBMC_EPS_PHILOX;
+    const bool pre_row = plan.tabled() && plan.a.eps_mode != VBMC_EPS_PHILOX;
     if (pre_row) {
       plan.a.extra = st->d_args;
       // its working set in LDS when the launch's entropy workgroups still fit beside it (pre_lds_limit)
@@ -990,7 +990,7 @@ extern "C" int vbmc_adam_run(vbmc_ctx* ctx, int n_iters, double* y_tab_out, doub
       f.times = d_times;
     }
     rc = adam_fused_launch(ctx, ctx->stream, f, st->fused_lds);
-    ctx->last_plan[0] = 4;  // vbmc_last_plan: the fused loop
+    ctx->last_plan[0] = (int)EntKernel::AdamFused;  // (vbmc_last_entmc_plan)
     // (the iterate moves without the other forms' side buffers following it: their table and any draws made ahead are stale)
     st->table_valid = false;
     st->eps_have = 0.0;
@@ -1092,7 +1092,7 @@ extern "C" int vbmc_adam_run_auto(vbmc_ctx* ctx, int max_iters, double tol_fun, 
   HIP_TRY(ctx, hipMemsetAsync(st->d_flags, 0, 512 * sizeof(unsigned long long), ctx->stream));
   int rc = adam_fused_launch(ctx, ctx->stream, f, st->fused_lds);
   if (rc) return rc;
-  ctx->last_plan[0] = 4;
+  ctx->last_plan[0] = (int)EntKernel::AdamFused;
   int word[3] = {0, 0, 0};
   HIP_TRY(ctx, hipMemcpyAsync(word, st->d_status, 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));

@@ -244,7 +244,8 @@ extern "C" int vbmc_neg_elcbo(vbmc_ctx* ctx, double* theta, int n_theta,
     }
     const bool ahead_ok = can_poll && opts->eps_mode == VBMC_EPS_PHILOX && ctx->opt_elbo_ahead &&
                           plan.a.eps != nullptr && plan.a.eps == ctx->d_epsgen[ctx->gen_cur];
-    if (spin && !(ahead_ok && plan.pregen_hit && plan.ws && !entmc_small_applies(plan.a, plan.DP)))
+    const bool ws_form = plan.kernel == EntKernel::Ws || plan.kernel == EntKernel::WsSpan || plan.kernel == EntKernel::Mfma;
+    if (spin && !(ahead_ok && plan.pregen_hit && ws_form))
       return -1000;  // (not a shape to arm: the caller restores the bookkeeping)
     if (can_poll) {
       pa.done.cnt = ctx->d_done_cnt + 8;
@@ -261,7 +262,6 @@ extern "C" int vbmc_neg_elcbo(vbmc_ctx* ctx, double* theta, int n_theta,
     ctx->gp_where = 0;
     // Polled step: the CPU writes the pack into device memory itself (no upload launch; the prep
     // launch copies it on for the later kernels).
-    PrepArgs gp_tail;
     double* fg = nullptr;
     if (can_poll && ctx->opt_mix_bar) fg = spin ? ctx->d_mix_fg : write_pack_to_device(ctx);
     if (spin && !fg) return -1000;
@@ -274,26 +274,15 @@ extern "C" int vbmc_neg_elcbo(vbmc_ctx* ctx, double* theta, int n_theta,
       // placement 225 us -- the finish placement was dropped in round 4).
       // (Few slots carry them: beyond ~6 items per slot they would outlast the entropy kernel -- S = 4 hyper-parameter
       // samples took 186 us per step against 114 with the prep placement -- so larger S keeps the prep launch.)
-      bool in_ws = false;
-      if (plan.a.sp.cus > 0) {
-        in_ws = plan.gp_in_ws && pa.n_glj > 0;  // span mode: the plan reserved the slots
-      } else if (pa.n_glj > 0 && plan.ws && !entmc_small_applies(plan.a, plan.DP)) {
-        const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-        const int slots = cus * ws_min_waves(plan.DP, ws_ktmax_for(K), grad_flags != 0);
-        const int free_slots = slots - K * plan.a.chunks;
-        in_ws = free_slots >= plan.a.chunks && pa.n_glj <= 6 * plan.a.chunks;
-      }
-      if (pa.n_glj > 0 && in_ws) {
-        gp_tail = pa;
-        gp_tail.n_table = 0;
-        gp_tail.gen = GenSlice();
-        gp_tail.mix = ctx->d_mix;
+      PrepArgs gp_tail = pa;
+      gp_tail.n_table = 0;
+      gp_tail.gen = GenSlice();
+      gp_tail.mix = ctx->d_mix;
+      if (entmc_take_gp(ctx, plan, gp_tail)) {
         pa.n_glj = 0;
-        plan.a.gp = gp_tail;
-        plan.a.gp_items = gp_tail.n_glj;
         ctx->gp_where = 2;
       }
-      if (mc && pa.n_glj > 0 && pa.done.flag != nullptr && ctx->opt_gp_ship && entmc_uses_mfma(ctx, plan)) {
+      if (mc && pa.n_glj > 0 && pa.done.flag != nullptr && ctx->opt_gp_ship && plan.kernel == EntKernel::Mfma) {
         // GP sums in the prep launch in front of the matrix-pipe kernel (config 5's shape): their hand-over to pinned memory
         // and the word ride in the entropy launch (EntArgs::ship_*): the prep launch ends with the sums, not with the 6 us
         // of its last block's PCIe copy
@@ -340,7 +329,7 @@ extern "C" int vbmc_neg_elcbo(vbmc_ctx* ctx, double* theta, int n_theta,
         done.cnt = ctx->d_done_cnt;
         done.sub = ctx->d_done_sub;
         {
-          static const int sub_min = [] { const char* e = getenv("VBMC_FIN_SUB_MIN"); return e ? atoi(e) : 256; }();  // measurement aid
+          static const int sub_min = [] { const char* e = getenv("VBMC_FIN_SUB_MIN"); return e ? atoi(e) : 256; }();  // measurement aid (entmc_launch_finish keeps it >= 16)
           done.sub_min = sub_min;
         }
         done.flag = ctx->hd_done;

@@ -233,6 +233,8 @@ struct vbmc_ctx {
   int randn_last_reused = 0;  // the last device pass found its window in the pass before (device_randn.hip)
   int opt_randn_dev = 1;      // vbmc_set_eps_numpy: the reference's stream generated on the device (0: on the host cores + PCIe)
 };
+// the device's CU count, which sizes one round of workgroups (256 where the runtime reports none)
+inline int ctx_cus(const vbmc_ctx* ctx) { return ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256; }
 int vbmc_live_contexts_on(int device);  // ctx.hip
 void adam_free(vbmc_ctx* ctx);
 void acq_is_free(vbmc_ctx* ctx);
@@ -437,12 +439,16 @@ int launch_prep_on(vbmc_ctx* ctx, hipStream_t stream, const PrepArgs& a);
 
 // staged launch of the Monte-Carlo entropy (entropy.hip)
 struct EntPlan;
-// gp_items: GP expected-log-joint items the caller would like this launch to carry in spare workgroup slots (the plan
-// says whether it does: EntPlan::gp_in_ws); allow_span = false keeps the chunk grid (no caller does: the optimiser loop's pre
-// workgroup is the LAST block of a span-mode launch and finds one of the slots the plan leaves free)
+// entmc_plan decides the geometry and which kernel runs (EntPlan::kernel).
+// gp_items: GP expected-log-joint items the caller would like a span-mode launch to carry in spare workgroup slots (the
+// plan says whether they fit: EntPlan::gp_in_ws; the optimiser loop's pre workgroup is the LAST block of a span-mode launch
+// and finds one of the slots the plan leaves free)
 // gp_per_slot > 0 (the optimiser loop): that many items per workgroup and one more free slot, for its pre workgroup
 int entmc_plan(vbmc_ctx* ctx, int64_t ns_per_comp, int eps_mode, uint64_t seed, int64_t row_begin,
-               int64_t row_count, int want_grad, EntPlan& p, int gp_items = 0, bool allow_span = true, int gp_per_slot = 0);
+               int64_t row_count, int want_grad, EntPlan& p, int gp_items = 0, int gp_per_slot = 0);
+// attach the GP sums `gp` (gp.n_glj items) to the plan's entropy launch when they fit its spare workgroup slots; returns
+// whether they ride there (the plan is untouched when not)
+bool entmc_take_gp(const vbmc_ctx* ctx, EntPlan& p, const PrepArgs& gp);
 void entmc_fill_prep(const vbmc_ctx* ctx, const EntPlan& p, PrepArgs& a);
 int entmc_pregen(vbmc_ctx* ctx, EntPlan& p, PrepArgs& a);
 

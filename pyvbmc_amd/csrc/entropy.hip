@@ -382,13 +382,6 @@ static bool use_ws_kernel(const vbmc_ctx* ctx, int D, int K) {
   return D <= 32 && K <= 128;
 }
 
-static int padded_d(int D) {
-  const int dps[] = {2, 4, 6, 8, 10, 12, 16, 20, 24, 32};
-  for (int dp : dps)
-    if (D <= dp) return dp;
-  return -1;
-}
-
 // Span mode: the front workgroup's share of a CU's batches, per mille (entropy_args.h WsSpan) -- the fraction of the
 // issue slots one wave per SIMD of this instantiation uses when it runs alone.  Read off tools/ws_front_probe.py
 // (kernel time over the share, every padded D x register-array size of the 2-waves/SIMD builds, value and value +
@@ -401,9 +394,9 @@ static int ws_front_default(int DP, int KT) {
   return 660;  // (one wave per SIMD: no filler parts, the value is not used)
 }
 
-// Decide the launch geometry and carve the scratch buffer.
+// Decide the kernel and its launch geometry and carve the scratch buffer.
 int entmc_plan(vbmc_ctx* ctx, int64_t ns_per_comp, int eps_mode, uint64_t seed, int64_t row_begin,
-               int64_t row_count, int want_grad, EntPlan& p, int gp_items, bool allow_span, int gp_per_slot) {
+               int64_t row_count, int want_grad, EntPlan& p, int gp_items, int gp_per_slot) {
   const int D = ctx->D, K = ctx->K;
   p.DP = padded_d(D);
   if (p.DP < 0) return vbmc_fail(ctx, VBMC_E_UNSUP, "entmc: D=%d > 32 not supported", D);
@@ -418,17 +411,17 @@ int entmc_plan(vbmc_ctx* ctx, int64_t ns_per_comp, int eps_mode, uint64_t seed, 
   a.seed = seed;
   a.eps_mode = eps_mode;
   a.want_grad = want_grad;
-  p.ws = use_ws_kernel(ctx, D, K);
+  const bool ws = use_ws_kernel(ctx, D, K);  // the wave-split kernel or one of its forms, on the (j,k) table
+  const int cus = ctx_cus(ctx);
   p.inv_ns = 1.0 / (double)ns_per_comp;
   int rows_per_wg = WG;
   a.rg = 1;
   size_t n_table = 0;
-  if (p.ws) {
+  if (ws) {
     // 64*rg rows per workgroup.  Two workgroups are resident per CU (2 waves/SIMD): size
     // the grid to about one full round of 2*CUs workgroups, which also amortises the
     // end-of-workgroup reductions over many batches.
     const int64_t total_rows = row_count * K;
-    const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
     int64_t rg = (total_rows + 64 * 2 * cus - 1) / (64 * 2 * cus);
     if (rg < 1) rg = 1;
     if (rg > 16) rg = 16;
@@ -438,12 +431,11 @@ int entmc_plan(vbmc_ctx* ctx, int64_t ns_per_comp, int eps_mode, uint64_t seed, 
   }
   a.chunks = (int)((row_count + rows_per_wg - 1) / rows_per_wg);
   if (a.chunks < 1) a.chunks = 1;
-  if (p.ws) {
+  if (ws) {
     // chunks are per component: rounding them up can push K * chunks just past one round of resident
     // workgroups (K = 52, 10 000 rows: 10 chunks of 1 024 rows = 520 workgroups for 512 slots, a second
     // round of 8).  A few more batches per workgroup keep the grid in one round.
-    const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-    const int64_t slots = cus * ws_min_waves(p.DP, ws_ktmax_for(K), want_grad != 0);
+    const int64_t slots = (int64_t)cus * ws_min_waves(p.DP, ws_ktmax_for(K), want_grad != 0);
     const int64_t fit = slots / K;  // chunks per component that fit one round
     if (fit >= 1 && a.chunks > fit && (int64_t)K * (a.chunks - 1) <= slots) {
       const int64_t rg2 = (row_count + 64 * fit - 1) / (64 * fit);
@@ -455,32 +447,34 @@ int entmc_plan(vbmc_ctx* ctx, int64_t ns_per_comp, int eps_mode, uint64_t seed, 
     }
   }
   a.pair_cus = 0;
-  if (p.ws) {
+  if (ws) {
     // one round of the 2-waves/SIMD build: workgroups b and b + CUs share a CU (entropy_ws.hip)
-    const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
     const int64_t total = (int64_t)K * a.chunks;
     if (ws_min_waves(p.DP, ws_ktmax_for(K), want_grad != 0) == 2 && total > cus && total <= 2 * (int64_t)cus)
       a.pair_cus = cus;
   }
-  // Span mode (entropy_args.h WsSpan): every CU gets a front part, all but the GP row's a filler part, sized so that
-  // they end together.  Used when the launch is the plain wave-split kernel (not its matrix-pipe or small-count forms)
-  // and a part is at least a few batches long.
-  a.sp = WsSpan();
-  a.gp_wgs = 0;
-  p.gp_in_ws = false;
-  EntArgs at_launch = a;  // (Philox draws generated ahead of the kernel reach it as resident draws: entmc_pregen)
+  // The kernel, chosen on the draw source it will see: Philox draws generated ahead of it (entmc_pregen) reach it as
+  // resident draws, and resident draws may come in a buffer the caller fills in after planning (the optimiser loop's own).
+  EntArgs at_launch = a;
   {
     const size_t n_eps = (size_t)K * (size_t)row_count * D;
     if (eps_mode == VBMC_EPS_PHILOX && ctx->opt_elbo_pregen && n_eps > 0 && n_eps <= ((size_t)1 << 28)) {
       at_launch.eps_mode = VBMC_EPS_RESIDENT;
       at_launch.eps = (const double*)ctx;  // any non-null address: only tested
     }
-    // (resident draws whose buffer the caller fills in after planning: the optimiser loop's own)
     if (at_launch.eps_mode == VBMC_EPS_RESIDENT && at_launch.eps == nullptr) at_launch.eps = (const double*)ctx;
   }
-  if (p.ws && allow_span && ctx->opt_ws_span && !entmc_small_applies(at_launch, p.DP) &&
-      !(ctx->opt_entmc_mfma && entmc_mfma_applies(at_launch, p.DP))) {
-    const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  p.kernel = !ws                                                          ? EntKernel::Valu
+             : entmc_small_applies(at_launch, p.DP)                       ? EntKernel::Small
+             : ctx->opt_entmc_mfma && entmc_mfma_applies(at_launch, p.DP) ? EntKernel::Mfma
+                                                                          : EntKernel::Ws;
+  // Span mode (entropy_args.h WsSpan): every CU gets a front part, all but the GP row's a filler part, sized so that
+  // they end together.  Used when the launch is the plain wave-split kernel (not its matrix-pipe or small-count forms)
+  // and a part is at least a few batches long.
+  a.sp = WsSpan();
+  a.gp_wgs = 0;
+  p.gp_in_ws = false;
+  if (p.kernel == EntKernel::Ws && ctx->opt_ws_span) {
     const int waves = ws_min_waves(p.DP, ws_ktmax_for(K), want_grad != 0);
     WsSpan sp;
     sp.cus = cus;
@@ -545,6 +539,7 @@ int entmc_plan(vbmc_ctx* ctx, int64_t ns_per_comp, int eps_mode, uint64_t seed, 
       a.chunks = R;
       a.rg = longest;
       a.pair_cus = 0;
+      p.kernel = EntKernel::WsSpan;
       if (gp_here) {
         a.gp_wgs = gp_wgs;
         p.gp_in_ws = true;
@@ -556,8 +551,29 @@ int entmc_plan(vbmc_ctx* ctx, int64_t ns_per_comp, int eps_mode, uint64_t seed, 
   int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, n_part + n_table);
   if (rc) return rc;
   a.partial = ctx->d_scratch;
-  p.table = p.ws ? ctx->d_scratch + n_part : nullptr;
+  p.table = ws ? ctx->d_scratch + n_part : nullptr;
   return 0;
+}
+
+// Where the GP sums ride: span mode in the slots entmc_plan reserved; a chunk grid (wave-split kernel or its matrix-pipe
+// form) in one more grid row when the launch leaves that many workgroup slots free and the row has at most six items per
+// workgroup.  The matrix-pipe form has no such row: with riders the launch is the wave-split kernel.
+bool entmc_take_gp(const vbmc_ctx* ctx, EntPlan& p, const PrepArgs& gp) {
+  if (gp.n_glj <= 0) return false;
+  EntArgs& a = p.a;
+  bool in_ws = false;
+  if (p.kernel == EntKernel::WsSpan) {
+    in_ws = p.gp_in_ws;
+  } else if (p.kernel == EntKernel::Ws || p.kernel == EntKernel::Mfma) {
+    const int slots = ctx_cus(ctx) * ws_min_waves(p.DP, ws_ktmax_for(ctx->K), a.want_grad != 0);
+    const int free_slots = slots - ctx->K * a.chunks;
+    in_ws = free_slots >= a.chunks && gp.n_glj <= 6 * a.chunks;
+  }
+  if (!in_ws) return false;
+  a.gp = gp;
+  a.gp_items = gp.n_glj;
+  if (p.kernel == EntKernel::Mfma) p.kernel = EntKernel::Ws;
+  return true;
 }
 
 // Host-only view of the span arithmetic (the CPU suite checks its invariants; the kernels use the same struct).
@@ -586,7 +602,7 @@ extern "C" int vbmc_ws_span_layout(int cus, int pb, int front, int nb, int pad, 
 void entmc_fill_prep(const vbmc_ctx* ctx, const EntPlan& p, PrepArgs& a) {
   a.mix = ctx->d_mix;
   a.ml = ctx->ml;
-  if (p.ws) {
+  if (p.tabled()) {
     a.n_table = ctx->K;
     a.DP = p.DP;
     a.K4 = ws_table_rows(ctx->K);
@@ -653,46 +669,36 @@ GenSlice entmc_ahead_slice(vbmc_ctx* ctx, const EntPlan& p) {
   return make_gen_slice(ctx->d_epsgen[other], K, D, a.row_count, a.n_half, a.row_begin, ah.seed, nullptr, 0.0, frac_end);
 }
 
-bool entmc_uses_mfma(const vbmc_ctx* ctx, const EntPlan& p) {
-  return p.ws && p.a.sp.cus == 0 && !entmc_small_applies(p.a, p.DP) && ctx->opt_entmc_mfma && entmc_mfma_applies(p.a, p.DP);
-}
-
 int entmc_launch_main(vbmc_ctx* ctx, const EntPlan& p) {
   const EntArgs& a = p.a;
   // timing: the wave-split launch carries the event pair on its own dispatch packet; the generic
   // kernel is bracketed by two records (each a barrier packet, ~6 us between dependent kernels)
   hipEvent_t e0 = ctx->timing ? ctx->ev[0] : nullptr, e1 = ctx->timing ? ctx->ev[1] : nullptr;
-  const bool small = p.ws && a.sp.cus == 0 && entmc_small_applies(a, p.DP);  // (a span-mode plan is the wave-split kernel's)
-  const bool mfma = p.ws && a.sp.cus == 0 && !small && ctx->opt_entmc_mfma && entmc_mfma_applies(a, p.DP);
-  ctx->last_plan[0] = small ? 2 : mfma ? 3 : (p.ws ? (a.sp.cus > 0 ? 5 : 1) : 0);  // (5: the wave-split kernel in span mode)
+  ctx->last_plan[0] = (int)p.kernel;
   ctx->last_plan[1] = a.rg;
   ctx->last_plan[2] = a.chunks;
   ctx->last_plan[3] = a.eps_mode == VBMC_EPS_RESIDENT ? 1 : 0;
-  const bool bracket = ctx->timing && (!p.ws || small);
+  const bool bracket = ctx->timing && (p.kernel == EntKernel::Valu || p.kernel == EntKernel::Small);
   if (bracket) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-  if (small) {
-    launch_entmc_small(ctx->stream, a, p.DP, p.table);
-  } else if (mfma) {
-    launch_entmc_mfma(ctx->stream, a, p.DP, p.table, e0, e1);
-  } else if (p.ws) {
-    switch (p.DP) {
+  switch (p.kernel) {
+    case EntKernel::Small: launch_entmc_small(ctx->stream, a, p.DP, p.table); break;
+    case EntKernel::Mfma: launch_entmc_mfma(ctx->stream, a, p.DP, p.table, e0, e1); break;
+    case EntKernel::Ws:
+    case EntKernel::WsSpan:
+      switch (p.DP) {
 #define VBMC_CASE_WS(dp) case dp: launch_entmc_ws_dp##dp(ctx->stream, a, p.table, e0, e1); break;
-      VBMC_WS_DPS(VBMC_CASE_WS)
+        VBMC_WS_DPS(VBMC_CASE_WS)
 #undef VBMC_CASE_WS
-    }
-  } else {
-    switch (p.DP) {
-      case 2: launch_entmc_dp<2>(ctx, a); break;
-      case 4: launch_entmc_dp<4>(ctx, a); break;
-      case 6: launch_entmc_dp<6>(ctx, a); break;
-      case 8: launch_entmc_dp<8>(ctx, a); break;
-      case 10: launch_entmc_dp<10>(ctx, a); break;
-      case 12: launch_entmc_dp<12>(ctx, a); break;
-      case 16: launch_entmc_dp<16>(ctx, a); break;
-      case 20: launch_entmc_dp<20>(ctx, a); break;
-      case 24: launch_entmc_dp<24>(ctx, a); break;
-      default: launch_entmc_dp<32>(ctx, a); break;
-    }
+      }
+      break;
+    case EntKernel::Valu:
+      switch (p.DP) {
+#define VBMC_CASE_VALU(dp) case dp: launch_entmc_dp<dp>(ctx, a); break;
+        VBMC_WS_DPS(VBMC_CASE_VALU)
+#undef VBMC_CASE_VALU
+      }
+      break;
+    default: return vbmc_fail(ctx, VBMC_E_ARG, "entmc: plan names no entropy kernel (%d)", (int)p.kernel);
   }
   if (ctx->timing) {
     if (bracket) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
@@ -768,10 +774,11 @@ int entmc_launch_finish(vbmc_ctx* ctx, const EntPlan& p, double* raw_out, const 
   if ((uint64_t)ctx->K * (uint64_t)p.a.chunks * (uint64_t)p.a.stride >= ((uint64_t)1 << 31))
     return vbmc_fail(ctx, VBMC_E_UNSUP, "entropy: partial block of %d x %d rows too large", ctx->K, p.a.chunks);
   const GenSlice g = gen ? *gen : GenSlice();
-  const DoneSignal ds = done ? *done : DoneSignal();
+  DoneSignal ds = done ? *done : DoneSignal();
+  ds.sub_min = std::max(ds.sub_min, FIN_SUB_COUNTERS);
   hipLaunchKernelGGL(entmc_finish_kernel, dim3((n_out + 3) / 4 + g.n_blocks), dim3(256), 0, ctx->stream,
                      p.a.partial, p.a.chunks, p.a.stride, ctx->d_mix, ctx->ml, p.inv_ns,
-                     p.a.want_grad, p.ws ? 1 : 0, raw_out, g, ds);
+                     p.a.want_grad, p.tabled() ? 1 : 0, raw_out, g, ds);
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }

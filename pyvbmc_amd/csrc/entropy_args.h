@@ -119,19 +119,31 @@ constexpr int ws_min_waves(int dp, int ktmax, bool grad) {
 #endif
 }
 
+// Which entropy kernel runs.  The values are the codes vbmc_last_entmc_plan reports (_lib.py decodes them); a plan holds
+// one of the first four or WsSpan, the optimiser loop reports its own two forms.
+enum class EntKernel : int { Valu = 0, Ws = 1, Small = 2, Mfma = 3, AdamFused = 4, WsSpan = 5, AdamTail = 6 };
+
 struct EntPlan {
   EntArgs a;
+  EntKernel kernel = EntKernel::Valu;  // chosen by entmc_plan; entmc_take_gp turns Mfma into Ws when GP sums ride
   bool gp_in_ws = false;    // span mode: the plan left workgroup slots for the GP sums (a.gp_wgs of them)
   bool pregen_hit = false;  // the draws come from a speculative generation (entmc_pregen)
-  bool ws = false;
   int DP = 0;
   double inv_ns = 0.0;
-  double* table = nullptr;  // ws only
+  double* table = nullptr;  // every kernel but Valu reads the (j,k) table
+  bool tabled() const { return kernel != EntKernel::Valu; }
 };
 
 // padded-D instantiations of the wave-split kernel (entropy_ws.hip), one translation
 // unit each; d_table: K * ws_table_rows(K) * (dp+6) doubles of scratch for the (j,k) table
 #define VBMC_WS_DPS(X) X(2) X(4) X(6) X(8) X(10) X(12) X(16) X(20) X(24) X(32)
+// the padded D of the entropy kernels and their table: the smallest entry of VBMC_WS_DPS >= D (-1: D > 32)
+inline int padded_d(int D) {
+#define VBMC_PAD_D(dp) if (D <= dp) return dp;
+  VBMC_WS_DPS(VBMC_PAD_D)
+#undef VBMC_PAD_D
+  return -1;
+}
 // e0 / e1 (may be null): HIP events that take the start / stop timestamps of the dispatch itself
 // (hipExtLaunchKernel) -- unlike hipEventRecord they put no barrier packet between dependent kernels
 #define VBMC_DECL_WS(dp) \
@@ -142,8 +154,6 @@ VBMC_WS_DPS(VBMC_DECL_WS)
 // matrix-pipe form for shapes the 16 x 16 x 4 tile pads little (entropy_mfma.hip: D = 20, K up to 112 -- BASELINE
 // config 5); same table, same partial rows
 bool entmc_mfma_applies(const EntArgs& a, int DP);
-struct vbmc_ctx;
-bool entmc_uses_mfma(const vbmc_ctx* ctx, const EntPlan& p);  // entmc_launch_main's choice for this plan (entropy.hip)
 void launch_entmc_mfma(hipStream_t st, const EntArgs& a, int DP, const double* d_table, hipEvent_t e0, hipEvent_t e1);
 
 // small sample counts: lane = component (entropy_small.hip); same table, same partial rows

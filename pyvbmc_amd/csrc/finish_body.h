@@ -21,6 +21,9 @@ __device__ unsigned long long g_fin_x[8];
 #else
 #define FIN_X_MAX(i) (void)0
 #endif
+// DoneSignal::sub: the sub-counters the workgroups count on.  Each must see at least one workgroup, or `cnt` stops short
+// of its target and nothing is published: the host raises DoneSignal::sub_min to at least this (entmc_launch_finish).
+constexpr int FIN_SUB_COUNTERS = 16;
 // (the body of entmc_finish_kernel, entropy.hip; also the first blocks of the optimiser loop's tail launch, adam.hip)
 __device__ __forceinline__ void entmc_finish_body(const double* __restrict__ partial, int chunks, int stride,
                                                   const double* __restrict__ mix, const MixLayout& ml, double inv_ns,
@@ -153,7 +156,7 @@ __device__ __forceinline__ void entmc_finish_body(const double* __restrict__ par
   if (threadIdx.x == 0) {
     const int n_main = (n + 3) / 4;
     if (done.sub != nullptr && n_main >= done.sub_min) {  // (DoneSignal::sub: one word takes ~88 increments per us)
-      constexpr int NS = 16;
+      constexpr int NS = FIN_SUB_COUNTERS;
       const int g = (int)blockIdx.x % NS, n_g = (n_main - g + NS - 1) / NS;
       int* sc = done.sub + g * 64;
       bool last = false;

@@ -1199,7 +1199,7 @@ int launch_gp_predict_products(vbmc_ctx* ctx, int64_t M, const double* d_xs, dou
   // M = 8192, S = 1: 61.1 -> 59.6 us between events; S = 4 (four rounds): 187 -> 205 us, so those keep the finish
   // launch.  Not while the product alone is being timed (vbmc_set_timing(2)).
   const int fuse_mode = ctx->opt_predict_fused;
-  const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int cus = ctx_cus(ctx);
   const int nprod = 8 * (((G + 1) / 2 + 7) / 8) * (ntiles + 1);
   if (dma && fin_v != nullptr && ctx->timing < 2 && (fuse_mode == 2 || (fuse_mode == 1 && nprod <= 2 * cus))) {
     const int rc = ensure_dev(ctx, &ctx->d_ptick, &ctx->d_ptick_cap, (size_t)(G + 1) / 2 + 1);
