@@ -595,6 +595,52 @@ int vbmc_kl_div_mc(vbmc_ctx* ctx, int64_t N, uint64_t seed, int K2, const double
                    const double* sigma2_K, const double* lambd2_D, const double* w2_K,
                    double kl_out[2]);
 
+/* ---- parameter transformer (parameter_transformer/parameter_transformer.py) ----
+ *
+ * The reference's ParameterTransformer on the device, so that VariationalPosterior's original-space
+ * calls run there.  A ctx holds two descriptors: slot 0 belongs to the ctx mixture, slot 1 to the second
+ * mixture of vbmc_kl_div_mc_orig.  The descriptor is the transformer's fields: per-dimension type_D
+ * (0 unbounded, 3 logit, 12 probit, 13 student4 -- the reference's float codes, :81-114), lb / ub
+ * (lb_orig / ub_orig), mu / delta (the centring), and the optional rotoscaling R_mat (D x D, row-major)
+ * and scale (D); pass NULL for a field the transformer holds as None.  Bounded dimensions need finite
+ * lb < ub.  D <= 32 (VBMC_E_UNSUP above).  Setting the values a slot already holds uploads nothing. */
+int vbmc_set_transformer(vbmc_ctx* ctx, int slot, int D, const double* type_D, const double* lb_D,
+                         const double* ub_D, const double* mu_D, const double* delta_D,
+                         const double* R_DxD, const double* scale_D);
+int vbmc_clear_transformer(vbmc_ctx* ctx, int slot);
+
+/* Slot 0's transformer on n host points: direction 0 = __call__ (x -> u, out n x D), 1 = inverse
+ * (u -> x, out n x D), 2 = log_abs_det_jacobian (u, out n) (:135-269). */
+enum { VBMC_XF_FORWARD = 0, VBMC_XF_INVERSE = 1, VBMC_XF_LOG_ABS_DET = 2 };
+int vbmc_transform(vbmc_ctx* ctx, int64_t n, int direction, const double* in_nxD, double* out);
+
+/* vbmc_mixture_sample_t's samples (same Philox stream, same seed -> same transformed draws), returned
+ * through slot 0's inverse: VariationalPosterior.sample(orig_flag=True) (:355-362). */
+int vbmc_mixture_sample_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed, int balance_flag, double df,
+                             double* x_NxD, int32_t* comp_N);
+
+/* VariationalPosterior.pdf(orig_flag=True) (:429-439, :543-559): rows strictly inside slot 0's bounds
+ * (every dimension) are transformed, their density taken in u and log|J| subtracted (log_flag) or
+ * exp(log|J|) divided out; rows outside are 0 / -inf, their density (and gradient row) taken at the
+ * original coordinates with non-finite ones replaced by 0.  dy: the transformed-space gradient rows,
+ * as the reference returns them.  log_flag with grad_flag is VBMC_E_UNSUP, as in the reference. */
+int vbmc_mixture_pdf_orig(vbmc_ctx* ctx, int64_t n, const double* x_nxD, int log_flag, int grad_flag,
+                          double df, double* y_n, double* dy_nxD);
+
+/* VariationalPosterior.moments(orig_flag=True) (:791-796): N balanced samples (vbmc_mixture_sample_orig's,
+ * balance_flag = 1) inverse-transformed, their mean and (cov_flag) the two-pass ddof = 1 covariance of
+ * np.cov, on the device.  cov_DxD is written in full (symmetric). */
+int vbmc_mixture_moments_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed, int cov_flag, double* mean_D,
+                              double* cov_DxD);
+
+/* vbmc_kl_div_mc between posteriors with different transformers (slot 0: the ctx mixture's, slot 1: the
+ * second mixture's), in original space as the reference computes it (:1107-1126): samples of each mixture
+ * (seed, seed + 1) through their own inverse, then both densities in their own transformed spaces with
+ * their Jacobians and bound masks, the zero-replacement rules, kl_out = max(0, [KL12, KL21]). */
+int vbmc_kl_div_mc_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed, int K2, const double* mu2_KxD,
+                        const double* sigma2_K, const double* lambd2_D, const double* w2_K,
+                        double kl_out[2]);
+
 /* ---- multi-GPU: one process per GPU, one collective ---------- */
 
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by

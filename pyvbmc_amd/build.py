@@ -30,6 +30,7 @@ SOURCES = [
     "api_acq.hip",
     "api_acq_is.hip",
     "sample.hip",
+    "transform.hip",
     "comm.hip",
     "host_randn.hip",
     "device_randn.hip",

@@ -232,6 +232,7 @@ struct vbmc_ctx {
   void* randn_dev = nullptr;  // buffers of the device-side NumPy stream (device_randn.hip)
   int randn_last_reused = 0;  // the last device pass found its window in the pass before (device_randn.hip)
   int opt_randn_dev = 1;      // vbmc_set_eps_numpy: the reference's stream generated on the device (0: on the host cores + PCIe)
+  void* xf = nullptr;         // parameter-transformer descriptors, two slots (transform.hip)
 };
 // the device's CU count, which sizes one round of workgroups (256 where the runtime reports none)
 inline int ctx_cus(const vbmc_ctx* ctx) { return ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256; }
@@ -239,6 +240,7 @@ int vbmc_live_contexts_on(int device);  // ctx.hip
 void adam_free(vbmc_ctx* ctx);
 void acq_is_free(vbmc_ctx* ctx);
 void randn_dev_free(vbmc_ctx* ctx);
+void xf_free(vbmc_ctx* ctx);  // transform.hip
 // device_randn.hip: the next n values of NumPy's legacy randn stream into d_out (device memory), state advanced as
 // vbmc_mt19937_randn does; VBMC_W_NOT_FUSED = not this path's size (the caller uses the host generator)
 int randn_device(vbmc_ctx* ctx, uint32_t* key, int* pos, int* has_gauss, double* gauss, double* d_out, int64_t n);
@@ -477,6 +479,11 @@ int launch_mixture_pdf(vbmc_ctx* ctx, int64_t n, const double* d_x, int log_flag
                        int grad_flag, double df, double* d_y, double* d_dy);
 int launch_mixture_pdf_on(vbmc_ctx* ctx, const double* d_pack, const MixLayout& ml, int64_t n,
                           const double* d_x, int log_flag, double* d_y);
+// sampling (sample.hip): N draws of the mixture `d_pack` (selection vectors through d_sel, (K+1) int64 + K doubles)
+int launch_sample(vbmc_ctx* ctx, const double* d_pack, const MixLayout& ml, const double* w_host, int64_t N,
+                  uint64_t seed, int balance, void* d_sel, double* d_x, int32_t* d_comp, double df = INFINITY);
+// per-block partial sums of log q_other - log q_own with kl_div's zero-replacement rules (nblk blocks)
+int launch_kl_terms(vbmc_ctx* ctx, const double* d_y_own, const double* d_y_other, int64_t n, int nblk, double* d_part);
 // gp
 int launch_gp_log_joint(vbmc_ctx* ctx, int want_grad, double* d_res, double* d_Z);
 int launch_gp_var(vbmc_ctx* ctx, const double* d_Z, double* d_V, double* d_Q);

@@ -193,11 +193,13 @@ void make_selector(const double* w, int K, int64_t N, int balance, Selector& s) 
   s.cdf[K - 1] = 2.0;  // the last component catches rounding in the cumulative sum
 }
 
+}  // namespace
+
 // Draw N samples of `d_pack` into d_x (device), optionally labels into d_comp.
 // d_sel: device scratch of (K+1) int64 + K doubles.
 int launch_sample(vbmc_ctx* ctx, const double* d_pack, const MixLayout& ml, const double* w_host,
                   int64_t N, uint64_t seed, int balance, void* d_sel, double* d_x, int32_t* d_comp,
-                  double df = INFINITY) {
+                  double df) {
   const int K = ml.K;
   Selector s;
   make_selector(w_host, K, N, balance, s);
@@ -222,7 +224,11 @@ int launch_sample(vbmc_ctx* ctx, const double* d_pack, const MixLayout& ml, cons
   return 0;
 }
 
-}  // namespace
+int launch_kl_terms(vbmc_ctx* ctx, const double* d_y_own, const double* d_y_other, int64_t n, int nblk, double* d_part) {
+  hipLaunchKernelGGL(kl_terms_kernel, dim3(nblk), dim3(256), 0, ctx->stream, d_y_own, d_y_other, n, d_part);
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
+}
 
 extern "C" int vbmc_mixture_sample(vbmc_ctx* ctx, int64_t N, uint64_t seed, int balance_flag,
                                    double* x_NxD, int32_t* comp_N) {
@@ -301,10 +307,8 @@ extern "C" int vbmc_kl_div_mc(vbmc_ctx* ctx, int64_t N, uint64_t seed, int K2, c
     if (rc) return rc;
     rc = launch_mixture_pdf_on(ctx, d_pack2, ml2, N, d_x, 0, d_y2);
     if (rc) return rc;
-    hipLaunchKernelGGL(kl_terms_kernel, dim3(nblk), dim3(256), 0, ctx->stream,
-                       (const double*)(dir == 0 ? d_y1 : d_y2), (const double*)(dir == 0 ? d_y2 : d_y1), N,
-                       d_part + (size_t)dir * nblk);
-    HIP_TRY(ctx, hipGetLastError());
+    rc = launch_kl_terms(ctx, dir == 0 ? d_y1 : d_y2, dir == 0 ? d_y2 : d_y1, N, nblk, d_part + (size_t)dir * nblk);
+    if (rc) return rc;
   }
   HIP_TRY(ctx, hipMemcpyAsync(part.data(), d_part, sizeof(double) * 2 * nblk, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));

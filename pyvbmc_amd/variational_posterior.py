@@ -17,6 +17,11 @@ stream exactly like the reference by default; ``rng="philox"`` (keyword-only, or
 ``VBMC_HIP_RNG=philox``) generates the samples on the device instead
 (vbmc_mixture_sample), which is what ``moments(orig_flag=True)`` and ``kl_div`` then use;
 with ``rng="philox"`` ``kl_div`` runs entirely on the device (vbmc_kl_div_mc).
+
+Original space (``orig_flag=True``, the default of ``sample`` / ``pdf`` / ``moments``): a transformer
+with the reference's fields (pyvbmc_amd/transformer.py) runs on the device -- fused into the sampling,
+density, moments and KL entry points (vbmc_*_orig) -- and any other transformer object is called on
+the host as the reference does.  ``VBMC_HIP_TRANSFORM=0`` keeps every transformer on the host.
 """
 import ctypes as C
 import os
@@ -25,6 +30,7 @@ import sys
 import numpy as np
 
 from . import _lib
+from . import transformer as _xf
 from ._duck import upload_vp
 from .entropy import _HOST_RANDN_MIN, host_randn
 
@@ -167,12 +173,14 @@ class VariationalPosterior:
             x = np.empty((N, self.D))
             i = np.empty(N, dtype=np.int32)
             tdf = float(df) if (np.isfinite(df) and df != 0) else float("inf")
-            ctx.check(ctx._lib.vbmc_mixture_sample_t(ctx._h, N, int(seed), int(bool(balance_flag)), tdf, _lib.ptr(x),
-                                                     i.ctypes.data_as(C.POINTER(C.c_int32))))
+            on_dev = orig_flag and _xf.upload(self.parameter_transformer, ctx, 0, self.D) is not None
+            fn = ctx._lib.vbmc_mixture_sample_orig if on_dev else ctx._lib.vbmc_mixture_sample_t
+            ctx.check(fn(ctx._h, N, int(seed), int(bool(balance_flag)), tdf, _lib.ptr(x),
+                         i.ctypes.data_as(C.POINTER(C.c_int32))))
             if balance_flag and shuffle and self.K > 1:
                 perm = np.random.permutation(N)
                 x, i = x[perm], i[perm]
-            if orig_flag:
+            if orig_flag and not on_dev:
                 x = self.parameter_transformer.inverse(x)
             return x, (i.astype(np.int64) if self.K > 1 else np.zeros(N))
         if mode not in ("numpy", "philox"):
@@ -208,8 +216,25 @@ class VariationalPosterior:
                 x = self.mu.T + lam * _randn(N, self.D) * self.sigma
             i = np.zeros(N)
         if orig_flag:
-            x = self.parameter_transformer.inverse(x)
+            x = self._inverse(x)
         return x, i
+
+    def _inverse(self, u):
+        """The transformer's inverse of the NumPy-stream draws: on the device when it is reference-shaped and
+        there is a device, else its own method.  These draws never needed a GPU, and still do not: without one
+        (none visible, or a host-only context) the transformer is called on the host as before."""
+        pt = self.parameter_transformer
+        ctx = self._device_ctx() if _xf.candidate(pt) else None
+        D = _xf.upload(pt, ctx, 0, self.D) if ctx is not None else None
+        if D is None:
+            return pt.inverse(u)
+        return _xf.transform_points(ctx, u, _xf.INVERSE, D)
+
+    def _device_ctx(self):
+        """The context to use when it has a device, else None (creates no context on a machine without one)."""
+        if self._ctx is not None:
+            return self._ctx if self._ctx.device >= 0 else None
+        return self.ctx if _lib.device_count() > 0 else None
 
     # -- density (:365-621) ---------------------------------------------------------------
     def pdf(self, x, orig_flag=True, log_flag=False, grad_flag=False, df=np.inf):
@@ -226,6 +251,9 @@ class VariationalPosterior:
                 "vbmc_pdf:NoOriginalGrad: Gradient computation in original space not supported yet."
             )
         if orig_flag:
+            ctx = self._upload()
+            if _xf.upload(self.parameter_transformer, ctx, 0, self.D) is not None:
+                return self._pdf_orig_device(ctx, x, in_dims, log_flag, grad_flag, df)
             pt = self.parameter_transformer
             mask = np.logical_and(np.all(x > pt.lb_orig, axis=1), np.all(x < pt.ub_orig, axis=1))
             x[mask] = pt(x[mask])
@@ -257,6 +285,22 @@ class VariationalPosterior:
                 y[mask] -= ladj
             else:
                 y[mask] /= np.exp(ladj)
+        out = (y, dy) if grad_flag else y
+        if in_dims == 1:
+            return tuple(o.ravel() for o in out) if grad_flag else out.ravel()
+        return out
+
+    def _pdf_orig_device(self, ctx, x, in_dims, log_flag, grad_flag, df):
+        """pdf(orig_flag=True) in one device call (vbmc_mixture_pdf_orig): bound mask, transform, density,
+        Jacobian; the host path's values, gradient rows included."""
+        n, D = x.shape
+        if D != self.D:
+            raise ValueError(f"points have {D} columns, the posterior D={self.D}")
+        y = np.empty(n)
+        dy = np.empty((n, D)) if grad_flag else None
+        ctx.check(ctx._lib.vbmc_mixture_pdf_orig(ctx._h, n, _lib.ptr(x), int(bool(log_flag)), int(bool(grad_flag)),
+                                                 float(df), _lib.ptr(y), _lib.ptr(dy)))
+        y = y.reshape(n, 1)
         out = (y, dy) if grad_flag else y
         if in_dims == 1:
             return tuple(o.ravel() for o in out) if grad_flag else out.ravel()
@@ -313,7 +357,20 @@ class VariationalPosterior:
 
     # -- moments (:761-808) ----------------------------------------------------------------------
     def moments(self, N=int(1e6), orig_flag=True, cov_flag=False, *, rng=None, seed=None):
-        if orig_flag:
+        mode = os.environ.get("VBMC_HIP_RNG", "numpy") if rng is None else rng
+        ctx = self._upload() if orig_flag and mode == "philox" else None
+        if ctx is not None and _xf.upload(self.parameter_transformer, ctx, 0, self.D) is not None:
+            # the balanced samples of sample(N, True, True, rng="philox", seed=seed), reduced where they are drawn
+            N = int(N)
+            if seed is None:
+                seed = int(np.random.randint(0, 2**62, dtype=np.int64))
+            mubar = np.empty(self.D)
+            cov = np.empty((self.D, self.D)) if cov_flag else None
+            ctx.check(ctx._lib.vbmc_mixture_moments_orig(ctx._h, N, int(seed), int(bool(cov_flag)), _lib.ptr(mubar),
+                                                         _lib.ptr(cov)))
+            if cov_flag:
+                cov = cov.squeeze()  # (np.cov's shape)
+        elif orig_flag:
             # mean / covariance do not depend on the order: skip the shuffle on the device path
             x, _ = self.sample(int(N), orig_flag=True, balance_flag=True, rng=rng, seed=seed, shuffle=False)
             mubar = np.mean(x, axis=0)
@@ -356,6 +413,18 @@ class VariationalPosterior:
             kls = np.empty(2)
             ctx.check(ctx._lib.vbmc_kl_div_mc(ctx._h, int(N), int(seed), vp2.K, _lib.ptr(mu2), _lib.ptr(sg2),
                                               _lib.ptr(lm2), _lib.ptr(w2), _lib.ptr(kls)))
+        elif (mode == "philox" and vp2.D == self.D
+              and _xf.upload(self.parameter_transformer, self._upload(), 0, self.D) is not None
+              and _xf.upload(vp2.parameter_transformer, self.ctx, 1, vp2.D) is not None):
+            # different transformers: both sides in original space, one device call (vbmc_kl_div_mc_orig)
+            ctx = self.ctx
+            if seed is None:
+                seed = int(np.random.randint(0, 2**62, dtype=np.int64))
+            mu2 = _lib.f64(np.asarray(vp2.mu, dtype=np.float64).reshape(vp2.D, vp2.K).T)
+            sg2, lm2, w2 = _lib.f64(np.ravel(vp2.sigma)), _lib.f64(np.ravel(vp2.lambd)), _lib.f64(np.ravel(vp2.w))
+            kls = np.empty(2)
+            ctx.check(ctx._lib.vbmc_kl_div_mc_orig(ctx._h, int(N), int(seed), vp2.K, _lib.ptr(mu2), _lib.ptr(sg2),
+                                                   _lib.ptr(lm2), _lib.ptr(w2), _lib.ptr(kls)))
         else:
             minp = sys.float_info.min
             xx1, _ = self.sample(N, True, True, rng=rng, seed=seed, shuffle=False)
@@ -378,7 +447,8 @@ class VariationalPosterior:
 
 def _same_transformer(a, b):
     ta, tb = a.parameter_transformer, b.parameter_transformer
-    return ta is tb or (isinstance(ta, IdentityTransformer) and isinstance(tb, IdentityTransformer))
+    return (ta is tb or (isinstance(ta, IdentityTransformer) and isinstance(tb, IdentityTransformer))
+            or (_xf.enabled() and _xf.same_by_value(ta, tb)))
 
 
 def kl_div_mvn(mu1, sigma1, mu2, sigma2):
