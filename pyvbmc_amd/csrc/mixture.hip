@@ -5,6 +5,7 @@
 // K x D scaled means and per-component constants are wave-uniform reads.  Linear-
 // domain accumulation over components then log with 0 -> -inf, exactly the
 // reference's order of operations (:451-463, :531-541).
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 
@@ -26,6 +27,21 @@ struct PdfArgs {
   double* dy;   // n x D or null
 };
 
+// The Gaussian term's exponent, bounded below: a squared distance that overflows (a coordinate near 1e308, or
+// 1e200 squared) makes it -inf, where exp2_fast's rint(x) - x is NaN; the reference's exp(-inf) is 0, and so is
+// exp2_fast of anything below -1075.  A NaN exponent (a NaN coordinate) fails the comparison and stays NaN.
+__device__ __forceinline__ double exp2_arg(double e) { return e < -2048.0 ? -2048.0 : e; }
+
+// x / lambda for the density.  With the gradient, a finite x whose quotient overflows is held at +-DBL_MAX:
+// its term c (x / lambda - mu_k / lambda) then has c = 0 and is 0, as the reference's nn (x - mu_k) / ... is,
+// while an infinite x keeps 0 * inf = NaN, as there.
+template <bool GRAD>
+__device__ __forceinline__ double scaled_coord(double x, double ilam) {
+  const double s = x * ilam;
+  if (GRAD && isinf(s) && isfinite(x)) return copysign(DBL_MAX, s);
+  return s;
+}
+
 template <int DP, int MODE, bool GRAD>
 __global__ __launch_bounds__(256) void mixture_pdf_kernel(PdfArgs a) {
   const int D = a.ml.D, K = a.ml.K;
@@ -42,7 +58,7 @@ __global__ __launch_bounds__(256) void mixture_pdf_kernel(PdfArgs a) {
   double xs[DP], g[DP];
 #pragma unroll
   for (int d = 0; d < DP; ++d) {
-    xs[d] = (d < D) ? a.x[i * D + d] * ilam[d] : 0.0;
+    xs[d] = (d < D) ? scaled_coord<GRAD>(a.x[i * D + d], ilam[d]) : 0.0;
     g[d] = 0.0;
   }
   double y = 0.0;
@@ -58,7 +74,7 @@ __global__ __launch_bounds__(256) void mixture_pdf_kernel(PdfArgs a) {
           d2 = fma(u, u, d2);
         }
       // exp(-d2 / (2 sigma_k^2)) as exp2 with log2(e) folded into the scale (fastmath.h, <= 1 ulp)
-      nn = wc[k] * fm::exp2_fast((-0.5 * 0x1.71547652b82fep+0 * is2[k]) * d2);
+      nn = wc[k] * fm::exp2_fast(exp2_arg((-0.5 * 0x1.71547652b82fep+0 * is2[k]) * d2));
       if (GRAD) {
         const double c = nn * is2[k];
 #pragma unroll
@@ -118,7 +134,7 @@ __global__ __launch_bounds__(256) void mixture_pdf_wave_kernel(PdfArgs a) {
   double xs[DP], g[DP];
 #pragma unroll
   for (int d = 0; d < DP; ++d) {
-    xs[d] = (d < D) ? a.x[i * D + d] * ilam[d] : 0.0;
+    xs[d] = (d < D) ? scaled_coord<GRAD>(a.x[i * D + d], ilam[d]) : 0.0;
     g[d] = 0.0;
   }
   double y = 0.0;
@@ -132,7 +148,7 @@ __global__ __launch_bounds__(256) void mixture_pdf_wave_kernel(PdfArgs a) {
         const double u = xs[d] - mk[d];
         d2 = fma(u, u, d2);
       }
-    const double nn = wc[k] * fm::exp2_fast((-0.5 * 0x1.71547652b82fep+0 * s2) * d2);
+    const double nn = wc[k] * fm::exp2_fast(exp2_arg((-0.5 * 0x1.71547652b82fep+0 * s2) * d2));
     y += nn;
     if (GRAD) {
       const double c = nn * s2;

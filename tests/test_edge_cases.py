@@ -265,6 +265,64 @@ def test_pdf_underflow_and_extremes(ctx):
     assert np.max(np.abs(ly[fin] - lyo[fin])) < 1e-11 * max(1.0, np.max(np.abs(lyo[fin])))
 
 
+@pytest.mark.parametrize("D", [4, 9])
+def test_pdf_overflowing_squared_distance(ctx, D):
+    """A coordinate of 1e308, 1e200 or -1e160 makes the squared distance overflow to inf: the reference's
+    exp(-inf) is 0, so the density is 0, log_pdf -inf and the gradient rows 0 (NaN where the log-gradient
+    divides 0 by 0).  Gaussian, multivariate t (df 5) and product-of-t (df -5) modes; the wave-per-point
+    kernel (at most kWavePerPointMax = 65536 points) and the thread-per-point one (more)."""
+    wl, wd = case(D, 6, 20, 40)
+    vp, _ = objects(wd, ctx)
+    mix = oracle_mix(wd)
+    rows = [wd["mu"].T, np.zeros((1, D))]
+    for v in (1e308, 1e200, -1e160, -1e308):
+        for d in range(D):
+            r = wd["mu"][:, d % wd["K"]].copy()
+            r[d] = v
+            rows.append(r[None])
+    x = np.vstack(rows)
+    big = np.any(np.abs(x) > 1e150, axis=1)
+    for n in (x.shape[0], 65536 + 100):
+        X = x[np.arange(n) % x.shape[0]]
+        bigX = big[np.arange(n) % x.shape[0]]
+        for df in (0.0, 5.0, -5.0):
+            for log_flag in (False, True):
+                with np.errstate(all="ignore"):
+                    y = vp.pdf(X, orig_flag=False, log_flag=log_flag, df=df)
+                    yo = mixture_ref.pdf(mix, X, log_flag=log_flag, df=df)
+                assert not np.any(np.isnan(y)) and not np.any(np.isnan(yo))
+                if log_flag:
+                    assert np.array_equal(np.isneginf(y), np.isneginf(yo)) and np.all(np.isneginf(y[bigX]))
+                    fin = np.isfinite(yo)
+                    assert np.max(np.abs(y[fin] - yo[fin])) < 1e-11 * max(1.0, np.max(np.abs(yo[fin])))
+                else:
+                    assert np.array_equal(y == 0, yo == 0) and np.all(y[bigX] == 0) and rel_err(y, yo) < 1e-12
+        for log_flag in (False, True):
+            with np.errstate(all="ignore"):
+                y, dy = vp.pdf(X, orig_flag=False, log_flag=log_flag, grad_flag=True)
+                yo, dyo = mixture_ref.pdf(mix, X, log_flag=log_flag, grad_flag=True)
+            assert np.array_equal(np.isnan(dy), np.isnan(dyo)) and np.array_equal(np.isinf(dy), np.isinf(dyo))
+            if log_flag:
+                assert np.all(np.isnan(dy[bigX])) and np.array_equal(np.isneginf(y), np.isneginf(yo))
+            else:
+                assert np.all(dy[bigX] == 0) and np.all(y[bigX] == 0) and rel_err(y, yo) < 1e-12
+            # (a gradient entry cancels between components, and at x = mu_k its own term is x / lambda - mu_k / lambda,
+            # the rounding of two quotients: compare at the scale of the operands, sum_k nn_k (|x| + |mu_k|) / (lambda sigma_k)^2)
+            lam = mix.lambd
+            T = np.zeros_like(dyo)
+            for k in range(mix.K):
+                z = (X - mix.mu[:, k]) / (mix.sigma[k] * lam)
+                with np.errstate(over="ignore"):
+                    nn = mix.w[k] / mix.sigma[k] ** D / (2 * np.pi) ** (D / 2) / np.prod(lam) * np.exp(-0.5 * np.sum(z**2, 1))
+                with np.errstate(over="ignore", invalid="ignore"):
+                    T += np.nan_to_num(nn[:, None] * (np.abs(X) + np.abs(mix.mu[:, k])) / (lam**2 * mix.sigma[k] ** 2))
+            if log_flag:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    T = T / mixture_ref.pdf(mix, X)
+            fin = np.isfinite(dyo)
+            assert np.all(np.abs(dy[fin] - dyo[fin]) <= 1e-12 * T[fin])
+
+
 def test_loud_failures(ctx):
     from pyvbmc_amd import VariationalPosterior, entmc_vbmc
     from pyvbmc_amd._lib import VbmcHipError

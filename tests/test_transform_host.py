@@ -1,13 +1,16 @@
 """CPU tests of the device transformer's host side: which objects are recognised as the reference's
 ``ParameterTransformer`` (pyvbmc_amd/transformer.py), the library's checks of a descriptor on a
-host-only context, and the internal consistency of tests/golden/transform.npz.  No kernel runs here."""
+host-only context, and the internal consistency of tests/golden/transform.npz and transform_wide.npz (where
+the restatement in transform_host.py is pinned at every padded width, so that the GPU tests can use it as
+a second reference).  No kernel runs here."""
 import warnings
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
-from transform_host import CASES, RefShapedTransformer
+from transform_host import CASES, WIDE_CASES, RefShapedTransformer
 
+from oracle import mixture_ref
 from oracle.transform_ref import BoundedLogit
 from pyvbmc_amd import VariationalPosterior, _lib
 from pyvbmc_amd import transformer as xf
@@ -129,29 +132,40 @@ def test_numpy_stream_sampling_needs_no_device():
         h.close()
 
 
+def _check_fixture(g, name):
+    """One case of a transform fixture: the stored fields have the reference's shapes and types, R is
+    orthogonal and the scale positive, and the restatement in transform_host.py reproduces the reference's
+    forward, inverse and log|J|; forward and inverse agree."""
+    pt = RefShapedTransformer.from_golden(g, name)
+    D = pt.type.size
+    assert pt.lb_orig.shape == (1, D) and pt.ub_orig.shape == (1, D) and pt.mu.shape == (D,) and pt.delta.shape == (D,)
+    bounded = np.isfinite(pt.lb_orig[0]) & np.isfinite(pt.ub_orig[0])
+    assert set(np.unique(pt.type[bounded])) <= {3.0, 12.0, 13.0} and np.all(pt.type[~bounded] == 0)
+    x, u = g[f"{name}_x"], g[f"{name}_u"]
+    assert x.shape[1] == D and u.shape[1] == D and g[f"{name}_ladj"].shape == (u.shape[0],)
+    assert g[f"{name}_u_fwd"].shape == x.shape and g[f"{name}_x_inv"].shape == u.shape
+    if pt.R_mat is not None:
+        assert pt.R_mat.shape == (D, D) and pt.scale.shape == (D,)
+        assert np.allclose(pt.R_mat @ pt.R_mat.T, np.eye(D), atol=1e-12) and np.all(pt.scale > 0)
+    with warnings.catch_warnings(), np.errstate(all="ignore"):
+        warnings.simplefilter("ignore")
+        for mine, ref in ((pt(x), g[f"{name}_u_fwd"]), (pt.inverse(u), g[f"{name}_x_inv"]),
+                          (pt.log_abs_det_jacobian(u), g[f"{name}_ladj"])):
+            fin = np.isfinite(ref)
+            assert np.array_equal(np.isfinite(mine), fin) and np.array_equal(mine[~fin], ref[~fin], equal_nan=True)
+            assert np.allclose(mine[fin], ref[fin], rtol=1e-13, atol=1e-13)
+    back = pt.inverse(g[f"{name}_u_fwd"][:24])  # (the first 24 points: random, inside the bounds)
+    assert np.allclose(back, x[:24], rtol=1e-6, atol=1e-6)
+    return pt
+
+
 def test_fixture_is_consistent(golden):
     """transform.npz: the restatement in transform_host.py reproduces the reference's stored outputs,
     forward and inverse agree, and the stored fields have the reference's shapes."""
     g = golden("transform")
     assert tuple(g["cases"]) == CASES
     for name in CASES:
-        pt = RefShapedTransformer.from_golden(g, name)
-        D = pt.type.size
-        bounded = np.isfinite(pt.lb_orig[0]) & np.isfinite(pt.ub_orig[0])
-        assert set(np.unique(pt.type[bounded])) <= {3.0, 12.0, 13.0} and np.all(pt.type[~bounded] == 0)
-        x, u = g[f"{name}_x"], g[f"{name}_u"]
-        assert x.shape[1] == D and u.shape[1] == D and g[f"{name}_ladj"].shape == (u.shape[0],)
-        if pt.R_mat is not None:
-            assert np.allclose(pt.R_mat @ pt.R_mat.T, np.eye(D), atol=1e-12) and np.all(pt.scale > 0)
-        with warnings.catch_warnings(), np.errstate(all="ignore"):
-            warnings.simplefilter("ignore")
-            for mine, ref in ((pt(x), g[f"{name}_u_fwd"]), (pt.inverse(u), g[f"{name}_x_inv"]),
-                              (pt.log_abs_det_jacobian(u), g[f"{name}_ladj"])):
-                fin = np.isfinite(ref)
-                assert np.array_equal(np.isfinite(mine), fin) and np.array_equal(mine[~fin], ref[~fin], equal_nan=True)
-                assert np.allclose(mine[fin], ref[fin], rtol=1e-13, atol=1e-13)
-        back = pt.inverse(g[f"{name}_u_fwd"][:24])  # (the first 24 points: random, inside the bounds)
-        assert np.allclose(back, x[:24], rtol=1e-6, atol=1e-6)
+        pt = _check_fixture(g, name)
         for df in ("0", "7"):
             y, ly = g[f"{name}_pdf_df{df}"], g[f"{name}_logpdf_df{df}"]
             xp = g[f"{name}_pdf_x"]
@@ -160,3 +174,70 @@ def test_fixture_is_consistent(golden):
             # (near the bounds the linear density under- or overflows, or passes through a subnormal exp(log|J|))
             pos = m & (y[:, 0] > 1e-200) & (y[:, 0] < 1e200)
             assert np.allclose(np.log(y[pos]), ly[pos], rtol=1e-12, atol=1e-9) and pos.sum() >= 5
+
+
+def _host_pdf_orig(g, name, pt, xp, df, log_flag=False, grad_flag=False):
+    """pdf(orig_flag=True) on the host: the reference's steps with transform_host.py's transformer and the
+    oracle's transformed-space density (oracle/mixture_ref.py)."""
+    mix = mixture_ref.Mixture.make(g[f"{name}_vp_mu"], g[f"{name}_vp_sigma"], g[f"{name}_vp_lambd"],
+                                   g[f"{name}_vp_w"])
+    m = np.all(xp > pt.lb_orig, axis=1) & np.all(xp < pt.ub_orig, axis=1)
+    x = xp.copy()
+    x[m] = pt(x[m])
+    out = mixture_ref.pdf(mix, x, log_flag=log_flag, grad_flag=grad_flag, df=df)
+    y, dy = out if grad_flag else (out, None)
+    y[~m] = -np.inf if log_flag else 0.0
+    lj = pt.log_abs_det_jacobian(x[m])[:, None]
+    if log_flag:
+        y[m] -= lj
+    else:
+        y[m] /= np.exp(lj)
+    return (y, dy) if grad_flag else y
+
+
+@pytest.mark.parametrize("name", WIDE_CASES)
+def test_wide_fixture_is_consistent(golden, name):
+    """transform_wide.npz, every padded width 2 .. 32 and both sides of the pairwise sum's switch at D = 8:
+    the checks of transform.npz, and the host's orig-space pdf (transform_host.py's transformer, the oracle's
+    density) reproduces the reference's, bounds, 1e308 / 1e200 coordinates and gradient rows included."""
+    g = golden("transform_wide")
+    assert tuple(g["cases"]) == WIDE_CASES
+    pt = _check_fixture(g, name)
+    D = pt.type.size
+    assert D == int(name[1:])
+    bounded = pt.type != 0
+    if D >= 8:  # the bounded types are spread over the wide cases
+        assert bounded.sum() >= 5 and (~bounded).sum() >= 2
+    xp = g[f"{name}_pdf_x"]
+    assert xp.shape[1] == D and np.all(np.isfinite(xp))
+    with warnings.catch_warnings(), np.errstate(all="ignore"):
+        warnings.simplefilter("ignore")
+        for df in ("0", "7"):
+            y, ly = g[f"{name}_pdf_df{df}"], g[f"{name}_logpdf_df{df}"]
+            assert y.shape == (xp.shape[0], 1) and ly.shape == y.shape
+            for mine, ref in ((_host_pdf_orig(g, name, pt, xp, float(df)), y),
+                              (_host_pdf_orig(g, name, pt, xp, float(df), log_flag=True), ly)):
+                fin = np.isfinite(ref)
+                assert np.array_equal(mine[~fin], ref[~fin], equal_nan=True)
+                assert np.allclose(mine[fin], ref[fin], rtol=1e-12, atol=0)
+            if pt.R_mat is None:  # the overflowing squared distances: exactly 0 / -inf, never NaN
+                big = np.any(np.abs(xp) > 1e150, axis=1)
+                assert (D == 1 or big.sum() >= 4) and np.all(y[big] == 0) and np.all(np.isneginf(ly[big]))
+        if f"{name}_pdf_g" in g:
+            yg, dyg = _host_pdf_orig(g, name, pt, xp, 0.0, grad_flag=True)
+            assert np.allclose(yg, g[f"{name}_pdf_g"], rtol=1e-12, atol=0, equal_nan=True)
+            assert np.allclose(dyg, g[f"{name}_dpdf_g"], rtol=1e-12, atol=1e-300, equal_nan=True)
+
+
+def test_wide_fixture_covers_every_width(golden):
+    g = golden("transform_wide")
+    Ds = sorted(int(n[1:]) for n in WIDE_CASES)
+    dp = [2, 4, 6, 8, 10, 12, 16, 20, 24, 32]  # the device kernels' padded widths (XF_DISPATCH)
+    assert {min(p for p in dp if p >= D) for D in Ds} == set(dp) - {4}  # (D = 3..5: transform.npz's cases)
+    assert any(D < 8 for D in Ds) and any(D > 8 and D % 8 for D in Ds) and any(D % 8 == 0 and D > 8 for D in Ds)
+    types = {t: [int(n[1:]) for n in WIDE_CASES if t in g[f"{n}_type"]] for t in (3.0, 12.0, 13.0)}
+    assert all(max(v) >= 8 for v in types.values())
+    rot = [n for n in WIDE_CASES if g[f"{n}_R"].size]
+    assert "w32" in rot and 4 <= len(rot) <= 8
+    assert sum(f"{n}_pdf_g" in g for n in WIDE_CASES) >= 3
+    assert set(np.unique(g["w16_type"])) == {0.0, 3.0, 12.0, 13.0}  # all three bounded types in one transformer

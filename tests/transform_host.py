@@ -1,6 +1,6 @@
 """A reference-shaped parameter transformer for the tests: the fields of the reference's
 ``ParameterTransformer`` (type, lb_orig, ub_orig, mu, delta, R_mat, scale) taken from
-tests/golden/transform.npz, and its three maps evaluated dimension by dimension from a table of
+tests/golden/transform.npz or transform_wide.npz, and its three maps evaluated dimension by dimension from a table of
 per-type formulas -- the host side that ``VBMC_HIP_TRANSFORM=0`` runs.
 
 Per bounded dimension (z in the unit interval, y the uncentred transformed value):
@@ -19,6 +19,8 @@ import numpy as np
 from scipy.special import erfc, erfcinv
 
 CASES = ("logit", "probit", "student4", "mixed", "roto")
+# transform_wide.npz: one case per padded width of the device kernels, D = the number in the name
+WIDE_CASES = ("w1", "w2", "w6", "w7", "w8", "w9", "w12", "w16", "w17", "w24", "w25", "w32")
 
 _TINY = np.nextafter(0.0, 1.0)
 _BELOW_ONE = np.nextafter(1.0, 0.0)
