@@ -641,6 +641,48 @@ int vbmc_kl_div_mc_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed, int K2, const d
                         const double* sigma2_K, const double* lambd2_D, const double* w2_K,
                         double kl_out[2]);
 
+/* ---- kernel density estimate and marginal total variation (stats/kde_1d.py, mtv) ----
+ *
+ * kde_1d (stats/kde_1d.py:144-257) for a batch of ncol columns of n host samples each (column c at
+ * x_colxn + c * n), mesh n_mesh (a power of two, <= 2^14: VBMC_E_UNSUP above).  lb_col / ub_col: the
+ * bounds per column, or NULL to derive them as min - 0.1 (max - min) / max + 0.1 (max - min) (:218-225).
+ * Every column is sorted on the device; from it the mesh, the bin counts (_linear_binning, :6-31),
+ * len(np.unique), the DCT, the bandwidth of _root / _fixed_point (:34-108, scipy's brentq restated) or,
+ * when that fails, Scott's rule (:111-130), and the density (:236-257).  Out: density and xmesh
+ * (ncol x n_mesh; xmesh nullable), the bandwidth per column, and info_colx2 = {len(np.unique(column)),
+ * flags}: 1 Scott's rule was used, 4 the mesh is degenerate (dx == 0 or non-finite: the reference
+ * raises IndexError), 8 _root stopped where the reference would repeat the same brentq call forever
+ * (Scott's rule used).  A non-finite sample -> VBMC_E_NONFINITE (the reference computes garbage). */
+int vbmc_kde_1d(vbmc_ctx* ctx, int ncol, int64_t n, const double* x_colxn, int n_mesh, const double* lb_col,
+                const double* ub_col, double* density_colxm, double* xmesh_colxm, double* bandwidth_col,
+                int64_t* info_colx2);
+
+/* One side of vbmc_mtv: host samples (x_NxD, row-major), or the N balanced draws of the ctx mixture through
+ * transformer slot 0 / of the second mixture through slot 1 -- the samples of vbmc_mixture_sample_orig
+ * with `seed`, which stay on the device.  lb_D / ub_D: the transformer's lb_orig / ub_orig (+-inf for
+ * samples, :974-975). */
+enum { VBMC_MTV_HOST = 0, VBMC_MTV_MIX1 = 1, VBMC_MTV_MIX2 = 2 };
+typedef struct vbmc_mtv_side {
+  int source;
+  int64_t n;
+  const double* x_NxD;
+  uint64_t seed;
+  const double* lb_D;
+  const double* ub_D;
+} vbmc_mtv_side;
+
+/* VariationalPosterior.mtv (variational_posterior.py:921-1030): per dimension, the kde_1d density of each
+ * side on 2^13 points within max(min - range/10, lb) .. min(max + range/10, ub) (:978-990), normalised
+ * by its trapezoid sum (:996-1002), the not-a-knot cubic spline of each (interp1d kind="cubic", 0 outside
+ * its mesh), and 0.5 * the trapezoid of |s1 - s2| over the three linspace(bb[j], bb[j+1], 1e5) segments of
+ * the sorted mesh ends (:1018-1029).  The second mixture (mu2 .. w2, K2) is needed only by a
+ * VBMC_MTV_MIX2 side.  All 2 D columns run at once; mtv_D gets the D distances and info_2Dx2 (nullable)
+ * vbmc_kde_1d's info per column (side 1's D columns, then side 2's).  A non-finite sample ->
+ * VBMC_E_NONFINITE. */
+int vbmc_mtv(vbmc_ctx* ctx, int D, const vbmc_mtv_side* s1, const vbmc_mtv_side* s2, int K2,
+             const double* mu2_KxD, const double* sigma2_K, const double* lambd2_D, const double* w2_K,
+             double* mtv_D, int64_t* info_2Dx2);
+
 /* ---- multi-GPU: one process per GPU, one collective ---------- */
 
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by

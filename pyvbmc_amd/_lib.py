@@ -79,6 +79,23 @@ class ElboCall(C.Structure):
     ]
 
 
+MTV_HOST, MTV_MIX1, MTV_MIX2 = 0, 1, 2  # vbmc_mtv_side.source
+KDE_SCOTT, KDE_DEGENERATE, KDE_ROOT_STUCK = 1, 4, 8  # vbmc_kde_1d / vbmc_mtv info flags
+
+
+class MtvSide(C.Structure):
+    """vbmc_mtv_side: host samples, or the device draws of the ctx mixture (slot 0) / the second mixture (slot 1)."""
+
+    _fields_ = [
+        ("source", C.c_int),
+        ("n", C.c_int64),
+        ("x_NxD", _dp),
+        ("seed", C.c_uint64),
+        ("lb_D", _dp),
+        ("ub_D", _dp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/vbmc_hip.h declares
 SIGNATURES = {
     "vbmc_abi_version": (C.c_int, []),
@@ -176,6 +193,9 @@ SIGNATURES = {
     "vbmc_mixture_pdf_orig": (C.c_int, [_vp, C.c_int64, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp]),
     "vbmc_mixture_moments_orig": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, _dp]),
     "vbmc_kl_div_mc_orig": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "vbmc_kde_1d": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "vbmc_mtv": (C.c_int, [_vp, C.c_int, C.POINTER(MtvSide), C.POINTER(MtvSide), C.c_int, _dp, _dp, _dp, _dp, _dp,
+                           C.POINTER(C.c_int64)]),
     "vbmc_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "vbmc_comm_init": (C.c_int, [_vp, C.POINTER(C.c_uint8), C.c_int, C.c_int]),
     "vbmc_comm_destroy": (C.c_int, [_vp]),

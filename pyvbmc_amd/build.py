@@ -31,6 +31,7 @@ SOURCES = [
     "api_acq_is.hip",
     "sample.hip",
     "transform.hip",
+    "kde.hip",
     "comm.hip",
     "host_randn.hip",
     "device_randn.hip",

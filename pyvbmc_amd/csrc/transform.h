@@ -230,3 +230,8 @@ __device__ __forceinline__ bool xf_inside(const XfView& t, const double (&v)[DP]
     if (d < t.D) in = in && (v[d] > t.p[XfLayout::row(XfLayout::LB, t.D) + d]) && (v[d] < t.p[XfLayout::row(XfLayout::UB, t.D) + d]);
   return in;
 }
+
+// host side (transform.hip): a slot's descriptor when it is set for D, and its transform of n device points
+struct vbmc_ctx;
+bool xf_view_slot(vbmc_ctx* ctx, int slot, int D, XfView& v);
+int xf_apply_slot(vbmc_ctx* ctx, const XfView& t, int64_t n, int dir, const double* d_in, double* d_out);

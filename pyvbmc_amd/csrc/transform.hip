@@ -274,6 +274,17 @@ void xf_free(vbmc_ctx* ctx) {
   ctx->xf = nullptr;
 }
 
+bool xf_view_slot(vbmc_ctx* ctx, int slot, int D, XfView& v) {
+  const XfSlot& s = xf_state(ctx)->slot[slot];
+  if (!s.set || s.D != D) return false;
+  v = xf_view(s);
+  return true;
+}
+
+int xf_apply_slot(vbmc_ctx* ctx, const XfView& t, int64_t n, int dir, const double* d_in, double* d_out) {
+  return launch_xf_apply(ctx, t, n, dir, d_in, d_out);
+}
+
 extern "C" int vbmc_set_transformer(vbmc_ctx* ctx, int slot, int D, const double* type_D, const double* lb_D,
                                     const double* ub_D, const double* mu_D, const double* delta_D,
                                     const double* R_DxD, const double* scale_D) {

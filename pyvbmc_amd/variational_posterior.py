@@ -7,8 +7,9 @@ methods on the ELBO path -- ``get_bounds`` (:140-239), ``sample`` (:241-363),
 ``pdf`` (:365-564), ``log_pdf`` (:566-621), ``get_parameters`` (:623-678),
 ``set_parameters`` (:680-759), ``moments`` (:761-808) -- with the same mutation
 side effects and exceptions -- plus ``kl_div`` (:1032-1127), the Monte-Carlo consumer
-SURVEY.md 8f row 4 names.  ``mode``, ``mtv``, ``plot`` are host-side analysis outside
-the path and are not provided.
+SURVEY.md 8f row 4 names, and ``mtv`` (:921-1030), the marginal total variation distance, whose
+density estimates, splines and integrals run on the device (csrc/kde.hip, vbmc_mtv; kde_1d itself is
+``pyvbmc_amd.stats.kde_1d``).  ``mode`` (scipy's L-BFGS-B around ``pdf``) and ``plot`` are not provided.
 
 Where the arithmetic runs: ``pdf``/``log_pdf`` -> HIP kernel (vbmc_mixture_pdf).
 State bookkeeping (get/set_parameters, bounds) and the closed-form K*D^2 moments are
@@ -26,6 +27,7 @@ the host as the reference does.  ``VBMC_HIP_TRANSFORM=0`` keeps every transforme
 import ctypes as C
 import os
 import sys
+import types
 
 import numpy as np
 
@@ -443,6 +445,92 @@ class VariationalPosterior:
             kl2 = -np.mean(np.log(q1) - np.log(q2))
             kls = np.concatenate((kl1, kl2), axis=None)
         return np.maximum(0, kls)  # correct for numerical errors (:1126)
+
+    # -- marginal total variation (:921-1030) ----------------------------------------------------------
+    def mtv(self, vp2=None, samples=None, N=int(1e5), *, rng=None, seed=None):
+        """Marginal total variation distances to ``vp2`` or to ``samples``, a ``(1, D)`` array; reference
+        signature.  ``rng="numpy"`` (the default) draws ``self.sample(N, True, True)`` then
+        ``vp2.sample(N, True, True)`` from NumPy's global stream, as the reference does, and uploads them
+        once; ``rng="philox"`` draws both on the device (seeds ``seed`` and ``seed + 1``) and never copies
+        them to the host.  Everything after the sampling is one device call (vbmc_mtv)."""
+        if vp2 is None and samples is None:
+            raise ValueError("Either vp2 or samples have to be not None")
+        mode = os.environ.get("VBMC_HIP_RNG", "numpy") if rng is None else rng
+        if mode not in ("numpy", "philox"):
+            raise ValueError(f"unknown rng {mode!r}")
+        D, N = self.D, int(N)
+        if vp2 is not None and vp2.D != D:
+            raise ValueError(f"vp2 has D={vp2.D}, this posterior D={D}")
+        if samples is not None and vp2 is None:
+            samples = np.ascontiguousarray(samples, dtype=np.float64)
+            if samples.ndim != 2 or samples.shape[1] != D:
+                raise ValueError(f"samples of shape {samples.shape}, the posterior D={D}")
+        ctx = self._upload()
+        if mode == "philox" and seed is None:
+            seed = int(np.random.randint(0, 2**62, dtype=np.int64))
+        held = []  # arrays the sides point at, alive until the call returns
+
+        def bounds(pt):
+            lb = _lib.f64(np.broadcast_to(np.asarray(pt.lb_orig, dtype=np.float64).reshape(-1), (D,)))
+            ub = _lib.f64(np.broadcast_to(np.asarray(pt.ub_orig, dtype=np.float64).reshape(-1), (D,)))
+            held.extend((lb, ub))
+            return lb, ub
+
+        def host_side(x, lb, ub):
+            x = _lib.f64(x)
+            held.extend((x, lb, ub))
+            return _lib.MtvSide(_lib.MTV_HOST, x.shape[0], _lib.ptr(x), 0, _lib.ptr(lb), _lib.ptr(ub))
+
+        def draw_side(vp, slot, s):
+            # sample(N, True, True, rng=mode, seed=s): on the device when its transformer can go to the slot
+            lb, ub = bounds(vp.parameter_transformer)
+            if mode == "philox" and _xf.upload(_device_pt(vp), ctx, slot, D) is not None:
+                src = _lib.MTV_MIX1 if slot == 0 else _lib.MTV_MIX2
+                return _lib.MtvSide(src, N, None, int(s), _lib.ptr(lb), _lib.ptr(ub))
+            x, _ = vp.sample(N, True, True, rng=mode, seed=s, shuffle=False)
+            return host_side(x, lb, ub)
+
+        s1 = draw_side(self, 0, seed)
+        if vp2 is not None:
+            s2 = draw_side(vp2, 1, None if seed is None else seed + 1)
+        else:
+            s2 = host_side(samples, np.full(D, -np.inf), np.full(D, np.inf))  # (:974-975)
+        if s1.source == _lib.MTV_MIX1:
+            # (vp2.sample on the host path may have put vp2's mixture or transformer in this context)
+            ctx = self._upload()
+            _xf.upload(_device_pt(self), ctx, 0, D)
+        K2, mix2 = 0, (None,) * 4
+        if s2.source == _lib.MTV_MIX2:
+            K2 = vp2.K
+            mix2 = (_lib.f64(np.asarray(vp2.mu, dtype=np.float64).reshape(D, K2).T), _lib.f64(np.ravel(vp2.sigma)),
+                    _lib.f64(np.ravel(vp2.lambd)), _lib.f64(np.ravel(vp2.w)))
+        out = np.empty(D)
+        info = np.empty((2 * D, 2), dtype=np.int64)
+        from .stats import _call_checked, _raise_degenerate
+        rc = ctx._lib.vbmc_mtv(ctx._h, D, C.byref(s1), C.byref(s2), K2, *(_lib.ptr(a) for a in mix2), _lib.ptr(out),
+                               info.ctypes.data_as(C.POINTER(C.c_int64)))
+        _call_checked(ctx, rc, "mtv")
+        if np.any(info[:, 1] & _lib.KDE_DEGENERATE):
+            _raise_degenerate("mtv")
+        return out.reshape(1, D)
+
+
+_IDENTITY_PT = {}
+
+
+def _device_pt(vp):
+    """The transformer to put in a device slot: its own when reference-shaped, the identity's fields for
+    ``IdentityTransformer`` (one object per D, so the slot's cached arguments are reused), else itself
+    (not recognised: the caller samples through ``sample``)."""
+    pt = vp.parameter_transformer
+    if isinstance(pt, IdentityTransformer):
+        D = vp.D
+        if D not in _IDENTITY_PT:
+            _IDENTITY_PT[D] = types.SimpleNamespace(type=np.zeros(D), lb_orig=np.full(D, -np.inf),
+                                                    ub_orig=np.full(D, np.inf), mu=np.zeros(D), delta=np.ones(D),
+                                                    R_mat=None, scale=None)
+        return _IDENTITY_PT[D]
+    return pt
 
 
 def _same_transformer(a, b):
