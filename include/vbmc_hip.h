@@ -683,6 +683,28 @@ int vbmc_mtv(vbmc_ctx* ctx, int D, const vbmc_mtv_side* s1, const vbmc_mtv_side*
              const double* mu2_KxD, const double* sigma2_K, const double* lambd2_D, const double* w2_K,
              double* mtv_D, int64_t* info_2Dx2);
 
+/* ---- mode of the variational posterior (variational_posterior.py:810-919) ----
+ *
+ * VariationalPosterior.mode: n_opts rounds, each "n candidates (+ the K component centres in round 0), the one
+ * with the highest log-density starts a local search"; the best round's point is the mode.  The mixture and the
+ * transformer (slot 0, needed when orig_flag) are the ones set in the context.  Candidates: cand_RxnxD, a host
+ * array of n_opts x n x D points in the requested space (the reference's self.sample(n, orig_flag) per round),
+ * or NULL = round r draws the n samples of vbmc_mixture_sample / vbmc_mixture_sample_orig(n, seed + r,
+ * balance_flag 0) in the kernel, never stored.  Start selection: highest value, ties to the lowest index, a
+ * NaN value never wins.  The local search (csrc/mode.hip) replaces SciPy's minimize (:906-908) by a monotone
+ * ascent with analytic derivatives -- safeguarded Newton steps, mean-shift (transformed space) or projected
+ * gradient (original space, inside the reference's L-BFGS-B box lb + sqrt(eps) .. ub - sqrt(eps), :888-898)
+ * otherwise -- until a step is <= step_tol max(1, |y|_inf) or max_iter iterations.  The original-space
+ * objective assumes an orthogonal rotation matrix (the caller's check).
+ * Out: x_D and its log-density f_out (nullable; pdf(x, orig_flag, log_flag=True)); rec_Rx5 (nullable), per
+ * round {start index, start value, final value, iterations, status: 0 converged, 1 converged on a bound, 2
+ * iteration cap}; pts_RxD (nullable), the rounds' final points, and ys_RxD (nullable), the same in the search
+ * coordinates.  With a host array all n_opts x n x D candidates are uploaded in one piece (n_opts = 37, D = 32:
+ * 0.95 GB of device scratch); n <= 2^24.  D > 32 -> VBMC_E_UNSUP. */
+int vbmc_mixture_mode(vbmc_ctx* ctx, int n_opts, int orig_flag, int64_t n, const double* cand_RxnxD,
+                      uint64_t seed, int max_iter, double step_tol, double* x_D, double* f_out,
+                      double* rec_Rx5, double* pts_RxD, double* ys_RxD);
+
 /* ---- multi-GPU: one process per GPU, one collective ---------- */
 
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by

@@ -32,6 +32,7 @@ SOURCES = [
     "sample.hip",
     "transform.hip",
     "kde.hip",
+    "mode.hip",
     "comm.hip",
     "host_randn.hip",
     "device_randn.hip",

@@ -92,6 +92,26 @@ __device__ __forceinline__ double bounded_lj(int type, double y) {
   return kLog3_8 - (5.0 / 2.0) * log1p(y * y / 4.0);
 }
 
+// d bounded_lj / dy and d^2 bounded_lj / dy^2 (the mode search's gradient and Hessian, mode.hip):
+//   logit     lj = -y - 2 log1p(e^-y)              lj' = -tanh(y / 2)                 lj'' = -1 / (2 cosh^2(y / 2))
+//   probit    lj = c - y^2 / 2                     lj' = -y                           lj'' = -1
+//   student4  lj = c - 5/2 log1p(y^2 / 4)          lj' = -5/4 y / (1 + y^2 / 4)       lj'' = -5/4 (1 - y^2/4) / (1 + y^2/4)^2
+__device__ __forceinline__ double bounded_lj_d1(int type, double y) {
+  if (type == XF_LOGIT) return -tanh(0.5 * y);
+  if (type == XF_PROBIT) return -y;
+  return -1.25 * y / (1.0 + y * y / 4.0);
+}
+
+__device__ __forceinline__ double bounded_lj_d2(int type, double y) {
+  if (type == XF_LOGIT) {
+    const double t = tanh(0.5 * y);
+    return -0.5 * (1.0 - t * t);
+  }
+  if (type == XF_PROBIT) return -1.0;
+  const double q = 1.0 + y * y / 4.0;
+  return -1.25 * (1.0 - y * y / 4.0) / (q * q);
+}
+
 // NumPy's pairwise sum of a short contiguous row (numpy/_core/src/umath/loops_utils.h.src, n <= 128)
 template <int DP>
 __device__ __forceinline__ double row_sum(const double (&v)[DP], int n) {

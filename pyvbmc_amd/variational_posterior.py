@@ -9,7 +9,8 @@ methods on the ELBO path -- ``get_bounds`` (:140-239), ``sample`` (:241-363),
 side effects and exceptions -- plus ``kl_div`` (:1032-1127), the Monte-Carlo consumer
 SURVEY.md 8f row 4 names, and ``mtv`` (:921-1030), the marginal total variation distance, whose
 density estimates, splines and integrals run on the device (csrc/kde.hip, vbmc_mtv; kde_1d itself is
-``pyvbmc_amd.stats.kde_1d``).  ``mode`` (scipy's L-BFGS-B around ``pdf``) and ``plot`` are not provided.
+``pyvbmc_amd.stats.kde_1d``), and ``mode`` (:810-919), whose start selection and local searches run on the
+device for all rounds at once (csrc/mode.hip, vbmc_mixture_mode).  ``plot`` is not provided.
 
 Where the arithmetic runs: ``pdf``/``log_pdf`` -> HIP kernel (vbmc_mixture_pdf).
 State bookkeeping (get/set_parameters, bounds) and the closed-form K*D^2 moments are
@@ -386,6 +387,130 @@ class VariationalPosterior:
                 cov = cov + (self.w * dev) @ dev.T
         return (mubar.reshape(1, -1), cov) if cov_flag else mubar.reshape(1, -1)
 
+    # -- mode (:810-919) -------------------------------------------------------------------------
+    def mode(self, orig_flag=True, n_opts=None, *, rng=None, seed=None):
+        """The mode of the posterior, a ``(D,)`` array; reference signature.  ``n_opts`` rounds (default
+        ``ceil(sqrt(K))``) each pick the best of 1e5 samples (plus the component centres in round 0) and run a
+        local search from it; all rounds run in one device call (vbmc_mixture_mode, csrc/mode.hip).
+        ``rng="numpy"`` (the default) draws ``self.sample(int(1e5), orig_flag)`` once per round from NumPy's
+        global stream, as the reference does; ``rng="philox"`` draws round k on the device with ``seed + k``
+        and never copies the candidates to the host.  The result for ``orig_flag=True`` is cached in
+        ``_mode`` until ``set_parameters``.  ``mode_info`` keeps the last search's details: ``log_pdf`` at the
+        result, per-round ``records`` (start index, start value, final value, iterations, status), the rounds'
+        final ``points`` (and, from the device, ``search_points``, the same in the search's coordinates) and
+        whether it ran on the ``device``.  With ``rng="numpy"`` the n_opts x 1e5 x D candidates are held and
+        uploaded in one piece.
+
+        Deviations from the reference: D = 1 with ``orig_flag=True`` returns the mode (the reference raises
+        ``AxisError``), and the local search is a monotone ascent with analytic derivatives that stops at a
+        step of 1e-12, so the result is a stationary point to a much tighter tolerance than SciPy's.  Without
+        a device (or with a transformer that cannot go to one and ``orig_flag=True``) a NumPy / SciPy loop
+        with the reference's structure runs around ``sample`` / ``pdf``."""
+        mode = os.environ.get("VBMC_HIP_RNG", "numpy") if rng is None else rng
+        if mode not in ("numpy", "philox"):
+            raise ValueError(f"unknown rng {mode!r}")
+        if n_opts is None:
+            n_opts = int(np.ceil(np.sqrt(self.K)))
+        n_opts = int(n_opts)
+        if n_opts < 1:
+            raise ValueError(f"n_opts={n_opts}: at least one optimization run is needed")
+        if orig_flag and self._mode is not None:
+            return self._mode
+        x, self.mode_info = self._mode_search(bool(orig_flag), n_opts, mode, seed)
+        if orig_flag:
+            self._mode = x
+        return x
+
+    def _mode_search(self, orig_flag, n_opts, mode, seed):
+        D, n = self.D, int(1e5)
+        if D > 32:
+            raise _lib.UnsupportedShape(f"mode: D={D} > 32 not supported")
+        ctx = self._device_ctx()
+        on_dev = ctx is not None
+        if on_dev and orig_flag:
+            pt = _device_pt(self)
+            on_dev = _xf.upload(pt, self._upload(ctx), 0, D) is not None and _orthogonal(pt.R_mat)
+        if not on_dev:
+            return self._mode_host(orig_flag, n_opts, mode, seed, n)
+        cand = None
+        if mode == "numpy":
+            cand = np.empty((n_opts, n, D))
+            for k in range(n_opts):
+                cand[k] = self.sample(n, orig_flag, rng="numpy")[0]
+        elif seed is None:
+            seed = int(np.random.randint(0, 2**62, dtype=np.int64))
+        ctx = self._upload(ctx)
+        if orig_flag:  # (sample may have put another transformer in the slot)
+            _xf.upload(_device_pt(self), ctx, 0, D)
+        x, f = np.empty(D), np.empty(1)
+        rec, pts, ys = np.empty((n_opts, 5)), np.empty((n_opts, D)), np.empty((n_opts, D))
+        ctx.check(ctx._lib.vbmc_mixture_mode(ctx._h, n_opts, int(orig_flag), n, _lib.ptr(cand), int(seed or 0), 200,
+                                             1e-12, _lib.ptr(x), _lib.ptr(f), _lib.ptr(rec), _lib.ptr(pts), _lib.ptr(ys)))
+        return x, {"log_pdf": float(f[0]), "records": rec, "points": pts, "search_points": ys, "device": True}
+
+    def _log_pdf_host(self, x, orig_flag):
+        """``pdf(x, orig_flag, log_flag=True)`` and, in the transformed space, its gradient, in NumPy (a 1-D
+        point gives a scalar and a ``(D,)`` gradient)."""
+        dims = np.ndim(x)
+        x = np.array(np.atleast_2d(x), dtype=np.float64)
+        pt, lj = self.parameter_transformer, 0.0
+        mask = np.full(x.shape[0], True)
+        if orig_flag:
+            mask = np.all(x > pt.lb_orig, axis=1) & np.all(x < pt.ub_orig, axis=1)
+            u = np.atleast_2d(pt(x[mask]))
+            lj = np.ravel(pt.log_abs_det_jacobian(u))
+        else:
+            u = x
+        lam, sig = self.lambd.reshape(1, 1, -1), np.ravel(self.sigma)
+        z = (u[:, None, :] - self.mu.T[None, :, :]) / lam                         # n x K x D
+        l = (np.log(np.ravel(self.w)) - self.D * np.log(sig) - 0.5 * self.D * np.log(2 * np.pi)
+             - np.sum(np.log(lam)) - 0.5 * np.sum(z**2, axis=2) / sig**2)
+        m = np.max(l, axis=1, keepdims=True)
+        p = np.exp(l - m)
+        y = np.full(x.shape[0], -np.inf)
+        y[mask] = m[:, 0] + np.log(np.sum(p, axis=1)) - lj
+        dy = None
+        if not orig_flag:
+            r = p / np.sum(p, axis=1, keepdims=True)
+            dy = -np.sum((r / sig**2)[:, :, None] * z, axis=1) / lam[0]
+        if dims == 1:
+            return y[0], (None if dy is None else dy[0])
+        return y, dy
+
+    def _mode_host(self, orig_flag, n_opts, mode, seed, n):
+        """The reference's loop (:863-914) around our own ``sample`` and a NumPy log-density: no device, or a
+        transformer that stays on the host."""
+        from scipy.optimize import minimize
+
+        pt = self.parameter_transformer
+
+        def neg_log_pdf(x0):
+            y, dy = self._log_pdf_host(x0, orig_flag)
+            return -y if orig_flag else (-y, -dy)
+
+        rec, pts = np.empty((n_opts, 5)), np.empty((n_opts, self.D))
+        for k in range(n_opts):
+            x0_mat, _ = self.sample(n, orig_flag, rng=mode, seed=None if seed is None else seed + k)
+            if k == 0:
+                x0_mu = self.mu.T
+                if orig_flag:
+                    x0_mu = pt.inverse(x0_mu)
+                x0_mat = np.concatenate([x0_mat, x0_mu])
+            y0 = -self._log_pdf_host(x0_mat, orig_flag)[0]
+            y0 = np.where(np.isnan(y0), np.inf, y0)  # a NaN value never wins (csrc/mode.hip)
+            idx = int(np.argmin(y0))
+            x0, bounds = x0_mat[idx], None
+            if orig_flag:
+                lb = np.broadcast_to(np.ravel(pt.lb_orig), (self.D,))  # (D = 1: the reference's np.stack raises)
+                ub = np.broadcast_to(np.ravel(pt.ub_orig), (self.D,))
+                bounds = np.stack((lb + np.sqrt(np.finfo(float).eps), ub - np.sqrt(np.finfo(float).eps)), axis=1)
+                x0 = np.minimum(ub, np.maximum(x0, lb))
+            res = minimize(fun=neg_log_pdf, x0=x0, bounds=bounds, jac=not orig_flag)
+            pts[k] = res.x
+            rec[k] = (idx, -y0[idx], -float(np.ravel(res.fun)[0]), res.nit, 0 if res.success else 2)
+        best = int(np.argmin(np.where(np.isnan(rec[:, 2]), np.inf, -rec[:, 2])))
+        return pts[best].copy(), {"log_pdf": rec[best, 2], "records": rec, "points": pts, "device": False}
+
     # -- Kullback-Leibler divergence (:1032-1127) ------------------------------------------------
     def kl_div(self, vp2=None, samples=None, N=int(1e5), gauss_flag=False, *, rng=None, seed=None):
         """Forward and reverse KL divergence between two posteriors, reference signature.
@@ -531,6 +656,15 @@ def _device_pt(vp):
                                                     R_mat=None, scale=None)
         return _IDENTITY_PT[D]
     return pt
+
+
+def _orthogonal(R):
+    """The mode search's original-space objective takes log|J| at the pre-rotation coordinates, which is what the
+    transformer computes when R R^T = I (csrc/mode.hip)."""
+    if R is None:
+        return True
+    R = np.asarray(R, dtype=np.float64)
+    return R.ndim == 2 and bool(np.max(np.abs(R @ R.T - np.eye(R.shape[0]))) <= 1e-10)
 
 
 def _same_transformer(a, b):
