@@ -257,6 +257,22 @@ extern thread_local std::string g_create_err;
                        hipGetErrorString(e_), __FILE__, __LINE__);                    \
   } while (0)
 
+// The padded widths DP of the per-point kernels (density, sampler consumers, transformer): 2, 4, 6, 8, 10, 12, 16, 20,
+// 24, 32.  CALL(DP) with the narrowest one that holds D (D <= 32 is the caller's check).
+#define VBMC_DISPATCH_DP(D, CALL)   \
+  do {                              \
+    if ((D) <= 2) CALL(2);          \
+    else if ((D) <= 4) CALL(4);     \
+    else if ((D) <= 6) CALL(6);     \
+    else if ((D) <= 8) CALL(8);     \
+    else if ((D) <= 10) CALL(10);   \
+    else if ((D) <= 12) CALL(12);   \
+    else if ((D) <= 16) CALL(16);   \
+    else if ((D) <= 20) CALL(20);   \
+    else if ((D) <= 24) CALL(24);   \
+    else CALL(32);                  \
+  } while (0)
+
 // Entry points that launch kernels refuse a host-only context (device_id -1).
 // cancel an armed evaluation (api_elbo.hip): its queued kernels return at once, host state is restored
 void spec_disarm(vbmc_ctx* ctx);
@@ -271,6 +287,10 @@ void spec_disarm(vbmc_ctx* ctx);
 
 void write_mixture_pack(const MixLayout& ml, const double* mu_KxD, const double* sigma,
                         const double* lambd, const double* w, double* p);
+// a second mixture (kl_div's and mtv's vp2) from host arrays: sigma2 checked (failure code `err`, message prefix `who`),
+// its layout planned and its pack written
+int make_mixture2(vbmc_ctx* ctx, const char* who, int err, int D, int K2, const double* mu2_KxD, const double* sigma2_K,
+                  const double* lambd2_D, const double* w2_K, MixLayout& ml2, std::vector<double>& pack2);
 int theta_to_arrays(int D, int K, const double* theta, int n_theta, int optimize_mask, double* mu,
                     double* sg, double* lm, double* w, double* eta);
 int upload_packed_mixture(vbmc_ctx* ctx);
@@ -479,7 +499,15 @@ int launch_mixture_pdf(vbmc_ctx* ctx, int64_t n, const double* d_x, int log_flag
                        int grad_flag, double df, double* d_y, double* d_dy);
 int launch_mixture_pdf_on(vbmc_ctx* ctx, const double* d_pack, const MixLayout& ml, int64_t n,
                           const double* d_x, int log_flag, double* d_y);
-// sampling (sample.hip): N draws of the mixture `d_pack` (selection vectors through d_sel, (K+1) int64 + K doubles)
+// sampling (sample.hip): counts / cdf of a mixture's component selection; without balance n_exact = 0 and cdf is
+// np.random.choice(p=w)'s cumulative sum
+struct Selector {
+  int64_t n_exact = 0;
+  std::vector<int64_t> cum;  // K+1
+  std::vector<double> cdf;   // K
+};
+void make_selector(const double* w, int K, int64_t N, int balance, Selector& s);
+// N draws of the mixture `d_pack` (selection vectors through d_sel, (K+1) int64 + K doubles)
 int launch_sample(vbmc_ctx* ctx, const double* d_pack, const MixLayout& ml, const double* w_host, int64_t N,
                   uint64_t seed, int balance, void* d_sel, double* d_x, int32_t* d_comp, double df = INFINITY);
 // per-block partial sums of log q_other - log q_own with kl_div's zero-replacement rules (nblk blocks)

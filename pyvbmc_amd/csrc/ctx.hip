@@ -404,6 +404,17 @@ void write_mixture_pack(const MixLayout& ml, const double* mu_KxD, const double*
   }
 }
 
+int make_mixture2(vbmc_ctx* ctx, const char* who, int err, int D, int K2, const double* mu2_KxD, const double* sigma2_K,
+                  const double* lambd2_D, const double* w2_K, MixLayout& ml2, std::vector<double>& pack2) {
+  for (int k = 0; k < K2; ++k)
+    if (!(sigma2_K[k] > 0.0) || !std::isfinite(sigma2_K[k]))
+      return vbmc_fail(ctx, err, "%s: sigma2[%d] must be finite and > 0", who, k);
+  ml2.plan(D, K2);
+  pack2.resize((size_t)ml2.total);
+  write_mixture_pack(ml2, mu2_KxD, sigma2_K, lambd2_D, w2_K, pack2.data());
+  return 0;
+}
+
 // VariationalPosterior.set_parameters (raw) on plain arrays (variational_posterior.py:680-759)
 // plus eta = theta[-K:] - max (variational_optimization.py:1082-1085).  In/out arrays start
 // from the current attribute values; blocks whose optimize bit is clear are left alone.

@@ -890,24 +890,18 @@ extern "C" int vbmc_mtv(vbmc_ctx* ctx, int D, const vbmc_mtv_side* s1, const vbm
     if (sd[s]->source == VBMC_MTV_MIX1 && !xf_view_slot(ctx, 0, D, t1)) return vbmc_fail(ctx, VBMC_E_ARG, "mtv: transformer slot 0 not set for D=%d", D);
     if (sd[s]->source == VBMC_MTV_MIX2 && !xf_view_slot(ctx, 1, D, t2)) return vbmc_fail(ctx, VBMC_E_ARG, "mtv: transformer slot 1 not set for D=%d", D);
   }
+  MixLayout ml2;
+  std::vector<double> pack2;
   if (need_mix2) {
     if (K2 < 1 || !mu2_KxD || !sigma2_K || !lambd2_D || !w2_K) return vbmc_fail(ctx, VBMC_E_ARG, "mtv: second mixture missing");
-    for (int k = 0; k < K2; ++k)
-      if (!(sigma2_K[k] > 0.0) || !std::isfinite(sigma2_K[k]))
-        return vbmc_fail(ctx, VBMC_E_ARG, "mtv: sigma2[%d] must be finite and > 0", k);
+    const int rc2 = make_mixture2(ctx, "mtv", VBMC_E_ARG, D, K2, mu2_KxD, sigma2_K, lambd2_D, w2_K, ml2, pack2);
+    if (rc2) return rc2;
   }
   NEED_DEVICE(ctx);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int ncol = 2 * D, nm = kMtvMesh;
   KdePlan pl;
   pl.plan(ncol, nm, s1->n > s2->n ? s1->n : s2->n, false, true, D);
-  MixLayout ml2;
-  std::vector<double> pack2;
-  if (need_mix2) {
-    ml2.plan(D, K2);
-    pack2.resize((size_t)ml2.total);
-    write_mixture_pack(ml2, mu2_KxD, sigma2_K, lambd2_D, w2_K, pack2.data());
-  }
   const int Kmax = ctx->K > K2 ? ctx->K : K2;
   size_t o = pl.total;
   const size_t o_x1 = o; o += (size_t)s1->n * D;
@@ -938,7 +932,7 @@ extern "C" int vbmc_mtv(vbmc_ctx* ctx, int D, const vbmc_mtv_side* s1, const vbm
       rc = launch_sample(ctx, m2 ? base + o_pack : ctx->d_mix, m2 ? ml2 : ctx->ml, m2 ? w2_K : ctx->w.data(), q.n,
                          q.seed, 1, (void*)(base + o_sel), d_x, nullptr, INFINITY);
       if (rc) return rc;
-      rc = xf_apply_slot(ctx, m2 ? t2 : t1, q.n, 1, d_x, d_x);
+      rc = launch_xf_apply(ctx, m2 ? t2 : t1, q.n, 1, d_x, d_x);
       if (rc) return rc;
     }
     src.x[s] = d_x;

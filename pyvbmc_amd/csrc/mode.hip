@@ -38,7 +38,7 @@
 
 #include "common.h"
 #include "fastmath.h"
-#include "philox.h"
+#include "mixture_dev.h"
 #include "transform.h"
 
 namespace {
@@ -69,34 +69,15 @@ struct ModeArgs {
   double* ys;           // [n_opts][D]: the final points in the search coordinates
 };
 
-__device__ __forceinline__ double exp2_arg(double e) { return e < -2048.0 ? -2048.0 : e; }
-
-// log q(u): the arithmetic of mixture_pdf_kernel<DP, 0, false> with log_flag (mixture.hip), operation for operation.
-// A COPY: mixture.hip's kernel is left as it is, so a change of its arithmetic has to be repeated here (the start
-// selection tests compare this function's values and argmax with vbmc_mixture_pdf's).
+// log q(u), as mixture_pdf_kernel<DP, 0, false> with log_flag computes it (mixture.hip)
 template <int DP>
-__device__ __forceinline__ double mix_log_density(const double* __restrict__ mix, const MixLayout& ml,
-                                                  const double (&u)[DP]) {
-  const int D = ml.D, K = ml.K;
-  const double* mup = mix + ml.o_mup;
-  const double* is2 = mix + ml.o_is2;
-  const double* wc = mix + ml.o_wc;
+__device__ __forceinline__ double mix_log_density(const double* mix, const MixLayout& ml, const double (&u)[DP]) {
+  const MixGauss mg = mix_gauss(mix, ml);
   const double* ilam = mix + ml.o_ilam;
-  double xs[DP];
+  double xs[DP], g[DP], y = 0.0;
 #pragma unroll
-  for (int d = 0; d < DP; ++d) xs[d] = (d < D) ? u[d] * ilam[d] : 0.0;
-  double y = 0.0;
-  for (int k = 0; k < K; ++k) {
-    const double* mk = mup + k * D;
-    double d2 = 0.0;
-#pragma unroll
-    for (int d = 0; d < DP; ++d)
-      if (d < D) {
-        const double t = xs[d] - mk[d];
-        d2 = fma(t, t, d2);
-      }
-    y += wc[k] * fm::exp2_fast(exp2_arg((-0.5 * 0x1.71547652b82fep+0 * is2[k]) * d2));
-  }
+  for (int d = 0; d < DP; ++d) xs[d] = (d < ml.D) ? scaled_coord<false>(u[d], ilam[d]) : 0.0;
+  mix_gauss_accumulate<DP, false, 1>(mg, xs, 0, y, g);
   return (y == 0.0) ? -INFINITY : log(y);
 }
 
@@ -131,30 +112,19 @@ __device__ __forceinline__ void candidate(const ModeArgs& a, int r, int64_t i, d
       if (d < D) v[d] = x[d];
     return;
   }
-  // sample i of vbmc_mixture_sample(N, seed + r, balance_flag = 0): a COPY of mixture_sample_kernel's Gaussian branch
-  // (sample.hip), to be kept in step with it (test_philox_start_is_the_best_philox_sample compares the two)
+  // sample i of vbmc_mixture_sample(N, seed + r, balance_flag = 0)
   const uint64_t seed = a.seed + (uint64_t)r, n = (uint64_t)i;
-  int k = 0;
-  if (K > 1) {
-    Philox4 q = philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 0u, 3u, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const double u = (double)((((uint64_t)q.x[0] << 32) | q.x[1]) >> 11) * 0x1.0p-53;
-    while (k + 1 < K && u >= a.cdf[k]) ++k;
-  }
+  const int k = K > 1 ? pick_component(a.cdf, K, philox_uniform(n, 3u, seed)) : 0;
   const double* mu = a.mix + a.ml.o_mu + (size_t)k * D;
   const double* lam = a.mix + a.ml.o_lam;
   const double sg = a.mix[a.ml.o_sig + k];
 #pragma unroll
   for (int p = 0; p < (DP + 1) / 2; ++p)
     if (2 * p < D) {
-      Philox4 q = philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), (uint32_t)p, 2u, (uint32_t)seed,
-                                (uint32_t)(seed >> 32));
-      const uint64_t ua = (((uint64_t)q.x[0] << 32) | q.x[1]) >> 11, ub = (((uint64_t)q.x[2] << 32) | q.x[3]) >> 11;
-      const double u1 = (double)(ua + 1) * 0x1.0p-53, u2 = (double)ub * 0x1.0p-53;
-      const double rad = sqrt(-2.0 * fm::log_fast(u1));
-      double s, c;
-      fm::sincospi_fast(2.0 * u2, s, c);
-      v[2 * p] = mu[2 * p] + (lam[2 * p] * (rad * c)) * sg;
-      if (2 * p + 1 < DP && 2 * p + 1 < D) v[2 * p + 1] = mu[2 * p + 1] + (lam[2 * p + 1] * (rad * s)) * sg;
+      double z0, z1;
+      philox_normal_pair(philox_block(n, (uint32_t)p, 2u, seed), z0, z1);
+      v[2 * p] = mu[2 * p] + (lam[2 * p] * z0) * sg;
+      if (2 * p + 1 < DP && 2 * p + 1 < D) v[2 * p + 1] = mu[2 * p + 1] + (lam[2 * p + 1] * z1) * sg;
     }
   if (a.orig) xf_inverse<DP>(a.xf, v);
 }
@@ -621,15 +591,9 @@ extern "C" int vbmc_mixture_mode(vbmc_ctx* ctx, int n_opts, int orig_flag, int64
   double* d_rec = d_pv + 2 * n_part;
   double* d_pts = d_rec + (size_t)n_opts * 5;
   double* d_ys = d_pts + (size_t)n_opts * D;
-  // np.random.choice(p=w)'s inverse CDF, as sample.hip's selector without balance
-  std::vector<double> cdf((size_t)K);
-  double c = 0.0;
-  for (int k = 0; k < K; ++k) {
-    c += ctx->w[k];
-    cdf[k] = c;
-  }
-  cdf[K - 1] = 2.0;
-  HIP_TRY(ctx, hipMemcpyAsync(d_cdf, cdf.data(), sizeof(double) * K, hipMemcpyHostToDevice, ctx->stream));
+  Selector sel;  // np.random.choice(p=w)'s inverse CDF: sample.hip's selector without balance
+  make_selector(ctx->w.data(), K, n, 0, sel);
+  HIP_TRY(ctx, hipMemcpyAsync(d_cdf, sel.cdf.data(), sizeof(double) * K, hipMemcpyHostToDevice, ctx->stream));
   if (cand_RxnxD)
     HIP_TRY(ctx, hipMemcpyAsync(d_cand, cand_RxnxD, sizeof(double) * n_cand, hipMemcpyHostToDevice, ctx->stream));
   a.mix = ctx->d_mix;
@@ -649,16 +613,9 @@ extern "C" int vbmc_mixture_mode(vbmc_ctx* ctx, int n_opts, int orig_flag, int64
   a.rec = d_rec;
   a.pts = d_pts;
   a.ys = d_ys;
-  if (D <= 2) launch_start_dp<2>(ctx, a);
-  else if (D <= 4) launch_start_dp<4>(ctx, a);
-  else if (D <= 6) launch_start_dp<6>(ctx, a);
-  else if (D <= 8) launch_start_dp<8>(ctx, a);
-  else if (D <= 10) launch_start_dp<10>(ctx, a);
-  else if (D <= 12) launch_start_dp<12>(ctx, a);
-  else if (D <= 16) launch_start_dp<16>(ctx, a);
-  else if (D <= 20) launch_start_dp<20>(ctx, a);
-  else if (D <= 24) launch_start_dp<24>(ctx, a);
-  else launch_start_dp<32>(ctx, a);
+#define CALL(DP) launch_start_dp<DP>(ctx, a)
+  VBMC_DISPATCH_DP(D, CALL);
+#undef CALL
   HIP_TRY(ctx, hipGetLastError());
   // the K x D scaled means in LDS while they fit next to the kernel's own 43 KiB (64 KiB per workgroup)
   if (K * D <= kStageMax)

@@ -22,7 +22,8 @@
 
 #include "common.h"
 #include "fastmath.h"
-#include "philox.h"
+#include "mixture_dev.h"
+#include "transform.h"
 
 namespace {
 
@@ -40,12 +41,6 @@ struct SampleArgs {
   double df;              // degrees of freedom of the multivariate-t tails; <= 0 or inf: Gaussian
 };
 
-__device__ __forceinline__ double philox_uniform(uint64_t n, uint32_t c3, uint64_t seed) {
-  Philox4 r = philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 0u, c3, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const uint64_t a = (((uint64_t)r.x[0] << 32) | r.x[1]) >> 11;
-  return (double)a * 0x1.0p-53;  // [0, 1)
-}
-
 // Gamma(shape, 1) variate of sample n by Marsaglia & Tsang's method (ACM TOMS 26, 2000): with
 // d = shape' - 1/3, c = 1/sqrt(9 d): z ~ N(0,1), v = (1 + c z)^3, accept when v > 0 and
 // ln U < z^2/2 + d - d v + d ln v; shape < 1 goes through shape' = shape + 1 and a factor U'^(1/shape).
@@ -58,21 +53,16 @@ __device__ inline double philox_gamma(uint64_t n, double shape, uint64_t seed) {
   const double d = sh - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
   double g = d, up = 1.0;
   for (uint32_t r = 0; r < 64; ++r) {
-    Philox4 q = philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 2 * r, 4u, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const uint64_t ua = (((uint64_t)q.x[0] << 32) | q.x[1]) >> 11, ub = (((uint64_t)q.x[2] << 32) | q.x[3]) >> 11;
-    const double u1 = (double)(ua + 1) * 0x1.0p-53, u2 = (double)ub * 0x1.0p-53;
-    double sn, cs;
-    fm::sincospi_fast(2.0 * u2, sn, cs);
-    const double z = sqrt(-2.0 * fm::log_fast(u1)) * cs;
+    double z, z_unused;
+    philox_normal_pair(philox_block(n, 2 * r, 4u, seed), z, z_unused);
     const double t = 1.0 + c * z;
     if (t <= 0.0) continue;
     const double v = t * t * t;
-    q = philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), 2 * r + 1, 4u, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const uint64_t uc = (((uint64_t)q.x[0] << 32) | q.x[1]) >> 11, ud = (((uint64_t)q.x[2] << 32) | q.x[3]) >> 11;
-    const double U = (double)(uc + 1) * 0x1.0p-53;
+    const Philox4 q = philox_block(n, 2 * r + 1, 4u, seed);
+    const double U = philox_u53_pos(q.x[0], q.x[1]);
     if (fm::log_fast(U) < 0.5 * z * z + d - d * v + d * fm::log_fast(v)) {
       g = d * v;
-      up = (double)(ud + 1) * 0x1.0p-53;
+      up = philox_u53_pos(q.x[2], q.x[3]);
       break;
     }
   }
@@ -89,8 +79,7 @@ __global__ __launch_bounds__(256) void mixture_sample_kernel(SampleArgs a) {
     if (n < a.n_exact) {
       while (k + 1 < K && n >= a.cum_cnt[k + 1]) ++k;
     } else {
-      const double u = philox_uniform((uint64_t)n, 3u, a.seed);
-      while (k + 1 < K && u >= a.cdf[k]) ++k;
+      k = pick_component(a.cdf, K, philox_uniform((uint64_t)n, 3u, a.seed));
     }
   }
   if (a.comp) a.comp[n] = k;
@@ -107,16 +96,7 @@ __global__ __launch_bounds__(256) void mixture_sample_kernel(SampleArgs a) {
   }
   for (int p = 0; 2 * p < D; ++p) {
     double z0, z1;
-    Philox4 r = philox4x32_10((uint32_t)n, (uint32_t)((uint64_t)n >> 32), (uint32_t)p, 2u,
-                              (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-    const uint64_t ua = (((uint64_t)r.x[0] << 32) | r.x[1]) >> 11;
-    const uint64_t ub = (((uint64_t)r.x[2] << 32) | r.x[3]) >> 11;
-    const double u1 = (double)(ua + 1) * 0x1.0p-53, u2 = (double)ub * 0x1.0p-53;
-    const double rad = sqrt(-2.0 * fm::log_fast(u1));
-    double s, c;
-    fm::sincospi_fast(2.0 * u2, s, c);
-    z0 = rad * c;
-    z1 = rad * s;
+    philox_normal_pair(philox_block((uint64_t)n, (uint32_t)p, 2u, a.seed), z0, z1);
     const int d0 = 2 * p, d1 = 2 * p + 1;
     if (!heavy) {
       a.x[n * D + d0] = mu[d0] + (lam[d0] * z0) * sg;  // the reference's association (:323-326)
@@ -152,13 +132,9 @@ __global__ __launch_bounds__(256) void kl_terms_kernel(const double* __restrict_
   if (tid == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// host: counts / cdf of one mixture's component selection
-struct Selector {
-  int64_t n_exact = 0;
-  std::vector<int64_t> cum;  // K+1
-  std::vector<double> cdf;   // K
-};
+}  // namespace
 
+// host: counts / cdf of one mixture's component selection
 void make_selector(const double* w, int K, int64_t N, int balance, Selector& s) {
   s.cum.assign((size_t)K + 1, 0);
   s.cdf.assign((size_t)K, 1.0);
@@ -192,8 +168,6 @@ void make_selector(const double* w, int K, int64_t N, int balance, Selector& s) 
   }
   s.cdf[K - 1] = 2.0;  // the last component catches rounding in the cumulative sum
 }
-
-}  // namespace
 
 // Draw N samples of `d_pack` into d_x (device), optionally labels into d_comp.
 // d_sel: device scratch of (K+1) int64 + K doubles.
@@ -235,23 +209,27 @@ extern "C" int vbmc_mixture_sample(vbmc_ctx* ctx, int64_t N, uint64_t seed, int 
   return vbmc_mixture_sample_t(ctx, N, seed, balance_flag, INFINITY, x_NxD, comp_N);
 }
 
-extern "C" int vbmc_mixture_sample_t(vbmc_ctx* ctx, int64_t N, uint64_t seed, int balance_flag, double df,
-                                     double* x_NxD, int32_t* comp_N) {
+// the argument checks that vbmc_mixture_sample_t and vbmc_mixture_sample_orig share
+static int sample_check(vbmc_ctx* ctx, const char* who, int64_t N, double df) {
   if (!ctx || N < 0) return VBMC_E_ARG;
   if (df < 0.0 || df != df)
-    return vbmc_fail(ctx, VBMC_E_ARG, "mixture_sample: df=%g (the reference's gamma draw needs df > 0)", df);
-  if (!ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "mixture_sample: mixture not set");
+    return vbmc_fail(ctx, VBMC_E_ARG, "%s: df=%g (the reference's gamma draw needs df > 0)", who, df);
+  if (!ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "%s: mixture not set", who);
+  return 0;
+}
+
+// N samples to the host; with a transformer `t` (original space) they are inverse-transformed where they lie
+static int mixture_sample_impl(vbmc_ctx* ctx, int64_t N, uint64_t seed, int balance_flag, double df, double* x_NxD,
+                               int32_t* comp_N, const XfView* t) {
   if (N == 0) return VBMC_OK;
   NEED_DEVICE(ctx);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int D = ctx->D, K = ctx->K;
-  const int64_t BATCH = (int64_t)1 << 22;
   // one launch covers all N indices so that sample n does not depend on the batching;
   // x is produced in full and copied back in one piece (N x D doubles of scratch)
   const size_t n_x = x_NxD ? (size_t)N * D : 0;
   const size_t n_c = comp_N ? ((size_t)N + 1) / 2 : 0;  // int32 labels, in doubles
   const size_t n_sel = (size_t)2 * K + 2;
-  (void)BATCH;
   int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, n_x + n_c + n_sel);
   if (rc) return rc;
   double* d_x = x_NxD ? ctx->d_scratch : nullptr;
@@ -259,39 +237,60 @@ extern "C" int vbmc_mixture_sample_t(vbmc_ctx* ctx, int64_t N, uint64_t seed, in
   void* d_sel = (void*)(ctx->d_scratch + n_x + n_c);
   rc = launch_sample(ctx, ctx->d_mix, ctx->ml, ctx->w.data(), N, seed, balance_flag, d_sel, d_x, d_c, df);
   if (rc) return rc;
-  if (x_NxD)
+  if (x_NxD) {
+    if (t && (rc = launch_xf_apply(ctx, *t, N, 1, d_x, d_x))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(x_NxD, d_x, sizeof(double) * n_x, hipMemcpyDeviceToHost, ctx->stream));
+  }
   if (comp_N)
     HIP_TRY(ctx, hipMemcpyAsync(comp_N, d_c, sizeof(int32_t) * N, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));
   return VBMC_OK;
 }
 
-extern "C" int vbmc_kl_div_mc(vbmc_ctx* ctx, int64_t N, uint64_t seed, int K2, const double* mu2_KxD,
-                              const double* sigma2_K, const double* lambd2_D, const double* w2_K,
-                              double kl_out[2]) {
-  if (!ctx || N < 1 || K2 < 1 || !mu2_KxD || !sigma2_K || !lambd2_D || !w2_K || !kl_out) return VBMC_E_ARG;
-  if (!ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "kl_div: mixture not set");
+extern "C" int vbmc_mixture_sample_t(vbmc_ctx* ctx, int64_t N, uint64_t seed, int balance_flag, double df,
+                                     double* x_NxD, int32_t* comp_N) {
+  const int rc = sample_check(ctx, "mixture_sample", N, df);
+  if (rc) return rc;
+  return mixture_sample_impl(ctx, N, seed, balance_flag, df, x_NxD, comp_N, nullptr);
+}
+
+extern "C" int vbmc_mixture_sample_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed, int balance_flag, double df,
+                                        double* x_NxD, int32_t* comp_N) {
+  int rc = sample_check(ctx, "mixture_sample_orig", N, df);
+  if (rc) return rc;
+  XfView t;
+  rc = xf_need(ctx, 0, ctx->D, "mixture_sample_orig", t);
+  if (rc) return rc;
+  return mixture_sample_impl(ctx, N, seed, balance_flag, df, x_NxD, comp_N, &t);
+}
+
+// kl_div's Monte-Carlo branch (:1107-1123).  With transformers t1 / t2 (original space, both or neither) each
+// direction's samples go through their own mixture's inverse and every density is taken in its mixture's
+// transformed space with the Jacobian divided out; without them nothing of that is allocated or launched.
+static int kl_div_mc_impl(vbmc_ctx* ctx, const char* who, int64_t N, uint64_t seed, int K2, const double* mu2_KxD,
+                          const double* sigma2_K, const double* lambd2_D, const double* w2_K, double kl_out[2],
+                          const XfView* t1, const XfView* t2) {
   NEED_DEVICE(ctx);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int D = ctx->D, K1 = ctx->K;
-  for (int k = 0; k < K2; ++k)
-    if (!(sigma2_K[k] > 0.0) || !std::isfinite(sigma2_K[k]))
-      return vbmc_fail(ctx, VBMC_E_NONFINITE, "kl_div: sigma2[%d] must be finite and > 0", k);
   MixLayout ml2;
-  ml2.plan(D, K2);
-  std::vector<double> pack2((size_t)ml2.total);
-  write_mixture_pack(ml2, mu2_KxD, sigma2_K, lambd2_D, w2_K, pack2.data());
+  std::vector<double> pack2;
+  int rc = make_mixture2(ctx, who, VBMC_E_NONFINITE, D, K2, mu2_KxD, sigma2_K, lambd2_D, w2_K, ml2, pack2);
+  if (rc) return rc;
   const int nblk = 512;
   const int Kmax = K1 > K2 ? K1 : K2;
-  const size_t need = (size_t)ml2.total + (size_t)N * D + 2 * (size_t)N + (size_t)2 * Kmax + 2 + 2 * (size_t)nblk;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, need);
+  const size_t n_xf = t1 ? (size_t)N * D + 2 * (size_t)N : 0;  // u, log|J|, inside
+  const size_t need = (size_t)ml2.total + (size_t)N * D + n_xf + 2 * (size_t)N + (size_t)2 * Kmax + 2 + 2 * (size_t)nblk;
+  rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, need);
   if (rc) return rc;
   double* d_pack2 = ctx->d_scratch;
   double* d_x = d_pack2 + ml2.total;
-  double* d_y1 = d_x + (size_t)N * D;
+  double* d_u = t1 ? d_x + (size_t)N * D : d_x;  // the points the densities are taken at
+  double* d_y1 = d_u + (size_t)N * D;
   double* d_y2 = d_y1 + N;
-  void* d_sel = (void*)(d_y2 + N);
+  double* d_lj = d_y2 + N;
+  double* d_in = d_lj + N;
+  void* d_sel = (void*)(t1 ? d_in + N : d_y2 + N);
   double* d_part = (double*)d_sel + 2 * Kmax + 2;
   HIP_TRY(ctx, hipMemcpyAsync(d_pack2, pack2.data(), sizeof(double) * ml2.total, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));
@@ -301,12 +300,17 @@ extern "C" int vbmc_kl_div_mc(vbmc_ctx* ctx, int64_t N, uint64_t seed, int K2, c
     const double* d_own = dir == 0 ? ctx->d_mix : d_pack2;
     const MixLayout& ml_own = dir == 0 ? ctx->ml : ml2;
     const double* w_own = dir == 0 ? ctx->w.data() : w2_K;
-    rc = launch_sample(ctx, d_own, ml_own, w_own, N, seed + (uint64_t)dir, 1, d_sel, d_x, nullptr);
+    rc = launch_sample(ctx, d_own, ml_own, w_own, N, seed + (uint64_t)dir, 1, d_sel, d_x, nullptr, INFINITY);
     if (rc) return rc;
-    rc = launch_mixture_pdf_on(ctx, ctx->d_mix, ctx->ml, N, d_x, 0, d_y1);
-    if (rc) return rc;
-    rc = launch_mixture_pdf_on(ctx, d_pack2, ml2, N, d_x, 0, d_y2);
-    if (rc) return rc;
+    if (t1 && (rc = launch_xf_apply(ctx, dir == 0 ? *t1 : *t2, N, 1, d_x, d_x))) return rc;
+    // q1 = vp1.pdf(xx), q2 = vp2.pdf(xx)
+    for (int m = 0; m < 2; ++m) {
+      double* d_y = m == 0 ? d_y1 : d_y2;
+      if (t1 && (rc = launch_xf_prep(ctx, m == 0 ? *t1 : *t2, N, d_x, d_u, d_lj, d_in))) return rc;
+      rc = launch_mixture_pdf_on(ctx, m == 0 ? ctx->d_mix : d_pack2, m == 0 ? ctx->ml : ml2, N, d_u, 0, d_y);
+      if (rc) return rc;
+      if (t1 && (rc = launch_xf_finish(ctx, N, 0, d_lj, d_in, d_y))) return rc;
+    }
     rc = launch_kl_terms(ctx, dir == 0 ? d_y1 : d_y2, dir == 0 ? d_y2 : d_y1, N, nblk, d_part + (size_t)dir * nblk);
     if (rc) return rc;
   }
@@ -319,4 +323,25 @@ extern "C" int vbmc_kl_div_mc(vbmc_ctx* ctx, int64_t N, uint64_t seed, int K2, c
     kl_out[dir] = kl > 0.0 ? kl : 0.0;      // np.maximum(0, kls)  (:1126)
   }
   return VBMC_OK;
+}
+
+extern "C" int vbmc_kl_div_mc(vbmc_ctx* ctx, int64_t N, uint64_t seed, int K2, const double* mu2_KxD,
+                              const double* sigma2_K, const double* lambd2_D, const double* w2_K,
+                              double kl_out[2]) {
+  if (!ctx || N < 1 || K2 < 1 || !mu2_KxD || !sigma2_K || !lambd2_D || !w2_K || !kl_out) return VBMC_E_ARG;
+  if (!ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "kl_div: mixture not set");
+  return kl_div_mc_impl(ctx, "kl_div", N, seed, K2, mu2_KxD, sigma2_K, lambd2_D, w2_K, kl_out, nullptr, nullptr);
+}
+
+extern "C" int vbmc_kl_div_mc_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed, int K2, const double* mu2_KxD,
+                                   const double* sigma2_K, const double* lambd2_D, const double* w2_K,
+                                   double kl_out[2]) {
+  if (!ctx || N < 1 || K2 < 1 || !mu2_KxD || !sigma2_K || !lambd2_D || !w2_K || !kl_out) return VBMC_E_ARG;
+  if (!ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "kl_div_orig: mixture not set");
+  XfView t1, t2;
+  int rc = xf_need(ctx, 0, ctx->D, "kl_div_orig", t1);
+  if (rc) return rc;
+  rc = xf_need(ctx, 1, ctx->D, "kl_div_orig", t2);
+  if (rc) return rc;
+  return kl_div_mc_impl(ctx, "kl_div_orig", N, seed, K2, mu2_KxD, sigma2_K, lambd2_D, w2_K, kl_out, &t1, &t2);
 }

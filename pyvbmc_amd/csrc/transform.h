@@ -251,7 +251,12 @@ __device__ __forceinline__ bool xf_inside(const XfView& t, const double (&v)[DP]
   return in;
 }
 
-// host side (transform.hip): a slot's descriptor when it is set for D, and its transform of n device points
+// host side (transform.hip): a slot's descriptor when it is set for D (xf_need: or the failure, prefixed `who`), and
+// the launchers of its kernels on n device points.  apply: dir 0 x -> u, 1 u -> x, 2 log|J|(u).  prep / finish: the
+// front and back of pdf(orig_flag=True) around the density of u.
 struct vbmc_ctx;
 bool xf_view_slot(vbmc_ctx* ctx, int slot, int D, XfView& v);
-int xf_apply_slot(vbmc_ctx* ctx, const XfView& t, int64_t n, int dir, const double* d_in, double* d_out);
+int xf_need(vbmc_ctx* ctx, int slot, int D, const char* who, XfView& v);
+int launch_xf_apply(vbmc_ctx* ctx, const XfView& t, int64_t n, int dir, const double* d_in, double* d_out);
+int launch_xf_prep(vbmc_ctx* ctx, const XfView& t, int64_t n, const double* d_x, double* d_u, double* d_lj, double* d_in);
+int launch_xf_finish(vbmc_ctx* ctx, int64_t n, int log_flag, const double* d_lj, const double* d_in, double* d_y);

@@ -4,8 +4,9 @@
 // ParameterTransformer (parameter_transformer/parameter_transformer.py) restated in transform.h.
 //
 // A context holds two transformer descriptors: slot 0 belongs to the context's mixture, slot 1 to the
-// second mixture of vbmc_kl_div_mc_orig.  Every entry point below works on device-resident points:
-// the samples are drawn, transformed and reduced on the device, and only results cross PCIe.
+// second mixture of vbmc_kl_div_mc_orig.  This file keeps the slots, the transformer's kernels and their launchers
+// (transform.h), vbmc_transform and the Monte-Carlo moments; the original-space sample, pdf and kl_div entry points
+// are the transformed-space ones of sample.hip and mixture.hip with a descriptor passed in.
 #include <cmath>
 #include <cstring>
 
@@ -39,16 +40,6 @@ XfView xf_view(const XfSlot& s) {
   v.has_R = s.has_R ? 1 : 0;
   v.has_scale = s.has_scale ? 1 : 0;
   return v;
-}
-
-// the slot's descriptor, checked against the context's D
-int xf_need(vbmc_ctx* ctx, int slot, int D, const char* who, XfView& v) {
-  XfState* st = xf_state(ctx);
-  const XfSlot& s = st->slot[slot];
-  if (!s.set) return vbmc_fail(ctx, VBMC_E_ARG, "%s: transformer slot %d not set", who, slot);
-  if (s.D != D) return vbmc_fail(ctx, VBMC_E_ARG, "%s: transformer slot %d has D=%d, the mixture D=%d", who, slot, s.D, D);
-  v = xf_view(s);
-  return 0;
 }
 
 constexpr int kThreads = 256;
@@ -222,45 +213,6 @@ void launch_colsum_dp(vbmc_ctx* ctx, const double* x, int64_t n, int D, int nblk
   hipLaunchKernelGGL((col_sum_kernel<DP>), dim3(nblk), dim3(kThreads), 0, ctx->stream, x, n, D, part);
 }
 
-// the padded widths of the mixture kernels (mixture.hip)
-#define XF_DISPATCH(D, CALL)              \
-  do {                                    \
-    if ((D) <= 2) CALL(2);                \
-    else if ((D) <= 4) CALL(4);           \
-    else if ((D) <= 6) CALL(6);           \
-    else if ((D) <= 8) CALL(8);           \
-    else if ((D) <= 10) CALL(10);         \
-    else if ((D) <= 12) CALL(12);         \
-    else if ((D) <= 16) CALL(16);         \
-    else if ((D) <= 20) CALL(20);         \
-    else if ((D) <= 24) CALL(24);         \
-    else CALL(32);                        \
-  } while (0)
-
-int launch_xf_apply(vbmc_ctx* ctx, const XfView& t, int64_t n, int dir, const double* d_in, double* d_out) {
-#define CALL(DP) launch_apply_dp<DP>(ctx, t, n, dir, d_in, d_out)
-  XF_DISPATCH(t.D, CALL);
-#undef CALL
-  HIP_TRY(ctx, hipGetLastError());
-  return 0;
-}
-
-int launch_xf_prep(vbmc_ctx* ctx, const XfView& t, int64_t n, const double* d_x, double* d_u, double* d_lj,
-                   double* d_in) {
-#define CALL(DP) launch_prep_dp<DP>(ctx, t, n, d_x, d_u, d_lj, d_in)
-  XF_DISPATCH(t.D, CALL);
-#undef CALL
-  HIP_TRY(ctx, hipGetLastError());
-  return 0;
-}
-
-int launch_xf_finish(vbmc_ctx* ctx, int64_t n, int log_flag, const double* d_lj, const double* d_in, double* d_y) {
-  hipLaunchKernelGGL(xf_finish_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, ctx->stream, n, log_flag, d_lj, d_in,
-                     d_y);
-  HIP_TRY(ctx, hipGetLastError());
-  return 0;
-}
-
 bool valid_type(double t) { return t == XF_UNBOUNDED || t == XF_LOGIT || t == XF_PROBIT || t == XF_STUDENT4; }
 
 }  // namespace
@@ -281,8 +233,38 @@ bool xf_view_slot(vbmc_ctx* ctx, int slot, int D, XfView& v) {
   return true;
 }
 
-int xf_apply_slot(vbmc_ctx* ctx, const XfView& t, int64_t n, int dir, const double* d_in, double* d_out) {
-  return launch_xf_apply(ctx, t, n, dir, d_in, d_out);
+// the slot's descriptor, checked against the context's D
+int xf_need(vbmc_ctx* ctx, int slot, int D, const char* who, XfView& v) {
+  XfState* st = xf_state(ctx);
+  const XfSlot& s = st->slot[slot];
+  if (!s.set) return vbmc_fail(ctx, VBMC_E_ARG, "%s: transformer slot %d not set", who, slot);
+  if (s.D != D) return vbmc_fail(ctx, VBMC_E_ARG, "%s: transformer slot %d has D=%d, the mixture D=%d", who, slot, s.D, D);
+  v = xf_view(s);
+  return 0;
+}
+
+int launch_xf_apply(vbmc_ctx* ctx, const XfView& t, int64_t n, int dir, const double* d_in, double* d_out) {
+#define CALL(DP) launch_apply_dp<DP>(ctx, t, n, dir, d_in, d_out)
+  VBMC_DISPATCH_DP(t.D, CALL);
+#undef CALL
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
+int launch_xf_prep(vbmc_ctx* ctx, const XfView& t, int64_t n, const double* d_x, double* d_u, double* d_lj,
+                   double* d_in) {
+#define CALL(DP) launch_prep_dp<DP>(ctx, t, n, d_x, d_u, d_lj, d_in)
+  VBMC_DISPATCH_DP(t.D, CALL);
+#undef CALL
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
+int launch_xf_finish(vbmc_ctx* ctx, int64_t n, int log_flag, const double* d_lj, const double* d_in, double* d_y) {
+  hipLaunchKernelGGL(xf_finish_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, ctx->stream, n, log_flag, d_lj, d_in,
+                     d_y);
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
 }
 
 extern "C" int vbmc_set_transformer(vbmc_ctx* ctx, int slot, int D, const double* type_D, const double* lb_D,
@@ -371,83 +353,6 @@ extern "C" int vbmc_transform(vbmc_ctx* ctx, int64_t n, int direction, const dou
   return VBMC_OK;
 }
 
-extern "C" int vbmc_mixture_sample_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed, int balance_flag, double df,
-                                        double* x_NxD, int32_t* comp_N) {
-  if (!ctx || N < 0) return VBMC_E_ARG;
-  if (df < 0.0 || df != df)
-    return vbmc_fail(ctx, VBMC_E_ARG, "mixture_sample_orig: df=%g (the reference's gamma draw needs df > 0)", df);
-  if (!ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "mixture_sample_orig: mixture not set");
-  XfView t;
-  int rc = xf_need(ctx, 0, ctx->D, "mixture_sample_orig", t);
-  if (rc) return rc;
-  if (N == 0) return VBMC_OK;
-  NEED_DEVICE(ctx);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int D = ctx->D, K = ctx->K;
-  // the samples of vbmc_mixture_sample_t (one launch over all N), inverse-transformed where they lie
-  const size_t n_x = x_NxD ? (size_t)N * D : 0;
-  const size_t n_c = comp_N ? ((size_t)N + 1) / 2 : 0;
-  rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, n_x + n_c + (size_t)2 * K + 2);
-  if (rc) return rc;
-  double* d_x = x_NxD ? ctx->d_scratch : nullptr;
-  int32_t* d_c = comp_N ? (int32_t*)(ctx->d_scratch + n_x) : nullptr;
-  void* d_sel = (void*)(ctx->d_scratch + n_x + n_c);
-  rc = launch_sample(ctx, ctx->d_mix, ctx->ml, ctx->w.data(), N, seed, balance_flag, d_sel, d_x, d_c, df);
-  if (rc) return rc;
-  if (x_NxD) {
-    rc = launch_xf_apply(ctx, t, N, 1, d_x, d_x);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(x_NxD, d_x, sizeof(double) * n_x, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (comp_N) HIP_TRY(ctx, hipMemcpyAsync(comp_N, d_c, sizeof(int32_t) * N, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, stream_wait(ctx));
-  return VBMC_OK;
-}
-
-extern "C" int vbmc_mixture_pdf_orig(vbmc_ctx* ctx, int64_t n, const double* x_nxD, int log_flag, int grad_flag,
-                                     double df, double* y_n, double* dy_nxD) {
-  if (!ctx || (n > 0 && (!x_nxD || !y_n))) return VBMC_E_ARG;
-  if (!ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "mixture_pdf_orig: mixture not set");
-  if (grad_flag && !dy_nxD) return vbmc_fail(ctx, VBMC_E_ARG, "mixture_pdf_orig: grad_flag without dy");
-  if (grad_flag && std::isfinite(df) && df != 0.0)
-    return vbmc_fail(ctx, VBMC_E_UNSUP, "Gradient of heavy-tailed pdf not supported yet.");
-  if (grad_flag && log_flag)
-    return vbmc_fail(ctx, VBMC_E_UNSUP,
-                     "vbmc_pdf:NoOriginalGrad: Gradient computation in original space not supported yet.");
-  XfView t;
-  int rc = xf_need(ctx, 0, ctx->D, "mixture_pdf_orig", t);
-  if (rc) return rc;
-  if (n == 0) return VBMC_OK;
-  NEED_DEVICE(ctx);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int D = ctx->D;
-  const int64_t BATCH = 1 << 22;
-  const size_t per = (size_t)D + 3 + (grad_flag ? D : 0);
-  const int64_t nb = n < BATCH ? n : BATCH;
-  rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, per * (size_t)nb);
-  if (rc) return rc;
-  double* d_x = ctx->d_scratch;  // x, then u in place
-  double* d_y = d_x + (size_t)nb * D;
-  double* d_lj = d_y + nb;
-  double* d_in = d_lj + nb;
-  double* d_dy = d_in + nb;
-  for (int64_t o = 0; o < n; o += nb) {
-    const int64_t m = (n - o) < nb ? (n - o) : nb;
-    HIP_TRY(ctx, hipMemcpyAsync(d_x, x_nxD + o * D, sizeof(double) * m * D, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_xf_prep(ctx, t, m, d_x, d_x, d_lj, d_in);
-    if (rc) return rc;
-    rc = launch_mixture_pdf(ctx, m, d_x, log_flag, grad_flag, df, d_y, grad_flag ? d_dy : nullptr);
-    if (rc) return rc;
-    rc = launch_xf_finish(ctx, m, log_flag, d_lj, d_in, d_y);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(y_n + o, d_y, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
-    if (grad_flag)
-      HIP_TRY(ctx, hipMemcpyAsync(dy_nxD + o * D, d_dy, sizeof(double) * m * D, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, stream_wait(ctx));
-  }
-  return VBMC_OK;
-}
-
 extern "C" int vbmc_mixture_moments_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed, int cov_flag, double* mean_D,
                                          double* cov_DxD) {
   if (!ctx || N < 1 || !mean_D || (cov_flag && !cov_DxD)) return VBMC_E_ARG;
@@ -474,7 +379,7 @@ extern "C" int vbmc_mixture_moments_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed
   if (rc) return rc;
   // np.mean(x, axis=0) = sum / N; np.cov(x.T): centred products times 1 / (N - 1)
 #define CALL(DP) launch_colsum_dp<DP>(ctx, d_x, N, D, nblk, d_part)
-  XF_DISPATCH(D, CALL);
+  VBMC_DISPATCH_DP(D, CALL);
 #undef CALL
   HIP_TRY(ctx, hipGetLastError());
   hipLaunchKernelGGL(part_reduce_kernel, dim3(D), dim3(kThreads), 0, ctx->stream, (const double*)d_part, nblk, D, 0.0,
@@ -495,75 +400,5 @@ extern "C" int vbmc_mixture_moments_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed
   if (cov_flag)
     for (int i = 0, p = 0; i < D; ++i)
       for (int j = i; j < D; ++j, ++p) cov_DxD[i * D + j] = cov_DxD[j * D + i] = tri[p];
-  return VBMC_OK;
-}
-
-extern "C" int vbmc_kl_div_mc_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed, int K2, const double* mu2_KxD,
-                                   const double* sigma2_K, const double* lambd2_D, const double* w2_K,
-                                   double kl_out[2]) {
-  if (!ctx || N < 1 || K2 < 1 || !mu2_KxD || !sigma2_K || !lambd2_D || !w2_K || !kl_out) return VBMC_E_ARG;
-  if (!ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "kl_div_orig: mixture not set");
-  XfView t1, t2;
-  int rc = xf_need(ctx, 0, ctx->D, "kl_div_orig", t1);
-  if (rc) return rc;
-  rc = xf_need(ctx, 1, ctx->D, "kl_div_orig", t2);
-  if (rc) return rc;
-  NEED_DEVICE(ctx);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int D = ctx->D, K1 = ctx->K;
-  for (int k = 0; k < K2; ++k)
-    if (!(sigma2_K[k] > 0.0) || !std::isfinite(sigma2_K[k]))
-      return vbmc_fail(ctx, VBMC_E_NONFINITE, "kl_div_orig: sigma2[%d] must be finite and > 0", k);
-  MixLayout ml2;
-  ml2.plan(D, K2);
-  std::vector<double> pack2((size_t)ml2.total);
-  write_mixture_pack(ml2, mu2_KxD, sigma2_K, lambd2_D, w2_K, pack2.data());
-  const int nblk = 512;
-  const int Kmax = K1 > K2 ? K1 : K2;
-  const size_t need = (size_t)ml2.total + 2 * (size_t)N * D + 4 * (size_t)N + (size_t)2 * Kmax + 2 + 2 * (size_t)nblk;
-  rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, need);
-  if (rc) return rc;
-  double* d_pack2 = ctx->d_scratch;
-  double* d_x = d_pack2 + ml2.total;
-  double* d_u = d_x + (size_t)N * D;
-  double* d_y1 = d_u + (size_t)N * D;
-  double* d_y2 = d_y1 + N;
-  double* d_lj = d_y2 + N;
-  double* d_in = d_lj + N;
-  void* d_sel = (void*)(d_in + N);
-  double* d_part = (double*)d_sel + 2 * Kmax + 2;
-  HIP_TRY(ctx, hipMemcpyAsync(d_pack2, pack2.data(), sizeof(double) * ml2.total, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, stream_wait(ctx));
-  std::vector<double> part(2 * (size_t)nblk);
-  for (int dir = 0; dir < 2; ++dir) {
-    // dir 0: xx1 = vp1.sample(N, True, True) (:1110); dir 1: xx2 = vp2.sample(N, True, True) (:1117)
-    const double* d_own = dir == 0 ? ctx->d_mix : d_pack2;
-    const MixLayout& ml_own = dir == 0 ? ctx->ml : ml2;
-    const double* w_own = dir == 0 ? ctx->w.data() : w2_K;
-    rc = launch_sample(ctx, d_own, ml_own, w_own, N, seed + (uint64_t)dir, 1, d_sel, d_x, nullptr, INFINITY);
-    if (rc) return rc;
-    rc = launch_xf_apply(ctx, dir == 0 ? t1 : t2, N, 1, d_x, d_x);
-    if (rc) return rc;
-    // q1 = vp1.pdf(xx, True), q2 = vp2.pdf(xx, True): each in its own transformed space, Jacobian divided out
-    for (int m = 0; m < 2; ++m) {
-      double* d_y = m == 0 ? d_y1 : d_y2;
-      rc = launch_xf_prep(ctx, m == 0 ? t1 : t2, N, d_x, d_u, d_lj, d_in);
-      if (rc) return rc;
-      rc = launch_mixture_pdf_on(ctx, m == 0 ? ctx->d_mix : d_pack2, m == 0 ? ctx->ml : ml2, N, d_u, 0, d_y);
-      if (rc) return rc;
-      rc = launch_xf_finish(ctx, N, 0, d_lj, d_in, d_y);
-      if (rc) return rc;
-    }
-    rc = launch_kl_terms(ctx, dir == 0 ? d_y1 : d_y2, dir == 0 ? d_y2 : d_y1, N, nblk, d_part + (size_t)dir * nblk);
-    if (rc) return rc;
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(part.data(), d_part, sizeof(double) * 2 * nblk, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, stream_wait(ctx));
-  for (int dir = 0; dir < 2; ++dir) {
-    double s = 0.0;
-    for (int b = 0; b < nblk; ++b) s += part[(size_t)dir * nblk + b];
-    const double kl = -s / (double)N;   // -mean(log q_other - log q_own)
-    kl_out[dir] = kl > 0.0 ? kl : 0.0;  // np.maximum(0, kls)  (:1126)
-  }
   return VBMC_OK;
 }

@@ -48,6 +48,33 @@ def _randn(n, d):
     return np.random.randn(n, d)
 
 
+def _rng_mode(rng, check=True):
+    """``rng``, or the environment's default when it is None; an unknown name raises unless ``check`` is off."""
+    mode = os.environ.get("VBMC_HIP_RNG", "numpy") if rng is None else rng
+    if check and mode not in ("numpy", "philox"):
+        raise ValueError(f"unknown rng {mode!r}")
+    return mode
+
+
+def _seed_or_draw(seed):
+    """``seed`` of the device generator, drawn from NumPy's global stream when it is None."""
+    return int(np.random.randint(0, 2**62, dtype=np.int64)) if seed is None else seed
+
+
+def _mixture_args(vp):
+    """``(mu.T, sigma, lambd, w)`` of ``vp`` as contiguous float64 arrays: a second mixture of the C ABI."""
+    return (_lib.f64(np.asarray(vp.mu, dtype=np.float64).reshape(vp.D, vp.K).T), _lib.f64(np.ravel(vp.sigma)),
+            _lib.f64(np.ravel(vp.lambd)), _lib.f64(np.ravel(vp.w)))
+
+
+def _shape_pdf(y, dy, in_dims, grad_flag):
+    """``pdf``'s result from y (n x 1) and dy: a pair with the gradient, raveled for a 1-D input."""
+    out = (y, dy) if grad_flag else y
+    if in_dims == 1:
+        return tuple(o.ravel() for o in out) if grad_flag else out.ravel()
+    return out
+
+
 class IdentityTransformer:
     """Unbounded-space parameter transformer (the reference's default
     ``ParameterTransformer(D)`` with infinite bounds is the identity map).  Any
@@ -167,12 +194,11 @@ class VariationalPosterior:
         balanced samples grouped by component; ``True`` permutes them like the reference)."""
         if N < 1:
             return np.zeros((0, self.D)), np.zeros((0, 1))
-        mode = os.environ.get("VBMC_HIP_RNG", "numpy") if rng is None else rng
+        mode = _rng_mode(rng, check=False)
         if mode == "philox" and not (np.isfinite(df) and df < 0):  # (df < 0: numpy's gamma raises, below)
             N = int(N)
             ctx = self._upload()
-            if seed is None:
-                seed = int(np.random.randint(0, 2**62, dtype=np.int64))
+            seed = _seed_or_draw(seed)
             x = np.empty((N, self.D))
             i = np.empty(N, dtype=np.int32)
             tdf = float(df) if (np.isfinite(df) and df != 0) else float("inf")
@@ -186,8 +212,7 @@ class VariationalPosterior:
             if orig_flag and not on_dev:
                 x = self.parameter_transformer.inverse(x)
             return x, (i.astype(np.int64) if self.K > 1 else np.zeros(N))
-        if mode not in ("numpy", "philox"):
-            raise ValueError(f"unknown rng {mode!r}")
+        _rng_mode(mode)  # (an unknown name raises here, after the device branch)
         lam = self.lambd.reshape(1, -1)
         heavy = np.isfinite(df) and df != 0
         if self.K > 1:
@@ -288,10 +313,7 @@ class VariationalPosterior:
                 y[mask] -= ladj
             else:
                 y[mask] /= np.exp(ladj)
-        out = (y, dy) if grad_flag else y
-        if in_dims == 1:
-            return tuple(o.ravel() for o in out) if grad_flag else out.ravel()
-        return out
+        return _shape_pdf(y, dy, in_dims, grad_flag)
 
     def _pdf_orig_device(self, ctx, x, in_dims, log_flag, grad_flag, df):
         """pdf(orig_flag=True) in one device call (vbmc_mixture_pdf_orig): bound mask, transform, density,
@@ -303,11 +325,7 @@ class VariationalPosterior:
         dy = np.empty((n, D)) if grad_flag else None
         ctx.check(ctx._lib.vbmc_mixture_pdf_orig(ctx._h, n, _lib.ptr(x), int(bool(log_flag)), int(bool(grad_flag)),
                                                  float(df), _lib.ptr(y), _lib.ptr(dy)))
-        y = y.reshape(n, 1)
-        out = (y, dy) if grad_flag else y
-        if in_dims == 1:
-            return tuple(o.ravel() for o in out) if grad_flag else out.ravel()
-        return out
+        return _shape_pdf(y.reshape(n, 1), dy, in_dims, grad_flag)
 
     def log_pdf(self, *args, **kwargs):
         return self.pdf(*args, **kwargs, log_flag=True)
@@ -360,13 +378,12 @@ class VariationalPosterior:
 
     # -- moments (:761-808) ----------------------------------------------------------------------
     def moments(self, N=int(1e6), orig_flag=True, cov_flag=False, *, rng=None, seed=None):
-        mode = os.environ.get("VBMC_HIP_RNG", "numpy") if rng is None else rng
+        mode = _rng_mode(rng, check=False)
         ctx = self._upload() if orig_flag and mode == "philox" else None
         if ctx is not None and _xf.upload(self.parameter_transformer, ctx, 0, self.D) is not None:
             # the balanced samples of sample(N, True, True, rng="philox", seed=seed), reduced where they are drawn
             N = int(N)
-            if seed is None:
-                seed = int(np.random.randint(0, 2**62, dtype=np.int64))
+            seed = _seed_or_draw(seed)
             mubar = np.empty(self.D)
             cov = np.empty((self.D, self.D)) if cov_flag else None
             ctx.check(ctx._lib.vbmc_mixture_moments_orig(ctx._h, N, int(seed), int(bool(cov_flag)), _lib.ptr(mubar),
@@ -406,9 +423,7 @@ class VariationalPosterior:
         step of 1e-12, so the result is a stationary point to a much tighter tolerance than SciPy's.  Without
         a device (or with a transformer that cannot go to one and ``orig_flag=True``) a NumPy / SciPy loop
         with the reference's structure runs around ``sample`` / ``pdf``."""
-        mode = os.environ.get("VBMC_HIP_RNG", "numpy") if rng is None else rng
-        if mode not in ("numpy", "philox"):
-            raise ValueError(f"unknown rng {mode!r}")
+        mode = _rng_mode(rng)
         if n_opts is None:
             n_opts = int(np.ceil(np.sqrt(self.K)))
         n_opts = int(n_opts)
@@ -437,8 +452,8 @@ class VariationalPosterior:
             cand = np.empty((n_opts, n, D))
             for k in range(n_opts):
                 cand[k] = self.sample(n, orig_flag, rng="numpy")[0]
-        elif seed is None:
-            seed = int(np.random.randint(0, 2**62, dtype=np.int64))
+        else:
+            seed = _seed_or_draw(seed)
         ctx = self._upload(ctx)
         if orig_flag:  # (sample may have put another transformer in the slot)
             _xf.upload(_device_pt(self), ctx, 0, D)
@@ -520,7 +535,7 @@ class VariationalPosterior:
             raise ValueError("Either vp2 or samples have to be not None")
         if not gauss_flag and vp2 is None:
             raise ValueError("Unless the KL divergence is gaussianized, VP2 is required.")
-        mode = os.environ.get("VBMC_HIP_RNG", "numpy") if rng is None else rng
+        mode = _rng_mode(rng, check=False)
         if gauss_flag:
             if N == 0:
                 raise ValueError("Analytical moments are available only for the transformed space.")
@@ -531,27 +546,13 @@ class VariationalPosterior:
                 q2mu = np.mean(samples)  # sic (:1103)
                 q2sigma = np.cov(samples.T)
             kls = kl_div_mvn(q1mu, q1sigma, q2mu, q2sigma)
-        elif mode == "philox" and _same_transformer(self, vp2) and vp2.D == self.D:
-            ctx = self._upload()
-            if seed is None:
-                seed = int(np.random.randint(0, 2**62, dtype=np.int64))
-            mu2 = _lib.f64(np.asarray(vp2.mu, dtype=np.float64).reshape(vp2.D, vp2.K).T)
-            sg2, lm2, w2 = _lib.f64(np.ravel(vp2.sigma)), _lib.f64(np.ravel(vp2.lambd)), _lib.f64(np.ravel(vp2.w))
-            kls = np.empty(2)
-            ctx.check(ctx._lib.vbmc_kl_div_mc(ctx._h, int(N), int(seed), vp2.K, _lib.ptr(mu2), _lib.ptr(sg2),
-                                              _lib.ptr(lm2), _lib.ptr(w2), _lib.ptr(kls)))
-        elif (mode == "philox" and vp2.D == self.D
-              and _xf.upload(self.parameter_transformer, self._upload(), 0, self.D) is not None
-              and _xf.upload(vp2.parameter_transformer, self.ctx, 1, vp2.D) is not None):
-            # different transformers: both sides in original space, one device call (vbmc_kl_div_mc_orig)
+        elif mode == "philox" and (fn := self._kl_device_fn(vp2)) is not None:
             ctx = self.ctx
-            if seed is None:
-                seed = int(np.random.randint(0, 2**62, dtype=np.int64))
-            mu2 = _lib.f64(np.asarray(vp2.mu, dtype=np.float64).reshape(vp2.D, vp2.K).T)
-            sg2, lm2, w2 = _lib.f64(np.ravel(vp2.sigma)), _lib.f64(np.ravel(vp2.lambd)), _lib.f64(np.ravel(vp2.w))
+            seed = _seed_or_draw(seed)
+            mu2, sg2, lm2, w2 = _mixture_args(vp2)
             kls = np.empty(2)
-            ctx.check(ctx._lib.vbmc_kl_div_mc_orig(ctx._h, int(N), int(seed), vp2.K, _lib.ptr(mu2), _lib.ptr(sg2),
-                                                   _lib.ptr(lm2), _lib.ptr(w2), _lib.ptr(kls)))
+            ctx.check(fn(ctx._h, int(N), int(seed), vp2.K, _lib.ptr(mu2), _lib.ptr(sg2), _lib.ptr(lm2), _lib.ptr(w2),
+                         _lib.ptr(kls)))
         else:
             minp = sys.float_info.min
             xx1, _ = self.sample(N, True, True, rng=rng, seed=seed, shuffle=False)
@@ -571,6 +572,17 @@ class VariationalPosterior:
             kls = np.concatenate((kl1, kl2), axis=None)
         return np.maximum(0, kls)  # correct for numerical errors (:1126)
 
+    def _kl_device_fn(self, vp2):
+        """The C function that runs kl_div's Monte-Carlo branch against ``vp2`` in one device call, with this
+        mixture uploaded and the transformers it needs in their slots; None when there is none."""
+        if _same_transformer(self, vp2) and vp2.D == self.D:
+            return self._upload()._lib.vbmc_kl_div_mc
+        if (vp2.D == self.D and _xf.upload(self.parameter_transformer, self._upload(), 0, self.D) is not None
+                and _xf.upload(vp2.parameter_transformer, self.ctx, 1, vp2.D) is not None):
+            # different transformers: both sides in original space (vbmc_kl_div_mc_orig)
+            return self.ctx._lib.vbmc_kl_div_mc_orig
+        return None
+
     # -- marginal total variation (:921-1030) ----------------------------------------------------------
     def mtv(self, vp2=None, samples=None, N=int(1e5), *, rng=None, seed=None):
         """Marginal total variation distances to ``vp2`` or to ``samples``, a ``(1, D)`` array; reference
@@ -580,9 +592,7 @@ class VariationalPosterior:
         them to the host.  Everything after the sampling is one device call (vbmc_mtv)."""
         if vp2 is None and samples is None:
             raise ValueError("Either vp2 or samples have to be not None")
-        mode = os.environ.get("VBMC_HIP_RNG", "numpy") if rng is None else rng
-        if mode not in ("numpy", "philox"):
-            raise ValueError(f"unknown rng {mode!r}")
+        mode = _rng_mode(rng)
         D, N = self.D, int(N)
         if vp2 is not None and vp2.D != D:
             raise ValueError(f"vp2 has D={vp2.D}, this posterior D={D}")
@@ -591,8 +601,8 @@ class VariationalPosterior:
             if samples.ndim != 2 or samples.shape[1] != D:
                 raise ValueError(f"samples of shape {samples.shape}, the posterior D={D}")
         ctx = self._upload()
-        if mode == "philox" and seed is None:
-            seed = int(np.random.randint(0, 2**62, dtype=np.int64))
+        if mode == "philox":
+            seed = _seed_or_draw(seed)
         held = []  # arrays the sides point at, alive until the call returns
 
         def bounds(pt):
@@ -626,9 +636,7 @@ class VariationalPosterior:
             _xf.upload(_device_pt(self), ctx, 0, D)
         K2, mix2 = 0, (None,) * 4
         if s2.source == _lib.MTV_MIX2:
-            K2 = vp2.K
-            mix2 = (_lib.f64(np.asarray(vp2.mu, dtype=np.float64).reshape(D, K2).T), _lib.f64(np.ravel(vp2.sigma)),
-                    _lib.f64(np.ravel(vp2.lambd)), _lib.f64(np.ravel(vp2.w)))
+            K2, mix2 = vp2.K, _mixture_args(vp2)
         out = np.empty(D)
         info = np.empty((2 * D, 2), dtype=np.int64)
         from .stats import _call_checked, _raise_degenerate

@@ -232,7 +232,7 @@ def test_wide_fixture_is_consistent(golden, name):
 def test_wide_fixture_covers_every_width(golden):
     g = golden("transform_wide")
     Ds = sorted(int(n[1:]) for n in WIDE_CASES)
-    dp = [2, 4, 6, 8, 10, 12, 16, 20, 24, 32]  # the device kernels' padded widths (XF_DISPATCH)
+    dp = [2, 4, 6, 8, 10, 12, 16, 20, 24, 32]  # the device kernels' padded widths (VBMC_DISPATCH_DP)
     assert {min(p for p in dp if p >= D) for D in Ds} == set(dp) - {4}  # (D = 3..5: transform.npz's cases)
     assert any(D < 8 for D in Ds) and any(D > 8 and D % 8 for D in Ds) and any(D % 8 == 0 and D > 8 for D in Ds)
     types = {t: [int(n[1:]) for n in WIDE_CASES if t in g[f"{n}_type"]] for t in (3.0, 12.0, 13.0)}
