@@ -51,11 +51,8 @@ __global__ __launch_bounds__(256) void adam_pre_kernel(AdamDev a) {
 
 // ---------------------------------------------------------------------------
 // adam_step_kernel (one workgroup, main stream): the only work between the entropy reduction and
-// the next iteration's table launch.  dF = pre + Jacobian(entropy gradient) (entmc_vbmc.py:114-130),
-// the Adam update with the box clamp (minimize_adam.py:89-105), then set_parameters + mixture pack
-// of the new iterate.  Every array that is read exactly once (entropy sums, pre, m, v, box) goes
-// from global memory straight to registers in one batch of independent loads; only theta and the
-// mixture attributes, which the pack re-reads across barriers, live in LDS.
+// the next iteration's table launch: the step (adam_dev.h adam_step_body), then set_parameters + mixture pack
+// of the new iterate.  Only theta and the mixture attributes, which the pack re-reads across barriers, live in LDS.
 template <bool LDS>
 __global__ __launch_bounds__(256) void adam_step_kernel(AdamDev a, int do_step, GenSlice gen) {
   extern __shared__ double sh[];
@@ -66,24 +63,11 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamDev a, int do_step, 
     gen_slice_block(gen, blockIdx.x - 1, threadIdx.x);
     return;
   }
-  const int D = a.D, K = a.K, tid = threadIdx.x, n = a.n_theta;
+  const int tid = threadIdx.x, n = a.n_theta;
   const AdamLayout& L = a.lay;
   double* theta = LDS ? sh : a.state + L.o_theta();
   double* aux = LDS ? sh + n : a.state + L.o_aux();
   double* ee = LDS ? sh + n + L.n_aux : a.ee;
-  const double* raw = a.state + L.o_raw();
-  const bool o_mu = a.mask & 1, o_sg = a.mask & 2, o_lm = a.mask & 4, o_w = a.mask & 8;
-  const int p_sg = o_mu ? D * K : 0, p_lm = p_sg + (o_sg ? K : 0), p_w = n - K;
-  const int f_w = 1 + D * K + K + D;  // weight block of the entropy accumulator
-
-  constexpr int U = 4;
-  double r_raw[U], r_pre[U], r_m[U], r_v[U], r_lo[U], r_hi[U];
-  double rw = 0.0;
-  int iter = 0;
-  if (do_step) {
-    iter = a.iter_base[0] + a.it_off;
-    if (o_w && tid < K) rw = raw[f_w + tid];  // K <= 256 per pass below
-  }
   if (LDS) {
     const int cnt = L.o_hyp();  // theta | aux: eight loads in flight per thread and round
     constexpr int UC = 8;
@@ -98,98 +82,16 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamDev a, int do_step, 
       }
     }
   }
-  // which accumulator entry / Jacobian scale belongs to theta index i
-  auto raw_index = [&](int i) -> int {
-    if (o_mu && i < D * K) return 1 + i;
-    if (o_sg && i >= p_sg && i < p_sg + K) return 1 + D * K + (i - p_sg);
-    if (o_lm && i >= p_lm && i < p_lm + D) return 1 + D * K + K + (i - p_lm);
-    return f_w + (i - p_w);
-  };
-  auto load_chunk = [&](int base) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = base + u * 256 + tid;
-      const bool in = i < n;
-      r_raw[u] = in ? raw[raw_index(i)] : 0.0;
-      r_pre[u] = in ? a.pre[i] : 0.0;
-      r_m[u] = in ? a.state[L.o_m() + i] : 0.0;
-      r_v[u] = in ? a.state[L.o_v() + i] : 0.0;
-      r_lo[u] = (in && a.has_box) ? a.state[L.o_xlb() + i] : 0.0;
-      r_hi[u] = (in && a.has_box) ? a.state[L.o_xub() + i] : 0.0;
-    }
-  };
-  if (do_step) load_chunk(0);
-  // minimize_adam.py:92-98 (evaluated while the loads above are in flight)
-  // beta^(i+1) and exp(-(i+1)/decay) as exp2 of host-prepared logarithms (pow() is ~200 dependent
-  // instructions; the powers are accurate to ~1e-15 relative for any iteration count in use)
-  const double it1 = (double)(iter + 1);
-  const double c1 = 1.0 / (1.0 - fm::exp2_fast(it1 * a.l2_beta1));
-  const double c2 = 1.0 / (1.0 - fm::exp2_fast(it1 * a.l2_beta2));
-  const double step = a.master_min + (a.master_max - a.master_min) * fm::exp2_fast(-it1 * a.l2e_over_decay);
-  double* x_row = a.x_tab + (size_t)iter * n;
-  double* y_out = a.y_tab + 3 * (size_t)iter;
-  __syncthreads();
-
   if (do_step) {
-    const double* sg = aux + K * D;
-    const double* lm = sg + K;
-    const double* eta = lm + D + K;
-    // ---- softmax Jacobian of the entropy's weight gradient: needs two sums over k ----
-    double sm_s = 1.0, sm_dot = 0.0;
-    if (o_w) {
-      double ps = 0.0, pd = 0.0;
-      for (int k = tid; k < K; k += 256) {
-        const double e = fm::exp2_fast(0x1.71547652b82fep+0 * eta[k]);
-        ee[k] = e;
-        ps += e;
-        pd += e * (k == tid ? rw : raw[f_w + k]);
-      }
-      ps = wave_sum(ps);
-      pd = wave_sum(pd);
-      if ((tid & 63) == 0) {
-        red[tid >> 6] = ps;
-        red[4 + (tid >> 6)] = pd;
-      }
-      __syncthreads();
-      sm_s = (red[0] + red[1]) + (red[2] + red[3]);
-      sm_dot = (red[4] + red[5]) + (red[6] + red[7]);
-    }
-    if (tid == 0) {
-      const double G = a.pre[n], loss = a.pre[n + 1], H = raw[0];
-      y_out[0] = -G - H + loss;
-      y_out[1] = G;
-      y_out[2] = H;
-    }
-    for (int base = 0; base < n; base += 256 * U) {
-      if (base > 0) load_chunk(base);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int i = base + u * 256 + tid;
-        if (i >= n) continue;
-        // ---- dF: pre + Jacobian of the entropy part of F = -G - H ----
-        double g;
-        if (o_mu && i < D * K) {
-          g = r_pre[u] - r_raw[u];
-        } else if (o_sg && i >= p_sg && i < p_sg + K) {
-          g = r_pre[u] - r_raw[u] * sg[i - p_sg];
-        } else if (o_lm && i >= p_lm && i < p_lm + D) {
-          g = r_pre[u] - r_raw[u] * lm[i - p_lm];
-        } else {
-          const double e = ee[i - p_w];
-          g = r_pre[u] + (e * sm_dot / (sm_s * sm_s) - e * r_raw[u] / sm_s);
-        }
-        // ---- Adam update (minimize_adam.py:89-105) ----
-        const double m = a.beta1 * r_m[u] + (1.0 - a.beta1) * g;
-        const double v = a.beta2 * r_v[u] + (1.0 - a.beta2) * (g * g);
-        a.state[L.o_m() + i] = m;
-        a.state[L.o_v() + i] = v;
-        const double m_hat = m * c1, v_hat = v * c2;
-        double x = theta[i] - step * m_hat / (sqrt(v_hat) + a.fudge);
-        if (a.has_box) x = fmin(r_hi[u], fmax(r_lo[u], x));
-        theta[i] = x;
-        x_row[i] = x;
-      }
-    }
+    const double* raw = a.state + L.o_raw();
+    adam_step_body(
+        a, a.iter_base[0] + a.it_off, theta, aux, ee, red, true, [&](int i) { return raw[i]; },
+        [&](int i, double m, double v) {
+          a.state[L.o_m() + i] = m;
+          a.state[L.o_v() + i] = v;
+        },
+        [] {});
+  } else {
     __syncthreads();
   }
 
@@ -232,7 +134,7 @@ __global__ __launch_bounds__(256) void adam_tail_kernel(AdamDev a, TailArgs t) {
   extern __shared__ double sh[];
   __shared__ double red[16];
   __shared__ int s_ok;
-  const int D = a.D, K = a.K, tid = threadIdx.x, n = a.n_theta;
+  const int K = a.K, tid = threadIdx.x, n = a.n_theta;
   const AdamLayout& L = a.lay;
   const int n_main = (L.n_raw + 3) / 4;
   if ((int)blockIdx.x < n_main + K) __builtin_amdgcn_s_setprio(3);  // the chain's blocks before the draws' on every SIMD they share
@@ -248,23 +150,7 @@ __global__ __launch_bounds__(256) void adam_tail_kernel(AdamDev a, TailArgs t) {
   const bool writer = tb == 0;
   TAIL_STAMP(0);
   // ---- wait for the reduction (bounded) ----
-  if (tid == 0) {
-    const unsigned long long t0 = wall_clock64();
-    int ok = 1;
-    while (__hip_atomic_load(t.red.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != t.red.seq) {
-      if (wall_clock64() - t0 > t.timeout) {
-        ok = 0;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(8);
-    }
-    s_ok = ok;
-  }
-  __syncthreads();
-  if (!s_ok) {
-    if (tid == 0) atomicOr(a.status, 8);
-    return;
-  }
+  if (!bounded_wait<8>(a, t.red.flag, t.timeout, &s_ok, [&](uint64_t w) { return w == t.red.seq; })) return;
   TAIL_STAMP(1);
   // LDS: theta n | aux | ee K | pack | table scratch K4 DP | new m, new v (writer)
   double* theta = sh;
@@ -274,109 +160,20 @@ __global__ __launch_bounds__(256) void adam_tail_kernel(AdamDev a, TailArgs t) {
   double* tsc = pack + a.ml.total;
   double* new_m = tsc + t.K4 * t.DP;
   double* new_v = new_m + n;
+  for (int i = tid; i < L.o_hyp(); i += 256) sh[i] = a.state[i];  // theta | aux
   // the raw vector was written through by the reduction's blocks of this launch: read past this CU's L1 (agent-scope loads;
   // an acquire fence instead costs ~2 us on the chain); everything else read here was written by earlier launches
   const double* raw_p = a.state + L.o_raw();
-  auto raw = [&](int i) { return __hip_atomic_load(raw_p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-  const bool o_mu = a.mask & 1, o_sg = a.mask & 2, o_lm = a.mask & 4, o_w = a.mask & 8;
-  const int p_sg = o_mu ? D * K : 0, p_lm = p_sg + (o_sg ? K : 0), p_w = n - K;
-  const int f_w = 1 + D * K + K + D;
-
-  constexpr int U = 4;
-  double r_raw[U], r_pre[U], r_m[U], r_v[U], r_lo[U], r_hi[U];
-  double rw = 0.0;
-  const int iter = a.iter_base[0] + a.it_off;
-  if (o_w && tid < K) rw = raw(f_w + tid);
-  for (int i = tid; i < L.o_hyp(); i += 256) sh[i] = a.state[i];  // theta | aux
-  auto raw_index = [&](int i) -> int {
-    if (o_mu && i < D * K) return 1 + i;
-    if (o_sg && i >= p_sg && i < p_sg + K) return 1 + D * K + (i - p_sg);
-    if (o_lm && i >= p_lm && i < p_lm + D) return 1 + D * K + K + (i - p_lm);
-    return f_w + (i - p_w);
-  };
-  auto load_chunk = [&](int base) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = base + u * 256 + tid;
-      const bool in = i < n;
-      r_raw[u] = in ? raw(raw_index(i)) : 0.0;
-      r_pre[u] = in ? a.pre[i] : 0.0;
-      r_m[u] = in ? a.state[L.o_m() + i] : 0.0;
-      r_v[u] = in ? a.state[L.o_v() + i] : 0.0;
-      r_lo[u] = (in && a.has_box) ? a.state[L.o_xlb() + i] : 0.0;
-      r_hi[u] = (in && a.has_box) ? a.state[L.o_xub() + i] : 0.0;
-    }
-  };
-  load_chunk(0);
-  const double it1 = (double)(iter + 1);
-  const double c1 = 1.0 / (1.0 - fm::exp2_fast(it1 * a.l2_beta1));
-  const double c2 = 1.0 / (1.0 - fm::exp2_fast(it1 * a.l2_beta2));
-  const double step = a.master_min + (a.master_max - a.master_min) * fm::exp2_fast(-it1 * a.l2e_over_decay);
-  double* x_row = a.x_tab + (size_t)iter * n;
-  double* y_out = a.y_tab + 3 * (size_t)iter;
-  __syncthreads();
-  TAIL_STAMP(2);
-  {
-    const double* sg = aux + K * D;
-    const double* lm = sg + K;
-    const double* eta = lm + D + K;
-    double sm_s = 1.0, sm_dot = 0.0;
-    if (o_w) {
-      double ps = 0.0, pd = 0.0;
-      for (int k = tid; k < K; k += 256) {
-        const double e = fm::exp2_fast(0x1.71547652b82fep+0 * eta[k]);
-        ee[k] = e;
-        ps += e;
-        pd += e * (k == tid ? rw : raw(f_w + k));
-      }
-      ps = wave_sum(ps);
-      pd = wave_sum(pd);
-      if ((tid & 63) == 0) {
-        red[tid >> 6] = ps;
-        red[4 + (tid >> 6)] = pd;
-      }
-      __syncthreads();
-      sm_s = (red[0] + red[1]) + (red[2] + red[3]);
-      sm_dot = (red[4] + red[5]) + (red[6] + red[7]);
-    }
-    if (writer && tid == 0) {
-      const double G = a.pre[n], loss = a.pre[n + 1], H = raw(0);
-      y_out[0] = -G - H + loss;
-      y_out[1] = G;
-      y_out[2] = H;
-    }
-    for (int base = 0; base < n; base += 256 * U) {
-      if (base > 0) load_chunk(base);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int i = base + u * 256 + tid;
-        if (i >= n) continue;
-        double g;
-        if (o_mu && i < D * K) {
-          g = r_pre[u] - r_raw[u];
-        } else if (o_sg && i >= p_sg && i < p_sg + K) {
-          g = r_pre[u] - r_raw[u] * sg[i - p_sg];
-        } else if (o_lm && i >= p_lm && i < p_lm + D) {
-          g = r_pre[u] - r_raw[u] * lm[i - p_lm];
-        } else {
-          const double e = ee[i - p_w];
-          g = r_pre[u] + (e * sm_dot / (sm_s * sm_s) - e * r_raw[u] / sm_s);
-        }
-        const double m = a.beta1 * r_m[u] + (1.0 - a.beta1) * g;
-        const double v = a.beta2 * r_v[u] + (1.0 - a.beta2) * (g * g);
+  adam_step_body(
+      a, a.iter_base[0] + a.it_off, theta, aux, ee, red, writer,
+      [&](int i) { return __hip_atomic_load(raw_p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); },
+      [&](int i, double m, double v) {
         if (writer) {
           new_m[i] = m;
           new_v[i] = v;
         }
-        const double m_hat = m * c1, v_hat = v * c2;
-        double x = theta[i] - step * m_hat / (sqrt(v_hat) + a.fudge);
-        if (a.has_box) x = fmin(r_hi[u], fmax(r_lo[u], x));
-        theta[i] = x;
-        if (writer) x_row[i] = x;
-      }
-    }
-    __syncthreads();
-  }
+      },
+      [&] { TAIL_STAMP(2); });
   // this block is through with the old moments (every load above has been consumed)
   if (tid == 0) __hip_atomic_fetch_add(t.rd_cnt, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   TAIL_STAMP(3);
@@ -389,23 +186,7 @@ __global__ __launch_bounds__(256) void adam_tail_kernel(AdamDev a, TailArgs t) {
   TAIL_STAMP(5);
   // ---- the writer: the new iterate goes to memory, the moments once every block has read the old ones ----
   for (int i = tid; i < a.ml.total; i += 256) a.mix[i] = pack[i];  // (read by the reduction blocks only: they are done)
-  if (tid == 0) {
-    const unsigned long long t0 = wall_clock64();
-    int ok = 1;
-    while (__hip_atomic_load(t.rd_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < t.rd_target) {
-      if (wall_clock64() - t0 > t.timeout) {
-        ok = 0;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    s_ok = ok;
-  }
-  __syncthreads();
-  if (!s_ok) {
-    if (tid == 0) atomicOr(a.status, 8);
-    return;
-  }
+  if (!bounded_wait<2>(a, t.rd_cnt, t.timeout, &s_ok, [&](unsigned long long c) { return c >= t.rd_target; })) return;
   TAIL_STAMP(6);
   for (int i = tid; i < L.o_hyp(); i += 256) a.state[i] = sh[i];  // theta | aux
   for (int i = tid; i < n; i += 256) {
@@ -591,9 +372,8 @@ extern "C" int vbmc_adam_begin(vbmc_ctx* ctx, const double* theta0, int n_theta,
   if (ctx->spec.armed) spec_disarm(ctx);  // launches waiting for a theta would hold CUs the loop's workgroups need
   const int D = ctx->D, K = ctx->K, S = ctx->gp.S;
   const int mask = opts->optimize_mask;
-  const int need = ((mask & 1) ? D * K : 0) + ((mask & 2) ? K : 0) + ((mask & 4) ? D : 0) +
-                   ((mask & 8) ? K : 0);
-  if (n_theta != need || n_theta < 1)
+  const ThetaMap tm(D, K, mask);
+  if (n_theta != tm.n_theta() || n_theta < 1)
     return vbmc_fail(ctx, VBMC_E_ARG, "adam_begin: theta length %d does not match D=%d K=%d mask=%d",
                      n_theta, D, K, mask);
   for (int i = 0; i < n_theta; ++i)
@@ -603,11 +383,8 @@ extern "C" int vbmc_adam_begin(vbmc_ctx* ctx, const double* theta0, int n_theta,
   ctx->pack_valid = false;  // the loop rewrites d_mix on the device; vbmc_adam_end re-syncs the host copies
   st->has_bnd = opts->bnd_lb && opts->bnd_ub;
   st->n_bnd = st->has_bnd ? opts->n_bnd : 0;
-  if (st->has_bnd) {
-    const int want = ((mask & 1) ? D * K : 0) + ((mask & 6) ? D * K : 0) + ((mask & 8) ? K : 0);
-    if (st->n_bnd != want)
-      return vbmc_fail(ctx, VBMC_E_ARG, "adam_begin: bounds length %d != %d", st->n_bnd, want);
-  }
+  if (st->has_bnd && st->n_bnd != tm.n_bnd())
+    return vbmc_fail(ctx, VBMC_E_ARG, "adam_begin: bounds length %d != %d", st->n_bnd, tm.n_bnd());
   st->has_box = lb != nullptr;
   st->n_theta = n_theta;
   st->max_iter = max_iter;
@@ -623,18 +400,8 @@ extern "C" int vbmc_adam_begin(vbmc_ctx* ctx, const double* theta0, int n_theta,
   st->w_thresh = opts->weight_threshold;
   st->w_pen = opts->weight_penalty;
   const int64_t n_half = st->ns / 2;
-  st->row_begin = opts->row_begin;
-  st->row_count = opts->row_count;
-  if (st->row_count < 0) {
-    st->row_begin = n_half * ctx->rank / ctx->world;
-    st->row_count = n_half * (ctx->rank + 1) / ctx->world - st->row_begin;
-  }
-  if (st->row_begin < 0 || st->row_begin + st->row_count > n_half)
-    return vbmc_fail(ctx, VBMC_E_ARG, "adam_begin: bad row slice");
-  if (st->eps_mode == VBMC_EPS_RESIDENT &&
-      (!ctx->d_eps || ctx->eps_K != K || ctx->eps_D != D || ctx->eps_n_half != n_half ||
-       ctx->eps_row_begin != st->row_begin || ctx->eps_rows != st->row_count))
-    return vbmc_fail(ctx, VBMC_E_ARG, "adam_begin: resident eps does not match the request");
+  int rc = resolve_row_slice(ctx, opts, "adam_begin", &st->row_begin, &st->row_count);
+  if (rc) return rc;
 
   // one allocation, carved: the state block, scratch, x_tab, y_tab
   AdamLayout& L = st->lay;
@@ -665,7 +432,7 @@ extern "C" int vbmc_adam_begin(vbmc_ctx* ctx, const double* theta0, int n_theta,
   }
   const size_t total = (size_t)L.end() + n_work + (size_t)K + (size_t)n_theta + 2 +
                        (size_t)max_iter * n_theta + 3 * (size_t)max_iter + 64;
-  int rc = ensure_dev(ctx, &st->d_buf, &st->d_cap, total);
+  rc = ensure_dev(ctx, &st->d_buf, &st->d_cap, total);
   if (rc) return rc;
   if (!st->d_status) HIP_TRY(ctx, hipMalloc((void**)&st->d_status, 4 * sizeof(int)));  // flag, iteration base
   if (!st->d_args) HIP_TRY(ctx, hipMalloc((void**)&st->d_args, sizeof(AdamDev)));
@@ -683,11 +450,7 @@ extern "C" int vbmc_adam_begin(vbmc_ctx* ctx, const double* theta0, int n_theta,
   HIP_TRY(ctx, hipMemsetAsync(st->d_status, 0, 4 * sizeof(int), sm));
   // attributes of the blocks theta does not carry start from the ctx mixture
   std::vector<double> aux(L.n_aux);
-  memcpy(aux.data(), ctx->mu.data(), sizeof(double) * K * D);
-  memcpy(aux.data() + K * D, ctx->sigma.data(), sizeof(double) * K);
-  memcpy(aux.data() + K * D + K, ctx->lambd.data(), sizeof(double) * D);
-  memcpy(aux.data() + K * D + K + D, ctx->w.data(), sizeof(double) * K);
-  memcpy(aux.data() + K * D + 2 * K + D, ctx->eta.data(), sizeof(double) * K);
+  ctx_pack_aux(ctx, aux.data());
   HIP_TRY(ctx, hipMemcpyAsync(sb + L.o_aux(), aux.data(), sizeof(double) * L.n_aux, hipMemcpyHostToDevice, sm));
   HIP_TRY(ctx, hipMemcpyAsync(sb + L.o_hyp(), ctx->gp.d_hyp, sizeof(double) * L.n_hyp, hipMemcpyDeviceToDevice, sm));
   if (st->has_bnd) {
@@ -782,28 +545,189 @@ extern "C" int vbmc_adam_begin(vbmc_ctx* ctx, const double* theta0, int n_theta,
   return VBMC_OK;
 }
 
-// One batch of iterations [i0, i0 + n_iters): four launches per iteration on one stream,
-//   prep (table rows + GP sums) -> entropy (+ the pre row) -> finish [-> all-reduce] -> step,
-// ordered by the stream alone.
-static int enqueue_batch(vbmc_ctx* ctx, AdamState* st, int i0, int n_iters, bool multi) {
-  hipStream_t sm = ctx->stream;
-  AdamDev a;
-  fill_dev(ctx, *st, a);
-  const bool use_gen = st->pregen;
+// What the iterations of one batch share: the draws' slices and whether the two-launch form is tried.
+struct BatchSetup {
+  vbmc_ctx* ctx;
+  AdamState* st;
+  bool use_gen, multi, try_tail;
+  int tail_gp_per_slot;
   // shares of the next iteration's draws given to the finish / step / prep launches, about
   // proportional to how long each of them leaves the GPU idle (5.5 / 12 / 8.5 us)
   // (a sweep of the split moved the iteration time by < 1 %)
-  const double f_fin = 0.20, f_step = 0.67;
-  auto slice = [&](int seed_off, double f0, double f1) {
+  static constexpr double f_fin = 0.20, f_step = 0.67;
+  GenSlice slice(int seed_off, double f0, double f1) const {
     return make_gen_slice(st->d_eps1, ctx->K, ctx->D, st->row_count, st->ns / 2, st->row_begin,
                           st->seed + (uint64_t)seed_off, st->d_status + 1, f0, f1);
-  };
+  }
+};
+
+// the pre workgroup's LDS (doubles) as an extra row of the plan's entropy launch: its working set when the launch's
+// entropy workgroups still fit beside it (pre_lds_limit), else 0 (it works from global memory)
+static int pre_extra_lds(const vbmc_ctx* ctx, const AdamState* st, const EntPlan& plan) {
+  return (st->pre_lds && st->pre_lds_bytes <= pre_lds_limit(ctx, plan)) ? (int)(st->pre_lds_bytes / sizeof(double)) : 0;
+}
+
+// VBMC_TAIL_TIMES=1 (measurement aid): the writer block's stamps of the batch's last iteration to stderr
+static int print_tail_times(vbmc_ctx* ctx, const unsigned long long* d_tt) {
+  unsigned long long tt[8];
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(tt, d_tt, sizeof(tt), hipMemcpyDeviceToHost));
+  fprintf(stderr, "tail launch, writer block, us: (%.0f) start -> word %.2f | loads %.2f | update %.2f | pack %.2f | table row %.2f | pack out + readers %.2f | write-back %.2f | total %.2f\n",
+          0.0, (tt[1] - tt[0]) * 0.01, (tt[2] - tt[1]) * 0.01, (tt[3] - tt[2]) * 0.01, (tt[4] - tt[3]) * 0.01, (tt[5] - tt[4]) * 0.01,
+          (tt[6] - tt[5]) * 0.01, (tt[7] - tt[6]) * 0.01, (tt[7] - tt[0]) * 0.01);
+  return 0;
+}
+
+// Iteration `it` of a batch as two launches (adam_tail_kernel): the wave-split kernel in span mode with the GP sums and the
+// pre workgroup in its free slots, then everything up to the next table in one launch.  *took: whether this form
+// applied (the plan is a span-mode one whose slots hold the GP sums); if not, nothing was launched.
+static int enqueue_two_launch(const BatchSetup& b, AdamDev& a, EntPlan& plan, const PrepArgs& pa, int it, bool last, bool* took) {
+  vbmc_ctx* ctx = b.ctx;
+  AdamState* st = b.st;
+  hipStream_t sm = ctx->stream;
+  const bool use_gen = b.use_gen;
+  *took = false;
+  PrepArgs gp = pa;
+  gp.n_table = 0;
+  gp.gen = GenSlice();
+  gp.mix = ctx->d_mix;
+  gp.done = DoneSignal();
+  gp.done.cnt = (int*)(st->d_sync + 8);
+  gp.done.flag = (uint64_t*)st->d_sync;
+  gp.done.seq = st->sync_seq + 1;
+  gp.done.dev = 1;
+  if (!(b.try_tail && plan.kernel == EntKernel::WsSpan && (use_gen || st->eps_mode == VBMC_EPS_RESIDENT) &&
+        entmc_take_gp(ctx, plan, gp)))
+    return 0;
+  *took = true;
+  int rc;
+  if (use_gen) {
+    plan.a.eps = st->d_eps1;
+    plan.a.eps_rows = st->row_count;
+  }
+  plan.table = st->d_table;
+  if (!st->table_valid || (use_gen && st->eps_have < 1.0)) {
+    // first iteration of a run (or after an iteration in another form): the table of the current iterate and the
+    // part of its draws that is not there yet -- everything at the start of a run, [f_step, 1) behind a four-launch
+    // iteration (whose finish and step launches made [0, f_step): ADVICE r05) --, by a prep launch of their own
+    PrepArgs pt;
+    entmc_fill_prep(ctx, plan, pt);
+    if (st->table_valid) pt.n_table = 0;
+    if (use_gen && st->eps_have < 1.0) pt.gen = b.slice(it, st->eps_have, 1.0);
+    rc = launch_prep(ctx, pt);
+    if (rc) return rc;
+  }
+  const unsigned long long seq = ++st->sync_seq;
+  plan.a.extra = st->d_args;
+  plan.a.extra_lds = pre_extra_lds(ctx, st, plan);
+  rc = entmc_launch_main(ctx, plan);
+  if (rc) return rc;
+  TailArgs t;
+  t.partial = plan.a.partial;
+  t.chunks = plan.a.chunks;
+  t.stride = plan.a.stride;
+  t.mu_from_w = 1;
+  t.inv_ns = plan.inv_ns;
+  t.red.cnt = (int*)(st->d_sync + 8) + 2;
+  t.red.flag = (uint64_t*)(st->d_sync + 1);
+  t.red.seq = seq;
+  t.red.dev = 1;
+  t.DP = plan.DP;
+  t.K4 = ws_table_rows(ctx->K);
+  t.table = st->d_table;
+  t.rd_cnt = st->d_sync + 2;
+  t.rd_target = (unsigned long long)ctx->K * (++st->tail_launches);
+  static const int gen_mode = [] {
+    const char* e = getenv("VBMC_TAIL_GEN");  // measurement aid: 0 = no draws (timing only: wrong values), 2 = a launch of their own behind the tail launch
+    return e ? atoi(e) : 1;
+  }();
+  if (use_gen && gen_mode == 1) t.gen = b.slice(it + 1, 0.0, 1.0);
+  a.it_off = it;
+  static const bool want_times = [] {
+    const char* e = getenv("VBMC_TAIL_TIMES");
+    return e && e[0] == '1';
+  }();
+  static unsigned long long* d_tt = nullptr;
+  if (want_times) {
+    if (!d_tt) HIP_TRY(ctx, hipMalloc((void**)&d_tt, 16 * sizeof(unsigned long long)));
+    t.times = d_tt;
+  }
+  const int n_main = (raw_len(ctx->D, ctx->K) + 3) / 4;
+  hipLaunchKernelGGL(adam_tail_kernel, dim3(n_main + ctx->K + t.gen.n_blocks), dim3(256), st->tail_lds_bytes, sm, a, t);
+  if (use_gen && gen_mode == 2) {
+    rc = launch_eps_gen(ctx, sm, b.slice(it + 1, 0.0, 1.0));
+    if (rc) return rc;
+  }
+  if (want_times && last) {
+    rc = print_tail_times(ctx, d_tt);
+    if (rc) return rc;
+  }
+  st->table_valid = true;
+  st->eps_have = (use_gen && gen_mode != 0) ? 1.0 : 0.0;
+  st->last_form = 2;
+  ctx->last_plan[0] = (int)EntKernel::AdamTail;  // (vbmc_last_entmc_plan)
+  return 0;
+}
+
+// Iteration `it` of a batch as four launches on one stream,
+//   prep (table rows + GP sums) -> entropy (+ the pre row) -> finish [-> all-reduce] -> step,
+// ordered by the stream alone.
+static int enqueue_four_launch(const BatchSetup& b, AdamDev& a, EntPlan& plan, PrepArgs& pa, int it) {
+  vbmc_ctx* ctx = b.ctx;
+  AdamState* st = b.st;
+  hipStream_t sm = ctx->stream;
+  const bool use_gen = b.use_gen;
+  st->table_valid = false;
+  st->last_form = 4;
+  if (use_gen) {
+    plan.a.eps = st->d_eps1;
+    plan.a.eps_rows = st->row_count;
+    // this iteration's remaining draws (all of them when no earlier launch began the buffer, none behind a two-launch
+    // iteration, whose tail launch made them all)
+    if (st->eps_have < 1.0) pa.gen = b.slice(it, st->eps_have, 1.0);
+    st->eps_have = b.f_step;  // (what this iteration's finish and step launches below put in for the next one)
+  }
+  entmc_fill_prep(ctx, plan, pa);
+  int rc = launch_prep(ctx, pa);
+  if (rc) return rc;
+  // the entropy-free part of dF: an extra row of the entropy launch when that kernel has one
+  // (wave-split, draws from memory), otherwise a launch of its own in front of it
+  const bool pre_row = plan.tabled() && plan.a.eps_mode != VBMC_EPS_PHILOX;
+  if (pre_row) {
+    plan.a.extra = st->d_args;
+    plan.a.extra_lds = pre_extra_lds(ctx, st, plan);
+  } else {
+    launch_pre(*st, sm, a);
+  }
+  rc = entmc_launch_main(ctx, plan);
+  if (rc) return rc;
+  const GenSlice g_fin = use_gen ? b.slice(it + 1, 0.0, b.f_fin) : GenSlice();
+  rc = entmc_launch_finish(ctx, plan, st->state + st->lay.o_raw(), &g_fin);
+  if (rc) return rc;
+  if (b.multi) {
+    rc = comm_allreduce_sum(ctx, st->state + st->lay.o_raw(), raw_len(ctx->D, ctx->K));
+    if (rc) return rc;
+  }
+  a.it_off = it;
+  launch_step(*st, sm, a, 1, use_gen ? b.slice(it + 1, b.f_fin, b.f_step) : GenSlice());
+  return 0;
+}
+
+// One batch of iterations [i0, i0 + n_iters), each as two launches where that form applies, else as four.
+static int enqueue_batch(vbmc_ctx* ctx, AdamState* st, int i0, int n_iters, bool multi) {
+  AdamDev a;
+  fill_dev(ctx, *st, a);
+  BatchSetup b;
+  b.ctx = ctx;
+  b.st = st;
+  b.use_gen = st->pregen;
+  b.multi = multi;
   // The two-launch iteration where it gains (measured, config 3's shape: 20 000 samples per component 97.5 -> 93 us per
   // iteration; 8 192: 61 -> 64; 4 096: 48 -> 52 -- below ~40 us of entropy kernel the GP sums and the pre workgroup in its
   // launch outlast the entropy parts, and the hand-off inside the tail launch costs what the two boundaries it replaces
   // cost): jobs of at least 250 000 antithetic rows.  Option "adam_tail" = 2 forces it wherever its shape applies (tests).
-  const bool try_tail = ctx->opt_adam_tail && !multi && st->tail_ok &&
-                        (ctx->opt_adam_tail == 2 || (int64_t)ctx->K * st->row_count >= 250000);
+  b.try_tail = ctx->opt_adam_tail && !multi && st->tail_ok &&
+               (ctx->opt_adam_tail == 2 || (int64_t)ctx->K * st->row_count >= 250000);
   // GP items per workgroup of the entropy launch: four where the entropy parts run long enough (>= ~60 us) to cover four
   // items (28 us) and the pre workgroup behind them (10 us from LDS) -- 2 / 3 / 4 / 5 items: 91.6 / 91.2 / 90.4 / 96.0 us per
   // iteration at config 3 --, one below that
@@ -811,135 +735,120 @@ static int enqueue_batch(vbmc_ctx* ctx, AdamState* st, int i0, int n_iters, bool
     const char* e = getenv("VBMC_TAIL_GP_PER_SLOT");  // measurement aid
     return e ? atoi(e) : 0;
   }();
-  const int tail_gp_per_slot = gp_per_slot_env > 0 ? gp_per_slot_env : ((int64_t)ctx->K * st->row_count >= 250000 ? 4 : 1);
+  b.tail_gp_per_slot = gp_per_slot_env > 0 ? gp_per_slot_env : ((int64_t)ctx->K * st->row_count >= 250000 ? 4 : 1);
   for (int it = 0; it < n_iters; ++it) {
     PrepArgs pa;
     glj_fill_prep(ctx, 1, st->state + st->lay.o_res(), nullptr, pa);
     EntPlan plan;
-    int rc = entmc_plan(ctx, st->ns, use_gen ? VBMC_EPS_RESIDENT : st->eps_mode, st->seed + (uint64_t)(i0 + it),
-                        st->row_begin, st->row_count, 1, plan, try_tail ? pa.n_glj : 0, try_tail ? tail_gp_per_slot : 0);
+    int rc = entmc_plan(ctx, st->ns, b.use_gen ? VBMC_EPS_RESIDENT : st->eps_mode, st->seed + (uint64_t)(i0 + it),
+                        st->row_begin, st->row_count, 1, plan, b.try_tail ? pa.n_glj : 0, b.try_tail ? b.tail_gp_per_slot : 0);
     if (rc) return rc;
-    // ---- two launches per iteration (adam_tail_kernel): the wave-split kernel in span mode with the GP sums and the
-    // pre workgroup in its free slots, then everything up to the next table in one launch ----
-    PrepArgs gp = pa;
-    gp.n_table = 0;
-    gp.gen = GenSlice();
-    gp.mix = ctx->d_mix;
-    gp.done = DoneSignal();
-    gp.done.cnt = (int*)(st->d_sync + 8);
-    gp.done.flag = (uint64_t*)st->d_sync;
-    gp.done.seq = st->sync_seq + 1;
-    gp.done.dev = 1;
-    if (try_tail && plan.kernel == EntKernel::WsSpan && (use_gen || st->eps_mode == VBMC_EPS_RESIDENT) &&
-        entmc_take_gp(ctx, plan, gp)) {
-      if (use_gen) {
-        plan.a.eps = st->d_eps1;
-        plan.a.eps_rows = st->row_count;
-      }
-      plan.table = st->d_table;
-      if (!st->table_valid || (use_gen && st->eps_have < 1.0)) {
-        // first iteration of a run (or after an iteration in another form): the table of the current iterate and the
-        // part of its draws that is not there yet -- everything at the start of a run, [f_step, 1) behind a four-launch
-        // iteration (whose finish and step launches made [0, f_step): ADVICE r05) --, by a prep launch of their own
-        PrepArgs pt;
-        entmc_fill_prep(ctx, plan, pt);
-        if (st->table_valid) pt.n_table = 0;
-        if (use_gen && st->eps_have < 1.0) pt.gen = slice(it, st->eps_have, 1.0);
-        rc = launch_prep(ctx, pt);
-        if (rc) return rc;
-      }
-      const unsigned long long seq = ++st->sync_seq;
-      plan.a.extra = st->d_args;
-      plan.a.extra_lds = (st->pre_lds && st->pre_lds_bytes <= pre_lds_limit(ctx, plan)) ? (int)(st->pre_lds_bytes / sizeof(double)) : 0;
-      rc = entmc_launch_main(ctx, plan);
-      if (rc) return rc;
-      TailArgs t;
-      t.partial = plan.a.partial;
-      t.chunks = plan.a.chunks;
-      t.stride = plan.a.stride;
-      t.mu_from_w = 1;
-      t.inv_ns = plan.inv_ns;
-      t.red.cnt = (int*)(st->d_sync + 8) + 2;
-      t.red.flag = (uint64_t*)(st->d_sync + 1);
-      t.red.seq = seq;
-      t.red.dev = 1;
-      t.DP = plan.DP;
-      t.K4 = ws_table_rows(ctx->K);
-      t.table = st->d_table;
-      t.rd_cnt = st->d_sync + 2;
-      t.rd_target = (unsigned long long)ctx->K * (++st->tail_launches);
-      static const int gen_mode = [] {
-        const char* e = getenv("VBMC_TAIL_GEN");  // measurement aid: 0 = no draws (timing only: wrong values), 2 = a launch of their own behind the tail launch
-        return e ? atoi(e) : 1;
-      }();
-      if (use_gen && gen_mode == 1) t.gen = slice(it + 1, 0.0, 1.0);
-      a.it_off = it;
-      static const bool want_times = [] {
-        const char* e = getenv("VBMC_TAIL_TIMES");  // measurement aid: the writer block's stamps of the batch's last iteration to stderr
-        return e && e[0] == '1';
-      }();
-      static unsigned long long* d_tt = nullptr;
-      if (want_times) {
-        if (!d_tt) HIP_TRY(ctx, hipMalloc((void**)&d_tt, 16 * sizeof(unsigned long long)));
-        t.times = d_tt;
-      }
-      const int n_main = (raw_len(ctx->D, ctx->K) + 3) / 4;
-      hipLaunchKernelGGL(adam_tail_kernel, dim3(n_main + ctx->K + t.gen.n_blocks), dim3(256), st->tail_lds_bytes, sm, a, t);
-      if (use_gen && gen_mode == 2) {
-        rc = launch_eps_gen(ctx, sm, slice(it + 1, 0.0, 1.0));
-        if (rc) return rc;
-      }
-      if (want_times && it == n_iters - 1) {
-        unsigned long long tt[8];
-        HIP_TRY(ctx, hipStreamSynchronize(sm));
-        HIP_TRY(ctx, hipMemcpy(tt, d_tt, sizeof(tt), hipMemcpyDeviceToHost));
-        fprintf(stderr, "tail launch, writer block, us: (%.0f) start -> word %.2f | loads %.2f | update %.2f | pack %.2f | table row %.2f | pack out + readers %.2f | write-back %.2f | total %.2f\n",
-                0.0, (tt[1] - tt[0]) * 0.01, (tt[2] - tt[1]) * 0.01, (tt[3] - tt[2]) * 0.01, (tt[4] - tt[3]) * 0.01, (tt[5] - tt[4]) * 0.01,
-                (tt[6] - tt[5]) * 0.01, (tt[7] - tt[6]) * 0.01, (tt[7] - tt[0]) * 0.01);
-      }
-      st->table_valid = true;
-      st->eps_have = (use_gen && gen_mode != 0) ? 1.0 : 0.0;
-      st->last_form = 2;
-      ctx->last_plan[0] = (int)EntKernel::AdamTail;  // (vbmc_last_entmc_plan)
-      continue;
-    }
-    st->table_valid = false;
-    st->last_form = 4;
-    if (use_gen) {
-      plan.a.eps = st->d_eps1;
-      plan.a.eps_rows = st->row_count;
-      // this iteration's remaining draws (all of them when no earlier launch began the buffer, none behind a two-launch
-      // iteration, whose tail launch made them all)
-      if (st->eps_have < 1.0) pa.gen = slice(it, st->eps_have, 1.0);
-      st->eps_have = f_step;  // (what this iteration's finish and step launches below put in for the next one)
-    }
-    entmc_fill_prep(ctx, plan, pa);
-    rc = launch_prep(ctx, pa);
+    bool took = false;
+    rc = enqueue_two_launch(b, a, plan, pa, it, it == n_iters - 1, &took);
+    if (!rc && !took) rc = enqueue_four_launch(b, a, plan, pa, it);
     if (rc) return rc;
-    // the entropy-free part of dF: an extra row of the entropy launch when that kernel has one
-    // (wave-split, draws from memory), otherwise a launch of its own in front of it
-    const bool pre_row = plan.tabled() && plan.a.eps_mode != VBMC_EPS_PHILOX;
-    if (pre_row) {
-      plan.a.extra = st->d_args;
-      // its working set in LDS when the launch's entropy workgroups still fit beside it (pre_lds_limit)
-      plan.a.extra_lds = (st->pre_lds && st->pre_lds_bytes <= pre_lds_limit(ctx, plan)) ? (int)(st->pre_lds_bytes / sizeof(double)) : 0;
-    } else {
-      launch_pre(*st, sm, a);
-    }
-    rc = entmc_launch_main(ctx, plan);
-    if (rc) return rc;
-    const GenSlice g_fin = use_gen ? slice(it + 1, 0.0, f_fin) : GenSlice();
-    rc = entmc_launch_finish(ctx, plan, st->state + st->lay.o_raw(), &g_fin);
-    if (rc) return rc;
-    if (multi) {
-      rc = comm_allreduce_sum(ctx, st->state + st->lay.o_raw(), raw_len(ctx->D, ctx->K));
-      if (rc) return rc;
-    }
-    a.it_off = it;
-    launch_step(*st, sm, a, 1, use_gen ? slice(it + 1, f_fin, f_step) : GenSlice());
   }
   HIP_TRY(ctx, hipGetLastError());
   return 0;
+}
+
+// VBMC_FUSED_TIMES=1 (measurement aid): the phase stamps of two workgroups of a fused launch to stderr
+static int print_fused_times(vbmc_ctx* ctx, unsigned long long* d_times, int n_iters) {
+  std::vector<unsigned long long> tt(2 * 64 * 16);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(tt.data(), d_times, sizeof(unsigned long long) * tt.size(), hipMemcpyDeviceToHost));
+  const int nt = n_iters < 64 ? n_iters : 64;
+  for (int w = 0; w < 2; ++w) {
+    double acc[9] = {}, sub[4] = {};
+    int cnt = 0;
+    for (int t = 2; t + 1 < nt; ++t, ++cnt) {
+      const unsigned long long* r = &tt[((size_t)w * 64 + t) * 16];
+      for (int p = 0; p < 8; ++p) acc[p] += (double)(r[p + 1] - r[p]) * 0.01;
+      acc[8] += (double)(tt[((size_t)w * 64 + t + 1) * 16] - r[0]) * 0.01;
+      if (w == 0) { sub[0] += (double)(r[9] - r[0]) * 0.01; sub[1] += (double)(r[10] - r[9]) * 0.01; sub[2] += (double)(r[11] - r[10]) * 0.01; sub[3] += (double)(r[1] - r[11]) * 0.01; }
+    }
+    if (cnt > 0)
+      fprintf(stderr, "fused loop, %s workgroup, us: phase A %.2f | drain %.2f | wait %.2f | gather %.2f | raw %.2f | pre %.2f | step %.2f | pack %.2f | iteration %.2f\n",
+              w == 0 ? "entropy" : "GP-sum", acc[0] / cnt, acc[1] / cnt, acc[2] / cnt, acc[3] / cnt, acc[4] / cnt, acc[5] / cnt,
+              acc[6] / cnt, acc[7] / cnt, acc[8] / cnt);
+    if (cnt > 0 && w == 0)
+      fprintf(stderr, "   phase A of the entropy workgroup: draws + table row %.2f | row loop %.2f | wave sums %.2f | record %.2f\n",
+              sub[0] / cnt, sub[1] / cnt, sub[2] / cnt, sub[3] / cnt);
+  }
+  return 0;
+}
+
+// The one-launch form of iterations [i0, i0 + n), queued.  stop_rule: every workgroup applies minimize_adam's stopping rule
+// itself (tol_fun) and workgroup 0 leaves the number of iterations run in status word 2.
+static int run_fused(vbmc_ctx* ctx, AdamState* st, int i0, int n, int stop_rule, double tol_fun) {
+  FusedArgs f = st->fz;
+  f.i0 = i0;
+  f.n_iters = n;
+  f.stop_rule = stop_rule;
+  f.tol_fun = tol_fun;
+  if (stop_rule) f.n_done = st->d_status + 2;
+  f.test_absent = ctx->opt_adam_fused == 2 ? 1 : 0;
+  f.rel_acq = ctx->opt_adam_fused == 3 ? 1 : 0;
+  HIP_TRY(ctx, hipMemsetAsync(st->d_flags, 0, 512 * sizeof(unsigned long long), ctx->stream));
+  static const bool want_times = [] {
+    const char* e = getenv("VBMC_FUSED_TIMES");
+    return e && e[0] == '1';
+  }();
+  unsigned long long* d_times = nullptr;
+  if (want_times && !stop_rule) {
+    HIP_TRY(ctx, hipMalloc((void**)&d_times, sizeof(unsigned long long) * 2 * 64 * 16));
+    HIP_TRY(ctx, hipMemsetAsync(d_times, 0, sizeof(unsigned long long) * 2 * 64 * 16, ctx->stream));
+    f.times = d_times;
+  }
+  int rc = adam_fused_launch(ctx, ctx->stream, f, st->fused_lds);
+  ctx->last_plan[0] = (int)EntKernel::AdamFused;  // (vbmc_last_entmc_plan)
+  // (the iterate moves without the other forms' side buffers following it: their table and any draws made ahead are stale)
+  st->table_valid = false;
+  st->eps_have = 0.0;
+  if (d_times && !rc) rc = print_fused_times(ctx, d_times, n);
+  if (d_times) (void)hipFree(d_times);
+  return rc;
+}
+
+// Behind a one-launch batch whose status word has come back: did it give up waiting (bit 4)?  Then the state it started
+// from is put back (fused_restore), the status reset and the one-launch form switched off for the rest of the optimisation;
+// the caller redoes the iterations in another form.
+static int fused_gave_up(vbmc_ctx* ctx, AdamState* st, int status, bool* gave_up) {
+  *gave_up = st->fused && (status & 4);
+  if (!*gave_up) return 0;
+  st->fused = false;
+  st->fused_gave_up++;
+  int rc = fused_restore(ctx, st);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(st->d_status, 0, sizeof(int), ctx->stream));
+  return 0;
+}
+
+// rows [i0, i0 + n) of y_tab (y, G, H) and x_tab to the caller's arrays (any of them may be null); waits for the stream
+static int copy_out_rows(vbmc_ctx* ctx, const AdamState* st, int i0, int n, double* y_out, double* x_out, double* G_out, double* H_out) {
+  const int nt = st->n_theta;
+  std::vector<double> y3(3 * (size_t)n);
+  if (n > 0) {
+    HIP_TRY(ctx, hipMemcpyAsync(y3.data(), st->y_tab + 3 * (size_t)i0, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (x_out)
+      HIP_TRY(ctx, hipMemcpyAsync(x_out, st->x_tab + (size_t)i0 * nt, sizeof(double) * (size_t)n * nt, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIP_TRY(ctx, stream_wait(ctx));
+  for (int it = 0; it < n; ++it) {
+    if (y_out) y_out[it] = y3[3 * (size_t)it];
+    if (G_out) G_out[it] = y3[3 * (size_t)it + 1];
+    if (H_out) H_out[it] = y3[3 * (size_t)it + 2];
+  }
+  return 0;
+}
+
+// the loop's status word as an error (the optimisation is then over), or VBMC_OK
+static int decode_status(vbmc_ctx* ctx, AdamState* st, const char* who, int status) {
+  if (!status) return VBMC_OK;
+  st->active = false;
+  if (status & 4) return vbmc_fail(ctx, VBMC_E_HIP, "%s: a workgroup of the fused loop did not publish within 20 ms", who);
+  if (status & 8) return vbmc_fail(ctx, VBMC_E_HIP, "%s: a hand-off inside the two-launch iteration did not arrive within 20 ms", who);
+  return vbmc_fail(ctx, VBMC_E_NONFINITE, "%s: an iterate became non-finite", who);
 }
 
 extern "C" int vbmc_adam_run(vbmc_ctx* ctx, int n_iters, double* y_tab_out, double* x_tab_out,
@@ -952,12 +861,7 @@ extern "C" int vbmc_adam_run(vbmc_ctx* ctx, int n_iters, double* y_tab_out, doub
     return vbmc_fail(ctx, VBMC_E_ARG, "adam_run: %d + %d iterations exceed max_iter %d", st->iter,
                      n_iters, st->max_iter);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int n = st->n_theta;
-  static const bool force_coll = [] {
-    const char* e = getenv("VBMC_FORCE_COLLECTIVE");
-    return e && e[0] == '1';
-  }();
-  const bool multi = ctx->comm != nullptr && (ctx->world > 1 || force_coll);
+  const bool multi = ctx_is_multi(ctx);
   struct TimingOff {  // no per-kernel event pairs inside the loop; restored on every exit path
     vbmc_ctx* c;
     bool was;
@@ -965,100 +869,29 @@ extern "C" int vbmc_adam_run(vbmc_ctx* ctx, int n_iters, double* y_tab_out, doub
     ~TimingOff() { c->timing = was; }
   } timing_off(ctx);
   const int i0 = st->iter;
-  int rc = 0;
   int status = 0;
-  std::vector<double> y3(3 * (size_t)n_iters);
-  // (second pass only when the one-launch form gave up waiting: the state in memory is then still that of the start of
-  // the batch -- workgroup 0 writes it back at the very end -- so the batch is simply run again as four launches per
-  // iteration, and the rest of the optimisation too)
-  for (int attempt = 0; attempt < 2; ++attempt) {
-  if (st->fused && !multi && n_iters > 0) {
-    FusedArgs f = st->fz;
-    f.i0 = i0;
-    f.n_iters = n_iters;
-    f.test_absent = ctx->opt_adam_fused == 2 ? 1 : 0;
-    f.rel_acq = ctx->opt_adam_fused == 3 ? 1 : 0;
-    HIP_TRY(ctx, hipMemsetAsync(st->d_flags, 0, 512 * sizeof(unsigned long long), ctx->stream));
-    static const bool want_times = [] {
-      const char* e = getenv("VBMC_FUSED_TIMES");  // measurement aid: phase stamps of two workgroups to stderr
-      return e && e[0] == '1';
-    }();
-    unsigned long long* d_times = nullptr;
-    if (want_times) {
-      HIP_TRY(ctx, hipMalloc((void**)&d_times, sizeof(unsigned long long) * 2 * 64 * 16));
-      HIP_TRY(ctx, hipMemsetAsync(d_times, 0, sizeof(unsigned long long) * 2 * 64 * 16, ctx->stream));
-      f.times = d_times;
+  // (second pass only when the one-launch form gave up waiting: the state in memory is then that of the start of the batch
+  // again, so the batch is simply run again as four launches per iteration, and the rest of the optimisation too)
+  for (int pass = 0; pass < 2; ++pass) {
+    int rc;
+    if (st->fused && !multi && n_iters > 0) {
+      rc = run_fused(ctx, st, i0, n_iters, 0, 0.0);
+    } else {
+      hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(1), 0, ctx->stream, st->d_status + 1, i0);
+      rc = enqueue_batch(ctx, st, i0, n_iters, multi);
     }
-    rc = adam_fused_launch(ctx, ctx->stream, f, st->fused_lds);
-    ctx->last_plan[0] = (int)EntKernel::AdamFused;  // (vbmc_last_entmc_plan)
-    // (the iterate moves without the other forms' side buffers following it: their table and any draws made ahead are stale)
-    st->table_valid = false;
-    st->eps_have = 0.0;
-    if (want_times && !rc) {
-      std::vector<unsigned long long> tt(2 * 64 * 16);
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      HIP_TRY(ctx, hipMemcpy(tt.data(), d_times, sizeof(unsigned long long) * tt.size(), hipMemcpyDeviceToHost));
-      (void)hipFree(d_times);
-      const int nt = n_iters < 64 ? n_iters : 64;
-      for (int w = 0; w < 2; ++w) {
-        double acc[9] = {}, sub[4] = {};
-        int cnt = 0;
-        for (int t = 2; t + 1 < nt; ++t, ++cnt) {
-          const unsigned long long* r = &tt[((size_t)w * 64 + t) * 16];
-          for (int p = 0; p < 8; ++p) acc[p] += (double)(r[p + 1] - r[p]) * 0.01;
-          acc[8] += (double)(tt[((size_t)w * 64 + t + 1) * 16] - r[0]) * 0.01;
-          if (w == 0) { sub[0] += (double)(r[9] - r[0]) * 0.01; sub[1] += (double)(r[10] - r[9]) * 0.01; sub[2] += (double)(r[11] - r[10]) * 0.01; sub[3] += (double)(r[1] - r[11]) * 0.01; }
-        }
-        if (cnt > 0)
-          fprintf(stderr, "fused loop, %s workgroup, us: phase A %.2f | drain %.2f | wait %.2f | gather %.2f | raw %.2f | pre %.2f | step %.2f | pack %.2f | iteration %.2f\n",
-                  w == 0 ? "entropy" : "GP-sum", acc[0] / cnt, acc[1] / cnt, acc[2] / cnt, acc[3] / cnt, acc[4] / cnt, acc[5] / cnt,
-                  acc[6] / cnt, acc[7] / cnt, acc[8] / cnt);
-        if (cnt > 0 && w == 0)
-          fprintf(stderr, "   phase A of the entropy workgroup: draws + table row %.2f | row loop %.2f | wave sums %.2f | record %.2f\n",
-                  sub[0] / cnt, sub[1] / cnt, sub[2] / cnt, sub[3] / cnt);
-      }
-    }
-  } else {
-    hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(1), 0, ctx->stream, st->d_status + 1, i0);
-    rc = enqueue_batch(ctx, st, i0, n_iters, multi);
-  }
-  if (rc) return rc;
-  HIP_TRY(ctx, hipGetLastError());
-  if (n_iters > 0) {
-    HIP_TRY(ctx, hipMemcpyAsync(y3.data(), st->y_tab + 3 * (size_t)i0, sizeof(double) * 3 * n_iters,
-                                hipMemcpyDeviceToHost, ctx->stream));
-    if (x_tab_out)
-      HIP_TRY(ctx, hipMemcpyAsync(x_tab_out, st->x_tab + (size_t)i0 * n, sizeof(double) * (size_t)n_iters * n,
-                                  hipMemcpyDeviceToHost, ctx->stream));
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(&status, st->d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, stream_wait(ctx));
-  if (!(status & 4) || !st->fused) break;
-  st->fused = false;
-  st->fused_gave_up++;
-  rc = fused_restore(ctx, st);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemsetAsync(st->d_status, 0, sizeof(int), ctx->stream));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(&status, st->d_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    rc = copy_out_rows(ctx, st, i0, n_iters, y_tab_out, x_tab_out, G_out, H_out);
+    if (rc) return rc;
+    bool again = false;
+    rc = fused_gave_up(ctx, st, status, &again);
+    if (rc) return rc;
+    if (!again) break;
   }
   st->iter = i0 + n_iters;
-  for (int it = 0; it < n_iters; ++it) {
-    if (y_tab_out) y_tab_out[it] = y3[3 * (size_t)it];
-    if (G_out) G_out[it] = y3[3 * (size_t)it + 1];
-    if (H_out) H_out[it] = y3[3 * (size_t)it + 2];
-  }
-  if (status & 4) {  // (cannot happen: the second pass does not wait for anybody)
-    st->active = false;
-    return vbmc_fail(ctx, VBMC_E_HIP, "adam_run: a workgroup of the fused loop did not publish within 20 ms");
-  }
-  if (status & 8) {
-    st->active = false;
-    return vbmc_fail(ctx, VBMC_E_HIP, "adam_run: a hand-off inside the two-launch iteration did not arrive within 20 ms");
-  }
-  if (status) {
-    st->active = false;
-    return vbmc_fail(ctx, VBMC_E_NONFINITE, "adam_run: an iterate became non-finite");
-  }
-  return VBMC_OK;
+  return decode_status(ctx, st, "adam_run", status);  // (bit 4 cannot be left: the second pass does not wait for anybody)
 }
 
 // The whole optimisation in one call where the one-launch form applies: the workgroups apply the reference's stopping
@@ -1071,58 +904,27 @@ extern "C" int vbmc_adam_run_auto(vbmc_ctx* ctx, int max_iters, double tol_fun, 
   if (!st || !st->active) return vbmc_fail(ctx, VBMC_E_ARG, "adam_run_auto: vbmc_adam_begin not called");
   if (st->iter + max_iters > st->max_iter)
     return vbmc_fail(ctx, VBMC_E_ARG, "adam_run_auto: %d + %d iterations exceed max_iter %d", st->iter, max_iters, st->max_iter);
-  static const bool force_coll = [] {
-    const char* e = getenv("VBMC_FORCE_COLLECTIVE");
-    return e && e[0] == '1';
-  }();
-  const bool multi = ctx->comm != nullptr && (ctx->world > 1 || force_coll);
   // the kernel's stopping rule compares the mean iterate of a batch with the previous batch's, which it accumulates
   // itself from iteration 0 on: a run resumed after vbmc_adam_run iterations has no previous-batch mean to compare with
-  if (!st->fused || multi || max_iters == 0 || st->iter != 0) return VBMC_W_NOT_FUSED;
+  if (!st->fused || ctx_is_multi(ctx) || max_iters == 0 || st->iter != 0) return VBMC_W_NOT_FUSED;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int n = st->n_theta, i0 = st->iter;
-  FusedArgs f = st->fz;
-  f.i0 = i0;
-  f.n_iters = max_iters;
-  f.stop_rule = 1;
-  f.tol_fun = tol_fun;
-  f.n_done = st->d_status + 2;
-  f.test_absent = ctx->opt_adam_fused == 2 ? 1 : 0;
-  f.rel_acq = ctx->opt_adam_fused == 3 ? 1 : 0;
-  HIP_TRY(ctx, hipMemsetAsync(st->d_flags, 0, 512 * sizeof(unsigned long long), ctx->stream));
-  int rc = adam_fused_launch(ctx, ctx->stream, f, st->fused_lds);
-  if (rc) return rc;
-  ctx->last_plan[0] = (int)EntKernel::AdamFused;
+  const int i0 = st->iter;
   int word[3] = {0, 0, 0};
+  bool gave_up = false;
+  int rc = run_fused(ctx, st, i0, max_iters, 1, tol_fun);
+  if (rc) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(word, st->d_status, 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));
-  if (word[0] & 4) {  // gave up waiting: nothing was written back, the caller runs its batches (four launches per iteration)
-    st->fused = false;
-    st->fused_gave_up++;
-    rc = fused_restore(ctx, st);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(st->d_status, 0, sizeof(int), ctx->stream));
-    return VBMC_W_NOT_FUSED;
-  }
+  rc = fused_gave_up(ctx, st, word[0], &gave_up);
+  if (rc) return rc;
+  if (gave_up) return VBMC_W_NOT_FUSED;  // nothing was written back: the caller runs its batches (four launches per iteration)
   const int done = word[2];
   if (done < 1 || done > max_iters) return vbmc_fail(ctx, VBMC_E_HIP, "adam_run_auto: bad iteration count %d", done);
-  std::vector<double> y3(3 * (size_t)done);
-  HIP_TRY(ctx, hipMemcpyAsync(y3.data(), st->y_tab + 3 * (size_t)i0, sizeof(double) * 3 * done, hipMemcpyDeviceToHost, ctx->stream));
-  if (x_tab_out)
-    HIP_TRY(ctx, hipMemcpyAsync(x_tab_out, st->x_tab + (size_t)i0 * n, sizeof(double) * (size_t)done * n, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, stream_wait(ctx));
+  rc = copy_out_rows(ctx, st, i0, done, y_tab_out, x_tab_out, G_out, H_out);
+  if (rc) return rc;
   st->iter = i0 + done;
   *n_done = done;
-  for (int it = 0; it < done; ++it) {
-    if (y_tab_out) y_tab_out[it] = y3[3 * (size_t)it];
-    if (G_out) G_out[it] = y3[3 * (size_t)it + 1];
-    if (H_out) H_out[it] = y3[3 * (size_t)it + 2];
-  }
-  if (word[0]) {
-    st->active = false;
-    return vbmc_fail(ctx, VBMC_E_NONFINITE, "adam_run_auto: an iterate became non-finite");
-  }
-  return VBMC_OK;
+  return decode_status(ctx, st, "adam_run_auto", word[0]);
 }
 
 extern "C" int vbmc_adam_end(vbmc_ctx* ctx, double* theta_out, double* mu_KxD, double* sigma_K,
@@ -1139,11 +941,7 @@ extern "C" int vbmc_adam_end(vbmc_ctx* ctx, double* theta_out, double* mu_KxD, d
   HIP_TRY(ctx, hipMemcpyAsync(th.data(), st->state + st->lay.o_theta(), sizeof(double) * st->n_theta, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));
   // the device pack in d_mix is the mixture of the last iterate: make the host copies agree
-  ctx->mu.assign(aux.begin(), aux.begin() + K * D);
-  ctx->sigma.assign(aux.begin() + K * D, aux.begin() + K * D + K);
-  ctx->lambd.assign(aux.begin() + K * D + K, aux.begin() + K * D + K + D);
-  ctx->w.assign(aux.begin() + K * D + K + D, aux.begin() + K * D + 2 * K + D);
-  ctx->eta.assign(aux.begin() + K * D + 2 * K + D, aux.end());
+  ctx_unpack_aux(ctx, aux.data());
   ctx->exp_eta_valid = false;
   ctx->pack_valid = true;
   if (theta_out) memcpy(theta_out, th.data(), sizeof(double) * st->n_theta);

@@ -1,6 +1,7 @@
 // Device-side pieces of the Adam loop (adam.hip) that other translation units need: the state
 // layout, the argument block, and the body of the "pre" workgroup, which the wave-split entropy
-// kernel (entropy_ws.hip) runs as an extra row of its own launch.
+// kernel (entropy_ws.hip) runs as an extra row of its own launch; and the pieces every form of the
+// loop shares: the step (adam_step_body, adam_update) and the pack of the new iterate (pack_from_theta).
 #pragma once
 #include "common.h"
 #include "fastmath.h"
@@ -110,6 +111,8 @@ static __device__ __forceinline__ double wave_sum(double v) {
 // either at run time makes the compiler emit flat_* instructions, several times slower on LDS).
 // PRELOADED (with LDS): sh already holds the state prefix (the fused loop, adam_fused.hip, keeps it there
 // across iterations); pre_out: where the result goes (a.pre, or that loop's LDS copy).
+// (This body keeps its own statement of the theta block map, not ThetaMap: with the map every wave-split entropy kernel
+// that carries it came out two registers higher, profiles/adam_step_resources.md.)
 // UB: soft-bound pairs requested together per thread (1 inside the wave-split entropy kernel, whose two-waves-per-SIMD builds
 // have no registers to spare: eight there cost the HEADLINE kernel its second wave -- 272 registers, "failed to meet
 // occupancy target"; 8 in the matrix-pipe kernel and the stand-alone launch)
@@ -370,8 +373,7 @@ static __device__ void pack_from_theta(const AdamDev& a, double* theta, double* 
   constexpr int NW = NT / 64;
   const int D = a.D, K = a.K, tid = threadIdx.x, n = a.n_theta;
   const int lane = tid & 63, wave = tid >> 6;
-  const bool o_mu = a.mask & 1, o_sg = a.mask & 2, o_lm = a.mask & 4, o_w = a.mask & 8;
-  const int p_sg = o_mu ? D * K : 0, p_lm = p_sg + (o_sg ? K : 0), p_w = n - K;
+  const ThetaMap tm(D, K, a.mask, n);
   double* mu = aux;
   double* sg = mu + K * D;
   double* lm = sg + K;
@@ -383,12 +385,12 @@ static __device__ void pack_from_theta(const AdamDev& a, double* theta, double* 
   // ---- round 1: raw lambda and its sum of squares; max of the eta tail ----
   double s2 = 0.0, mx = -INFINITY;
   for (int d = tid; d < D; d += NT) {
-    const double l = o_lm ? fm::exp2_fast(0x1.71547652b82fep+0 * theta[p_lm + d]) : lm[d];  // exp(.)
+    const double l = tm.o_lm() ? fm::exp2_fast(0x1.71547652b82fep+0 * theta[tm.p_lm + d]) : lm[d];  // exp(.)
     lm[d] = l;
     s2 = fma(l, l, s2);
   }
-  if (o_w)
-    for (int k = tid; k < K; k += NT) mx = fmax(mx, theta[p_w + k]);
+  if (tm.o_w())
+    for (int k = tid; k < K; k += NT) mx = fmax(mx, theta[tm.p_w + k]);
   s2 = wave_sum(s2);
   mx = fm::wave_max_dpp(mx);
   __syncthreads();
@@ -407,10 +409,10 @@ static __device__ void pack_from_theta(const AdamDev& a, double* theta, double* 
   const double inl = 1.0 / nl;
   // ---- round 2: unnormalised weights and their sum; product of the normalised lambdas ----
   double wsum = 0.0, pr = 1.0;
-  if (o_w)
+  if (tm.o_w())
     for (int k = tid; k < K; k += NT) {
-      const double e = theta[p_w + k] - mx;
-      theta[p_w + k] = e;
+      const double e = theta[tm.p_w + k] - mx;
+      theta[tm.p_w + k] = e;
       eta[k] = e;
       const double we = fm::exp2_fast(0x1.71547652b82fep+0 * e);
       w[k] = we;
@@ -436,14 +438,14 @@ static __device__ void pack_from_theta(const AdamDev& a, double* theta, double* 
   const MixLayout& ml = a.ml;
   for (int i = tid; i < K * D; i += NT) {
     const int d = i % D;
-    const double m = o_mu ? theta[i] : mu[i];
+    const double m = tm.o_mu() ? theta[i] : mu[i];
     mu[i] = m;
     p[ml.o_mu + i] = m;
     p[ml.o_mup + i] = m * fm::rcp_fast(lm[d] * inl);
   }
   for (int k = tid; k < K; k += NT) {
-    const double s = (o_sg ? fm::exp2_fast(0x1.71547652b82fep+0 * theta[p_sg + k]) : sg[k]) * nl;
-    const double wk = o_w ? w[k] / wsum : w[k];
+    const double s = (tm.o_sg() ? fm::exp2_fast(0x1.71547652b82fep+0 * theta[tm.p_sg + k]) : sg[k]) * nl;
+    const double wk = tm.o_w() ? w[k] / wsum : w[k];
     double sD = 1.0, b = s;  // sigma^D by repeated squaring, as the host pack (ctx.hip)
     for (int e = D; e > 0; e >>= 1) {
       if (e & 1) sD *= b;
@@ -468,5 +470,145 @@ static __device__ void pack_from_theta(const AdamDev& a, double* theta, double* 
   }
 }
 
+// ---------------------------------------------------------------------------
+// The step every form of the loop takes once dF is known (minimize_adam.py:89-105): the moments, their bias corrections
+// c1 / c2, the step and the box clamp.  m, v: in / out.  omb1, omb2 = 1 - beta1, 1 - beta2 (arguments: the fused loop keeps
+// them in LDS); lo, hi: where the box of this entry is (a register of the caller, or memory; read only with a box).
+static __device__ __forceinline__ double adam_update(const AdamDev& a, double x, double g, double& m, double& v, double omb1,
+                                                     double omb2, double c1, double c2, double step, const double* lo,
+                                                     const double* hi) {
+  m = a.beta1 * m + omb1 * g;
+  v = a.beta2 * v + omb2 * (g * g);
+  const double m_hat = m * c1, v_hat = v * c2;
+  x = x - step * m_hat / (sqrt(v_hat) + a.fudge);
+  if (a.has_box) x = fmin(*hi, fmax(*lo, x));
+  return x;
+}
+
+// One iteration's update of theta by a workgroup of 256 threads, shared by adam_step_kernel and the table blocks of
+// adam_tail_kernel (adam.hip): dF = pre + Jacobian(entropy gradient) (entmc_vbmc.py:114-130), then adam_update.  Every
+// array that is read exactly once (entropy sums, pre, m, v, box) goes from global memory straight to registers in one
+// batch of independent loads.  theta | aux must have been requested (mirror or memory) by the caller: the barrier in
+// here orders them.  What differs between the kernels:
+//   raw(i)              entry i of the normalised entropy accumulator (a plain or an agent-scope load)
+//   store_mv(i, m, v)   where the new moments go
+//   writer              this workgroup stores the iterate's row of x_tab / y_tab
+//   loaded()            called once the loads have been consumed into LDS order (a time stamp, or nothing)
+// Ends with a barrier: theta holds the new iterate.
+template <class Raw, class StoreMV, class Loaded>
+static __device__ __forceinline__ void adam_step_body(const AdamDev& a, int iter, double* theta, const double* aux, double* ee,
+                                                      double* red, bool writer, Raw raw, StoreMV store_mv, Loaded loaded) {
+  const int D = a.D, K = a.K, tid = threadIdx.x, n = a.n_theta;
+  const AdamLayout& L = a.lay;
+  const ThetaMap tm(D, K, a.mask, n);
+  const int f_w = tm.raw_w();
+
+  constexpr int U = 4;
+  double r_raw[U], r_pre[U], r_m[U], r_v[U], r_lo[U], r_hi[U];
+  double rw = 0.0;
+  if (tm.o_w() && tid < K) rw = raw(f_w + tid);  // K <= 256 per pass below
+  auto load_chunk = [&](int base) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = base + u * 256 + tid;
+      const bool in = i < n;
+      r_raw[u] = in ? raw(tm.raw_index(i)) : 0.0;
+      r_pre[u] = in ? a.pre[i] : 0.0;
+      r_m[u] = in ? a.state[L.o_m() + i] : 0.0;
+      r_v[u] = in ? a.state[L.o_v() + i] : 0.0;
+      r_lo[u] = (in && a.has_box) ? a.state[L.o_xlb() + i] : 0.0;
+      r_hi[u] = (in && a.has_box) ? a.state[L.o_xub() + i] : 0.0;
+    }
+  };
+  load_chunk(0);
+  // minimize_adam.py:92-98 (evaluated while the loads above are in flight)
+  // beta^(i+1) and exp(-(i+1)/decay) as exp2 of host-prepared logarithms (pow() is ~200 dependent
+  // instructions; the powers are accurate to ~1e-15 relative for any iteration count in use)
+  const double it1 = (double)(iter + 1);
+  const double c1 = 1.0 / (1.0 - fm::exp2_fast(it1 * a.l2_beta1));
+  const double c2 = 1.0 / (1.0 - fm::exp2_fast(it1 * a.l2_beta2));
+  const double step = a.master_min + (a.master_max - a.master_min) * fm::exp2_fast(-it1 * a.l2e_over_decay);
+  double* x_row = a.x_tab + (size_t)iter * n;
+  double* y_out = a.y_tab + 3 * (size_t)iter;
+  __syncthreads();
+  loaded();
+
+  const double* sg = aux + K * D;
+  const double* lm = sg + K;
+  const double* eta = lm + D + K;
+  // ---- softmax Jacobian of the entropy's weight gradient: needs two sums over k ----
+  double sm_s = 1.0, sm_dot = 0.0;
+  if (tm.o_w()) {
+    double ps = 0.0, pd = 0.0;
+    for (int k = tid; k < K; k += 256) {
+      const double e = fm::exp2_fast(0x1.71547652b82fep+0 * eta[k]);
+      ee[k] = e;
+      ps += e;
+      pd += e * (k == tid ? rw : raw(f_w + k));
+    }
+    ps = wave_sum(ps);
+    pd = wave_sum(pd);
+    if ((tid & 63) == 0) {
+      red[tid >> 6] = ps;
+      red[4 + (tid >> 6)] = pd;
+    }
+    __syncthreads();
+    sm_s = (red[0] + red[1]) + (red[2] + red[3]);
+    sm_dot = (red[4] + red[5]) + (red[6] + red[7]);
+  }
+  if (writer && tid == 0) {
+    const double G = a.pre[n], loss = a.pre[n + 1], H = raw(0);
+    y_out[0] = -G - H + loss;
+    y_out[1] = G;
+    y_out[2] = H;
+  }
+  for (int base = 0; base < n; base += 256 * U) {
+    if (base > 0) load_chunk(base);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = base + u * 256 + tid;
+      if (i >= n) continue;
+      // ---- dF: pre + Jacobian of the entropy part of F = -G - H ----
+      double g;
+      if (tm.in_mu(i)) {
+        g = r_pre[u] - r_raw[u];
+      } else if (tm.in_sg(i)) {
+        g = r_pre[u] - r_raw[u] * sg[i - tm.p_sg];
+      } else if (tm.in_lm(i)) {
+        g = r_pre[u] - r_raw[u] * lm[i - tm.p_lm];
+      } else {
+        const double e = ee[i - tm.p_w];
+        g = r_pre[u] + (e * sm_dot / (sm_s * sm_s) - e * r_raw[u] / sm_s);
+      }
+      double m = r_m[u], v = r_v[u];
+      const double x = adam_update(a, theta[i], g, m, v, 1.0 - a.beta1, 1.0 - a.beta2, c1, c2, step, &r_lo[u], &r_hi[u]);
+      store_mv(i, m, v);
+      theta[i] = x;
+      if (writer) x_row[i] = x;
+    }
+  }
+  __syncthreads();
+}
+
+// Thread 0 polls *word at agent scope until arrived(value) or `timeout` wall-clock ticks have passed, SLEEP between two
+// looks; every thread returns whether it arrived (s_ok: a shared word of the caller).  If not, bit 8 of the status word is raised.
+template <int SLEEP, class T, class Arrived>
+static __device__ bool bounded_wait(const AdamDev& a, const T* word, unsigned long long timeout, int* s_ok, Arrived arrived) {
+  if (threadIdx.x == 0) {
+    const unsigned long long t0 = wall_clock64();
+    int ok = 1;
+    while (!arrived(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+      if (wall_clock64() - t0 > timeout) {
+        ok = 0;
+        break;
+      }
+      __builtin_amdgcn_s_sleep(SLEEP);
+    }
+    *s_ok = ok;
+  }
+  __syncthreads();
+  if (!*s_ok && threadIdx.x == 0) atomicOr(a.status, 8);
+  return *s_ok;
+}
 
 }  // namespace adam_dev

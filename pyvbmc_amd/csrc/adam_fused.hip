@@ -80,8 +80,7 @@ __device__ __forceinline__ double sumw(const double* r) {
 __device__ void pack_waves(const AdamDev& a, double* theta, double* aux, double* p, int tid) {
   const int D = a.D, K = a.K, n = a.n_theta;
   const int lane = tid & 63, wave = tid >> 6;
-  const bool o_mu = a.mask & 1, o_sg = a.mask & 2, o_lm = a.mask & 4, o_w = a.mask & 8;
-  const int p_sg = o_mu ? D * K : 0, p_lm = p_sg + (o_sg ? K : 0), p_w = n - K;
+  const ThetaMap tm(D, K, a.mask, n);
   double* mu = aux;
   double* sg = mu + K * D;
   double* lm = sg + K;
@@ -93,16 +92,16 @@ __device__ void pack_waves(const AdamDev& a, double* theta, double* aux, double*
   if (bad) atomicOr(a.status, 1);
   const bool isd = lane < D, isk = lane < K;
   // raw lambda (lane = d), the eta tail (lane = k)
-  const double l_raw = isd ? (o_lm ? fm::exp2_fast(LOG2E * theta[p_lm + lane]) : lm[lane]) : 0.0;
-  const double th_w = (o_w && isk) ? theta[p_w + lane] : -INFINITY;
-  const double th_s = (o_sg && isk) ? theta[p_sg + lane] : 0.0;
+  const double l_raw = isd ? (tm.o_lm() ? fm::exp2_fast(LOG2E * theta[tm.p_lm + lane]) : lm[lane]) : 0.0;
+  const double th_w = (tm.o_w() && isk) ? theta[tm.p_w + lane] : -INFINITY;
+  const double th_s = (tm.o_sg() && isk) ? theta[tm.p_sg + lane] : 0.0;
   const double sg_old = isk ? sg[lane] : 1.0, w_old = isk ? w[lane] : 0.0;
   const double s2 = fm::wave_sum_dpp(l_raw * l_raw);
   const double mx = fm::wave_max_dpp(th_w);
   const double nl = sqrt(s2 / D);  // lambda -> unit RMS, sigma absorbs it
   const double inl = 1.0 / nl;
   const double e = th_w - mx;
-  const double we = (o_w && isk) ? fm::exp2_fast(LOG2E * e) : 0.0;
+  const double we = (tm.o_w() && isk) ? fm::exp2_fast(LOG2E * e) : 0.0;
   const double wsum = fm::wave_sum_dpp(we);
   const double l_n = l_raw * inl;
   const double pr = fm::wave_prod_dpp(isd ? l_n : 1.0);
@@ -112,15 +111,15 @@ __device__ void pack_waves(const AdamDev& a, double* theta, double* aux, double*
   // per component (lane = k): wave 0 stores
   if (wave == 0 && isk) {
     const int k = lane;
-    const double s = (o_sg ? fm::exp2_fast(LOG2E * th_s) : sg_old) * nl;
-    const double wk = o_w ? we / wsum : w_old;
+    const double s = (tm.o_sg() ? fm::exp2_fast(LOG2E * th_s) : sg_old) * nl;
+    const double wk = tm.o_w() ? we / wsum : w_old;
     double sD = 1.0, b = s;  // sigma^D by repeated squaring, as the host pack (ctx.hip)
     for (int ex = D; ex > 0; ex >>= 1) {
       if (ex & 1) sD *= b;
       b *= b;
     }
-    if (o_w) {
-      theta[p_w + k] = e;
+    if (tm.o_w()) {
+      theta[tm.p_w + k] = e;
       eta[k] = e;
     }
     sg[k] = s;
@@ -148,7 +147,7 @@ __device__ void pack_waves(const AdamDev& a, double* theta, double* aux, double*
       const int ilo = __builtin_amdgcn_ds_bpermute(d << 2, __double2loint(il));
       const int ihi = __builtin_amdgcn_ds_bpermute(d << 2, __double2hiint(il));
       if (i < K * D) {
-        const double m = o_mu ? theta[i] : mu[i];
+        const double m = tm.o_mu() ? theta[i] : mu[i];
         mu[i] = m;
         p[ml.o_mu + i] = m;
         p[ml.o_mup + i] = m * __hiloint2double(ihi, ilo);
@@ -170,8 +169,7 @@ __global__ __launch_bounds__(NT) void adam_fused_kernel(FusedArgs f) {
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = blockIdx.x, G = gridDim.x;
-  const bool o_mu = a.mask & 1, o_sg = a.mask & 2, o_lm = a.mask & 4, o_w = a.mask & 8;
-  const int p_sg = o_mu ? D * K : 0, p_lm = p_sg + (o_sg ? K : 0), p_w = n - K;
+  const ThetaMap tm(D, K, a.mask, n);
   const int RE = 2 + 2 * D + K;       // entropy record: slog | raw mu_j (D) | raw sigma_j | lam_j (D) | W_j (K)
   const int RC = 2 * D + 4;           // GP contribution record: gmu (D) | glm (D) | gs | nu | b0 | qbar
   const int n_blocks = S * K;
@@ -583,7 +581,7 @@ __global__ __launch_bounds__(NT) void adam_fused_kernel(FusedArgs f) {
     const double c1 = 1.0 / (1.0 - fm::exp2_fast(it1 * a.l2_beta1));
     const double c2 = 1.0 / (1.0 - fm::exp2_fast(it1 * a.l2_beta2));
     const double step = a.master_min + cst[5] * fm::exp2_fast(-it1 * a.l2e_over_decay);
-    if (o_w)
+    if (tm.o_w())
       for (int k = tid; k < K; k += NT) ee[k] = fm::exp2_fast(LOG2E * eta[k]);  // softmax terms of the current iterate
     double loss = 0.0;
     if (a.has_bnd) {
@@ -591,19 +589,8 @@ __global__ __launch_bounds__(NT) void adam_fused_kernel(FusedArgs f) {
       // ahead of the normals, into registers, was measured and cost more in spills than the ~0.3 us it hides)
       const double* bnd_lb = a.state + L.o_blb();
       const double* bnd_ub = a.state + L.o_bub();
-      const int n_mu = o_mu ? D * K : 0, n_sc = (o_sg || o_lm) ? D * K : 0;
       for (int i = tid; i < a.n_bnd; i += NT) {
-        double x;
-        if (i < n_mu) {
-          x = theta[i];
-        } else if (i < n_mu + n_sc) {
-          const int q = i - n_mu, k = q / D, d = q - k * D;  // ravel('F') of the (D,K) array
-          const double ls = o_sg ? theta[p_sg + k] : log(sg[k]);
-          const double ll = o_lm ? theta[p_lm + d] : log(lm[d]);
-          x = ll + ls;
-        } else {
-          x = theta[p_w + (i - n_mu - n_sc)];
-        }
+        const double x = tm.bound_coord(i, theta, sg, lm);
         const double lb = bnd_lb[i], ub = bnd_ub[i];
         const double ell = (ub - lb) * a.tol_con;
         double gg = 0.0;
@@ -713,13 +700,13 @@ __global__ __launch_bounds__(NT) void adam_fused_kernel(FusedArgs f) {
         gpart = wk * wI;
         gsg[k] = wk * sgk * (gs - qbar);
         double gg = -wI;  // d(-G)/dw_k; the entropy part is added by the update below
-        if (a.has_bnd && o_w) {  // weight penalty (:1211-1229)
+        if (a.has_bnd && tm.o_w()) {  // weight penalty (:1211-1229)
           const bool small = wk < a.w_thresh;
           loss += (small ? wk : a.w_thresh) * a.w_pen;
           if (small) gg += a.w_pen;
         }
         gw[k] = gg;
-        if (o_w) {
+        if (tm.o_w()) {
           const double e = ee[k];
           ps = e;
           pd = e * gg;
@@ -737,11 +724,11 @@ __global__ __launch_bounds__(NT) void adam_fused_kernel(FusedArgs f) {
       // per dimension (a 16-lane group each, sixteen groups; D > 16: a second round): lambda's sums over (s, k), the soft
       // bounds folded onto lambda
       const int ns = tid & 15;
-      const int sc0 = o_mu ? D * K : 0;
+      const int sc0 = tm.p_sg;
       for (int d = (tid - 64) >> 4; d < D; d += 16) {
         double acc = 0.0, accb = 0.0;
         for (int idx = ns; idx < n_blocks; idx += 16) acc += crec[(size_t)idx * RC + D + d];
-        if (a.has_bnd && o_lm)
+        if (a.has_bnd && tm.o_lm())
           for (int k = ns; k < K; k += 16) accb += dL[sc0 + d * K + k];
         acc = fm::row16_sum_dpp(acc);
         accb = fm::row16_sum_dpp(accb);
@@ -750,7 +737,7 @@ __global__ __launch_bounds__(NT) void adam_fused_kernel(FusedArgs f) {
           bl[d] = accb;
         }
       }
-    } else if (o_w) {
+    } else if (tm.o_w()) {
       // the softmax Jacobian of the entropy's weight gradient needs sum_k e_k raw_k with raw_k = -(slog_k + sum_j w_j W_jk) / ns:
       // summed the other way round, sum_j [e_j slog_j + w_j sum_k e_k W_jk], it needs no finished raw_k.  lane = j, the
       // three waves split the k range
@@ -782,10 +769,10 @@ __global__ __launch_bounds__(NT) void adam_fused_kernel(FusedArgs f) {
     // Adam update with the box clamp (minimize_adam.py:89-105)
     {
       const double Gv = red[0], lossv = a.has_bnd ? sumw(red + SW) : 0.0;
-      const double sm_s = o_w ? red[2 * SW] : 1.0;       // sum_k e_k
-      const double pm_dot = o_w ? red[3 * SW] : 0.0;     // sum_k e_k gw_k
-      const double sm_dot = o_w ? -f.inv_ns * ((red[6 * SW] + red[6 * SW + 1]) + red[6 * SW + 2]) : 0.0;  // sum_k e_k raw_k
-      const int sc0 = o_mu ? D * K : 0;
+      const double sm_s = tm.o_w() ? red[2 * SW] : 1.0;       // sum_k e_k
+      const double pm_dot = tm.o_w() ? red[3 * SW] : 0.0;     // sum_k e_k gw_k
+      const double sm_dot = tm.o_w() ? -f.inv_ns * ((red[6 * SW] + red[6 * SW + 1]) + red[6 * SW + 2]) : 0.0;  // sum_k e_k raw_k
+      const int sc0 = tm.p_sg;
       auto out_sum = [&](int o) {
         double sum = (red2[0][o] + red2[1][o]) + (red2[2][o] + red2[3][o]);
         if (SW == 8) sum += (red2[4][o] + red2[5][o]) + (red2[6][o] + red2[7][o]);
@@ -808,15 +795,15 @@ __global__ __launch_bounds__(NT) void adam_fused_kernel(FusedArgs f) {
         const int i = u * NT + tid;
         if (i >= n) continue;
         double gr;  // dF_i
-        if (o_mu && i < D * K) {
+        if (tm.in_mu(i)) {
           const int k = i / D, d = i - k * D;
           double gm = 0.0;
           for (int sidx = 0; sidx < S; ++sidx) gm += crec[(size_t)(sidx * K + k) * RC + d];
           double gg = -gm;
           if (a.has_bnd) gg += dL[i];
           gr = gg - recs[k * RE + 1 + d];
-        } else if (o_sg && i >= p_sg && i < p_sg + K) {
-          const int k = i - p_sg;
+        } else if (tm.in_sg(i)) {
+          const int k = i - tm.p_sg;
           double gg = -gsg[k] * sg[k];
           if (a.has_bnd) {
             // the reference reshapes this block C-order (D,K) (:585-587); restated as-is
@@ -825,27 +812,23 @@ __global__ __launch_bounds__(NT) void adam_fused_kernel(FusedArgs f) {
             gg += acc;
           }
           gr = gg - recs[k * RE + 1 + D] * sg[k];
-        } else if (o_lm && i >= p_lm && i < p_lm + D) {
-          const int d = i - p_lm;
+        } else if (tm.in_lm(i)) {
+          const int d = i - tm.p_lm;
           double gg = -glm[d] * lm[d];
           if (a.has_bnd) gg += bl[d];
           const double rr = out_sum(1 + d) * f.inv_ns * pack[ml.o_ilam + d];
           gr = gg - rr * lm[d];
         } else {
-          const int k = i - p_w;
+          const int k = i - tm.p_w;
           const double e = ee[k];
           double gg = -e * pm_dot / (sm_s * sm_s) + e * gw[k] / sm_s;
           if (a.has_bnd) gg += dL[a.n_bnd - K + k];
           const double rr = -f.inv_ns * (recs[k * RE] + out_sum(1 + D + k));
           gr = gg + (e * sm_dot / (sm_s * sm_s) - e * rr / sm_s);
         }
-        const double m = a.beta1 * r_m[u] + cst[0] * gr;
-        const double v = a.beta2 * r_v[u] + cst[1] * (gr * gr);
-        r_m[u] = m;
-        r_v[u] = v;
-        const double m_hat = m * c1, v_hat = v * c2;
-        double x = theta[i] - step * m_hat / (sqrt(v_hat) + a.fudge);
-        if (a.has_box) x = fmin(a.state[L.o_xub() + i], fmax(a.state[L.o_xlb() + i], x));  // (minimize_adam's lb / ub: not optimize_vp's path)
+        // (the box is minimize_adam's lb / ub: not optimize_vp's path)
+        const double x = adam_update(a, theta[i], gr, r_m[u], r_v[u], cst[0], cst[1], c1, c2, step, a.state + L.o_xlb() + i,
+                                     a.state + L.o_xub() + i);
         theta[i] = x;
         if (g == 0) {
           if (f.stop_rule) st_wt(x_row + i, x);  // read back by every workgroup at the end of the batch (below)

@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void batch_finalize_kernel(BatchFin f) {
   const double* lm = sg + K;
   const double* w = lm + D;
   const bool quad = f.mean_kind == VBMC_MEAN_NEGQUAD;
-  const bool o_mu = f.mask & 1, o_sg = f.mask & 2, o_lm = f.mask & 4, o_w = f.mask & 8;
+  const ThetaMap tm(D, K, f.mask, f.n_theta);
   const int st1 = 1 + 2 * D;
   if (quad)
     for (int i = tid; i < S * D; i += 256) {
@@ -208,26 +208,16 @@ __global__ __launch_bounds__(256) void batch_finalize_kernel(BatchFin f) {
   // ---- soft bounds on (mu, ln sigma + ln lambda, eta) and the weight penalty (:1195-1229) ----
   double L = 0.0;
   if (f.n_bnd > 0) {
-    const int n_mu = o_mu ? D * K : 0, n_sc = (o_sg || o_lm) ? D * K : 0;
-    const int p_sg = n_mu, p_lm = p_sg + (o_sg ? K : 0), p_w = f.n_theta - K;
     const double* bsg = f.base_aux + K * D;
     const double* blm = bsg + K;
     for (int q = tid; q < f.n_bnd; q += 256) {
-      double x;
-      if (q < n_mu) {
-        x = th[q];
-      } else if (q < n_mu + n_sc) {
-        const int r = q - n_mu, k = r / D, d = r - k * D;
-        x = (o_lm ? th[p_lm + d] : log(blm[d])) + (o_sg ? th[p_sg + k] : log(bsg[k]));
-      } else {
-        x = th[p_w + (q - n_mu - n_sc)];  // (the tail was max-shifted by the pack kernel)
-      }
+      const double x = tm.bound_coord(q, th, bsg, blm);  // (the eta tail was max-shifted by the pack kernel)
       const double lb = f.blb[q], ub = f.bub[q];
       const double ell = (ub - lb) * f.tol_con;
       if (x < lb) L += 0.5 * ((lb - x) / ell) * ((lb - x) / ell);
       if (x > ub) L += 0.5 * ((x - ub) / ell) * ((x - ub) / ell);
     }
-    if (o_w)
+    if (tm.o_w())
       for (int k = tid; k < K; k += 256) L += ((w[k] < f.w_thresh) ? w[k] : f.w_thresh) * f.w_pen;
   }
   gacc = wave_sum(gacc);
@@ -270,13 +260,11 @@ extern "C" int vbmc_neg_elcbo_batch(vbmc_ctx* ctx, const double* thetas_BxN, int
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int D = ctx->D, K = ctx->K, S = ctx->gp.S;
   const int mask = opts->optimize_mask;
-  const bool o_mu = mask & 1, o_sg = mask & 2, o_lm = mask & 4, o_w = mask & 8;
-  const int need = (o_mu ? D * K : 0) + (o_sg ? K : 0) + (o_lm ? D : 0) + (o_w ? K : 0);
-  if (n_theta != need) return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo_batch: theta length %d does not match", n_theta);
+  const ThetaMap tm(D, K, mask);
+  if (n_theta != tm.n_theta()) return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo_batch: theta length %d does not match", n_theta);
   const bool has_bnd = opts->bnd_lb && opts->bnd_ub;
-  const int n_ext = (o_mu ? D * K : 0) + ((o_sg || o_lm) ? D * K : 0) + (o_w ? K : 0);
-  if (has_bnd && n_ext != opts->n_bnd)
-    return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo_batch: bounds length %d != %d", opts->n_bnd, n_ext);
+  if (has_bnd && tm.n_bnd() != opts->n_bnd)
+    return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo_batch: bounds length %d != %d", opts->n_bnd, tm.n_bnd());
   const int n_bnd = has_bnd ? opts->n_bnd : 0;
   MixLayout ml;
   ml.plan(D, K);
@@ -302,11 +290,7 @@ extern "C" int vbmc_neg_elcbo_batch(vbmc_ctx* ctx, const double* thetas_BxN, int
   hipStream_t sm = ctx->stream;
   // the small host-side inputs through the pinned buffer: the ctx mixture's attributes, the bounds
   double* hp = ctx->h_pinned + 3 * (size_t)B;
-  memcpy(hp, ctx->mu.data(), sizeof(double) * K * D);
-  memcpy(hp + K * D, ctx->sigma.data(), sizeof(double) * K);
-  memcpy(hp + K * D + K, ctx->lambd.data(), sizeof(double) * D);
-  memcpy(hp + K * D + K + D, ctx->w.data(), sizeof(double) * K);
-  memcpy(hp + K * D + 2 * K + D, ctx->eta.data(), sizeof(double) * K);
+  ctx_pack_aux(ctx, hp);
   if (has_bnd) {
     memcpy(hp + n_aux, opts->bnd_lb, sizeof(double) * n_bnd);
     memcpy(hp + n_aux + n_bnd, opts->bnd_ub, sizeof(double) * n_bnd);

@@ -116,7 +116,7 @@ extern "C" int vbmc_neg_elcbo(vbmc_ctx* ctx, double* theta, int n_theta,
   };
   const int D = ctx->D, K = ctx->K;
   const int mask = opts->optimize_mask;
-  const bool o_mu = mask & 1, o_sg = mask & 2, o_lm = mask & 4, o_w = mask & 8;
+  const ThetaMap tm(D, K, mask, n_theta);
   // theta -> mixture -> pinned pack now; its upload is issued further down, back to back with the
   // launches that wait for it (a copy issued here would sit finished in the queue while the
   // planning below runs: 4 us of idle GPU per evaluation)
@@ -124,7 +124,7 @@ extern "C" int vbmc_neg_elcbo(vbmc_ctx* ctx, double* theta, int n_theta,
   int rc = vbmc_theta_to_mixture(ctx, theta, n_theta, mask, mu_KxD, sigma_K, lambd_D, w_K, eta_K);
   ctx->defer_mix_upload = false;
   if (rc) return rc;
-  if (o_w) {
+  if (tm.o_w()) {
     // the reference shifts its caller's theta tail in place (:1082-1085)
     double* e = theta + (n_theta - K);
     double mx = e[0];
@@ -144,17 +144,8 @@ extern "C" int vbmc_neg_elcbo(vbmc_ctx* ctx, double* theta, int n_theta,
   if (mc) {
     if (opts->ns_per_comp & 1)
       return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo: ns_per_comp must be even");
-    const int64_t n_half = opts->ns_per_comp / 2;
-    if (row_count < 0) {
-      row_begin = n_half * ctx->rank / ctx->world;
-      row_count = n_half * (ctx->rank + 1) / ctx->world - row_begin;
-    }
-    if (row_begin < 0 || row_begin + row_count > n_half)
-      return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo: bad row slice");
-    if (opts->eps_mode == VBMC_EPS_RESIDENT &&
-        (!ctx->d_eps || ctx->eps_K != K || ctx->eps_D != D || ctx->eps_n_half != n_half ||
-         ctx->eps_row_begin != row_begin || ctx->eps_rows != row_count))
-      return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo: resident eps does not match the request");
+    rc = resolve_row_slice(ctx, opts, "neg_elcbo", &row_begin, &row_count);
+    if (rc) return rc;
   }
 
   // Results land in pinned host memory: the GP sums are written there directly by the
@@ -166,11 +157,7 @@ extern "C" int vbmc_neg_elcbo(vbmc_ctx* ctx, double* theta, int n_theta,
   double* hp_dev = ctx->hp_dev;  // device-side address of the pinned block
   double* res_out = hp_dev;
   double* raw_host = hp_dev + n_res;
-  static const bool force_coll = [] {
-    const char* e = getenv("VBMC_FORCE_COLLECTIVE");
-    return e && e[0] == '1';
-  }();
-  const bool multi = ctx->comm != nullptr && (ctx->world > 1 || force_coll);
+  const bool multi = ctx_is_multi(ctx);
   double* raw_out = raw_host;
   if (multi && mc) {
     rc = ensure_dev(ctx, &ctx->d_out, &ctx->d_out_cap, (size_t)n_raw);
@@ -485,68 +472,36 @@ extern "C" int vbmc_neg_elcbo(vbmc_ctx* ctx, double* theta, int n_theta,
   std::vector<double>& dFb = sc.dFb;
   if (has_bnd && grad_flags) dFb.assign((size_t)n_theta, 0.0);
   if (has_bnd) {
+    if (tm.n_bnd() != opts->n_bnd)
+      return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo: bounds length %d != %d", opts->n_bnd, tm.n_bnd());
     std::vector<double>& ext = sc.ext;
-    ext.clear();
-    int pos = 0;
-    std::vector<double>&ln_sigma = sc.ln_sigma, &ln_lambd = sc.ln_lambd;
-    ln_sigma.resize(K);
-    ln_lambd.resize(D);
-    if (o_mu) {
-      ext.insert(ext.end(), theta, theta + D * K);
-      pos = D * K;
-    }
-    if (o_sg) {
-      for (int k = 0; k < K; ++k) ln_sigma[k] = theta[pos + k];
-      pos += K;
-    } else {
-      for (int k = 0; k < K; ++k) ln_sigma[k] = std::log(ctx->sigma[k]);
-    }
-    if (o_lm) {
-      for (int d = 0; d < D; ++d) ln_lambd[d] = theta[pos + d];
-    } else {
-      for (int d = 0; d < D; ++d) ln_lambd[d] = std::log(ctx->lambd[d]);
-    }
-    const int sc0 = (int)ext.size();
-    if (o_sg || o_lm)
-      for (int k = 0; k < K; ++k)
-        for (int d = 0; d < D; ++d) ext.push_back(ln_lambd[d] + ln_sigma[k]);  // ravel('F')
-    if (o_w) ext.insert(ext.end(), theta + (n_theta - K), theta + n_theta);
-    if ((int)ext.size() != opts->n_bnd)
-      return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo: bounds length %d != %d", opts->n_bnd,
-                       (int)ext.size());
+    ext.resize((size_t)tm.n_bnd());
+    const int sc0 = tm.p_sg;
+    for (int i = 0; i < tm.n_bnd(); ++i) ext[i] = tm.bound_coord(i, theta, ctx->sigma.data(), ctx->lambd.data());
     std::vector<double>& dL = sc.dL;
     const double L = soft_bound_loss(ext, opts->bnd_lb, opts->bnd_ub, opts->tol_con,
                                      grad_flags ? &dL : nullptr);
     F_bnd += L;
     if (grad_flags) {
-      int q = 0;
-      if (o_mu) {
-        for (int i = 0; i < D * K; ++i) dFb[q + i] += dL[i];
-        q += D * K;
-      }
-      if (o_sg || o_lm) {
-        // the reference reshapes this block C-order (D,K) (:585-587); restated as-is
-        if (o_sg) {
-          for (int k = 0; k < K; ++k) {
-            double a = 0.0;
-            for (int d = 0; d < D; ++d) a += dL[sc0 + d * K + k];
-            dFb[q + k] += a;
-          }
-          q += K;
+      if (tm.o_mu())
+        for (int i = 0; i < D * K; ++i) dFb[i] += dL[i];
+      // the reference reshapes the scale block C-order (D,K) (:585-587); restated as-is
+      if (tm.o_sg())
+        for (int k = 0; k < K; ++k) {
+          double a = 0.0;
+          for (int d = 0; d < D; ++d) a += dL[sc0 + d * K + k];
+          dFb[tm.p_sg + k] += a;
         }
-        if (o_lm) {
-          for (int d = 0; d < D; ++d) {
-            double a = 0.0;
-            for (int k = 0; k < K; ++k) a += dL[sc0 + d * K + k];
-            dFb[q + d] += a;
-          }
-          q += D;
+      if (tm.o_lm())
+        for (int d = 0; d < D; ++d) {
+          double a = 0.0;
+          for (int k = 0; k < K; ++k) a += dL[sc0 + d * K + k];
+          dFb[tm.p_lm + d] += a;
         }
-      }
-      if (o_w)
-        for (int k = 0; k < K; ++k) dFb[q + k] += dL[dL.size() - K + k];
+      if (tm.o_w())
+        for (int k = 0; k < K; ++k) dFb[tm.p_w + k] += dL[dL.size() - K + k];
     }
-    if (o_w) {
+    if (tm.o_w()) {
       const double th = opts->weight_threshold, pen = opts->weight_penalty;
       double a = 0.0;
       std::vector<double>& wg = sc.wpen;

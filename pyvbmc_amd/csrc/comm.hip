@@ -61,14 +61,18 @@ int rccl_load(vbmc_ctx* ctx) {
       return vbmc_fail((ctx), VBMC_E_RCCL, "%s failed: %s", #call, g_rccl.GetErrorString(r_)); \
   } while (0)
 
-int comm_allreduce_sum(vbmc_ctx* ctx, double* d_buf, int n) {
+bool ctx_is_multi(const vbmc_ctx* ctx) {
   // world == 1 normally skips the collective; VBMC_FORCE_COLLECTIVE=1 keeps it (a 1-rank
   // all-reduce) so the RCCL call path can be exercised on a single-GPU box
   static const bool force = [] {
     const char* e = getenv("VBMC_FORCE_COLLECTIVE");
     return e && e[0] == '1';
   }();
-  if (!ctx->comm || (ctx->world <= 1 && !force)) return 0;
+  return ctx->comm != nullptr && (ctx->world > 1 || force);
+}
+
+int comm_allreduce_sum(vbmc_ctx* ctx, double* d_buf, int n) {
+  if (!ctx_is_multi(ctx)) return 0;
   NCCL_TRY(ctx, g_rccl.AllReduce(d_buf, d_buf, (size_t)n, ncclDouble, ncclSum, (ncclComm_t)ctx->comm,
                                  ctx->stream));
   return 0;

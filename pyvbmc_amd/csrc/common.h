@@ -46,6 +46,55 @@ struct MixLayout {
   }
 };
 
+// theta = [mu (K D) | ln sigma (K) | ln lambda (D) | eta (K)], each block present when its bit of the optimise mask
+// (1, 2, 4, 8) is set: where the blocks start, which entry of the raw entropy vector [H | d mu | d sigma | d lambda | d w]
+// and which coordinate of the extended soft-bound vector [mu | ln sigma + ln lambda | eta] belongs to an entry.  Kernels
+// build it at the top of their body, where its values are wave-uniform locals.
+struct ThetaMap {
+  int D, K;
+  int mask;
+  __host__ __device__ bool o_mu() const { return mask & 1; }
+  __host__ __device__ bool o_sg() const { return mask & 2; }
+  __host__ __device__ bool o_lm() const { return mask & 4; }
+  __host__ __device__ bool o_w() const { return mask & 8; }
+  int p_sg, p_lm, p_w;  // first entry of the sigma, lambda and eta blocks (mu starts at 0)
+  int n_sc;             // entries of the extended soft-bound vector's scale block: the (D,K) array of ln scales if sigma or lambda
+  __host__ __device__ ThetaMap(int D_, int K_, int mask_) : ThetaMap(D_, K_, mask_, 0) { p_w = n_theta() - K; }
+  // (n_theta: of a caller that holds it already)
+  __host__ __device__ ThetaMap(int D_, int K_, int mask_, int n_theta_)
+      : D(D_), K(K_), mask(mask_), p_sg((mask_ & 1) ? D_ * K_ : 0), p_lm(p_sg + ((mask_ & 2) ? K_ : 0)), p_w(n_theta_ - K_),
+        n_sc((mask_ & 6) ? D_ * K_ : 0) {}
+  __host__ __device__ int n_theta() const { return p_lm + (o_lm() ? D : 0) + (o_w() ? K : 0); }
+  // the extended soft-bound vector: mu | ln scale | eta
+  __host__ __device__ int n_bnd() const { return p_sg + n_sc + (o_w() ? K : 0); }
+  // the block theta index i lies in (tested in this order; what is left is the eta block)
+  __host__ __device__ bool in_mu(int i) const { return o_mu() && i < D * K; }
+  __host__ __device__ bool in_sg(int i) const { return o_sg() && i >= p_sg && i < p_sg + K; }
+  __host__ __device__ bool in_lm(int i) const { return o_lm() && i >= p_lm && i < p_lm + D; }
+  __host__ __device__ int raw_w() const { return 1 + D * K + K + D; }  // weight block of the raw vector
+  __host__ __device__ int raw_index(int i) const {
+    if (o_w() && i >= p_w) return raw_w() + (i - p_w);
+    if (o_lm() && i >= p_lm) return 1 + D * K + K + (i - p_lm);
+    if (o_sg() && i >= p_sg) return 1 + D * K + (i - p_sg);
+    return 1 + i;
+  }
+  // coordinate i of the extended soft-bound vector; sigma / lambda: the attributes, for the blocks theta does not carry
+  __host__ __device__ double bound_coord(int i, const double* theta, const double* sigma, const double* lambda) const {
+    double x;
+    if (i < p_sg) {
+      x = theta[i];
+    } else if (i < p_sg + n_sc) {
+      const int q = i - p_sg, k = q / D, d = q - k * D;  // ravel('F') of the (D,K) array
+      const double ls = o_sg() ? theta[p_sg + k] : log(sigma[k]);
+      const double ll = o_lm() ? theta[p_lm + d] : log(lambda[d]);
+      x = ll + ls;
+    } else {
+      x = theta[p_w + (i - p_sg - n_sc)];
+    }
+    return x;
+  }
+};
+
 struct GpState {
   bool set = false;
   int N = 0, D = 0, S = 0, P = 0, mean_kind = 0;
@@ -81,7 +130,7 @@ struct GljHost {
 // host scratch of one fused evaluation, kept in the context so that the hot call allocates nothing
 struct ElboScratch {
   GljHost glj;
-  std::vector<double> dG, dH, dF, dFb, mu, sg, lm, wg, ext, ln_sigma, ln_lambd, dL, wpen, jw;
+  std::vector<double> dG, dH, dF, dFb, mu, sg, lm, wg, ext, dL, wpen, jw;
 };
 
 struct vbmc_ctx {
@@ -293,6 +342,12 @@ int make_mixture2(vbmc_ctx* ctx, const char* who, int err, int D, int K2, const 
                   const double* lambd2_D, const double* w2_K, MixLayout& ml2, std::vector<double>& pack2);
 int theta_to_arrays(int D, int K, const double* theta, int n_theta, int optimize_mask, double* mu,
                     double* sg, double* lm, double* w, double* eta);
+// [mu | sigma | lambda | w | eta] of the context's mixture (adam_dev::aux_len doubles) into dst / back from src
+void ctx_pack_aux(const vbmc_ctx* ctx, double* dst);
+void ctx_unpack_aux(vbmc_ctx* ctx, const double* src);
+// this rank's slice of the ns_per_comp / 2 antithetic rows (opts->row_count < 0: the even split over the ranks), checked
+// against the range and, for resident draws, against what the context holds; `who` prefixes the messages
+int resolve_row_slice(vbmc_ctx* ctx, const vbmc_elbo_opts* opts, const char* who, int64_t* row_begin, int64_t* row_count);
 int upload_packed_mixture(vbmc_ctx* ctx);
 double* write_pack_to_device(vbmc_ctx* ctx);
 int set_mixture_host(vbmc_ctx* ctx, int D, int K, const double* mu_KxD, const double* sigma_K,
@@ -538,6 +593,7 @@ void glj_finalize(const vbmc_ctx* ctx, const double* res, int want_grad, GljHost
 int glj_pack(vbmc_ctx* ctx, const double* mu, const double* sg, const double* lm,
              const double* wg, int grad_flags, int jacobian_flag, double* out);
 // comm
+bool ctx_is_multi(const vbmc_ctx* ctx);  // the entropy sums go through the all-reduce
 int comm_allreduce_sum(vbmc_ctx* ctx, double* d_buf, int n);
 
 // host finalisation (api_entropy.hip) -------------------------------------

@@ -1,4 +1,5 @@
 // Context, device memory and mixture/eps/GP state upload for libvbmc_hip.so.
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
@@ -420,25 +421,18 @@ int make_mixture2(vbmc_ctx* ctx, const char* who, int err, int D, int K2, const 
 // from the current attribute values; blocks whose optimize bit is clear are left alone.
 int theta_to_arrays(int D, int K, const double* theta, int n_theta, int optimize_mask, double* mu,
                     double* sg, double* lm, double* w, double* eta) {
-  const bool o_mu = optimize_mask & 1, o_sg = optimize_mask & 2, o_lm = optimize_mask & 4,
-             o_w = optimize_mask & 8;
-  const int need = (o_mu ? D * K : 0) + (o_sg ? K : 0) + (o_lm ? D : 0) + (o_w ? K : 0);
-  if (n_theta != need) return -1;
+  const ThetaMap tm(D, K, optimize_mask);
+  if (n_theta != tm.n_theta()) return -1;
   for (int i = 0; i < n_theta; ++i)
     if (!std::isfinite(theta[i])) return -2;
-  int pos = 0;
-  if (o_mu) {
+  if (tm.o_mu())
     for (int i = 0; i < D * K; ++i) mu[i] = theta[i];
-    pos = D * K;
-  }
-  if (o_sg) {
-    for (int k = 0; k < K; ++k) sg[k] = std::exp(theta[pos + k]);
-    pos += K;
-  }
-  if (o_lm)
-    for (int d = 0; d < D; ++d) lm[d] = std::exp(theta[pos + d]);
-  if (o_w) {
-    const double* e = theta + (n_theta - K);
+  if (tm.o_sg())
+    for (int k = 0; k < K; ++k) sg[k] = std::exp(theta[tm.p_sg + k]);
+  if (tm.o_lm())
+    for (int d = 0; d < D; ++d) lm[d] = std::exp(theta[tm.p_lm + d]);
+  if (tm.o_w()) {
+    const double* e = theta + tm.p_w;
     double mx = e[0];
     for (int k = 1; k < K; ++k) mx = e[k] > mx ? e[k] : mx;
     for (int k = 0; k < K; ++k) {
@@ -452,11 +446,38 @@ int theta_to_arrays(int D, int K, const double* theta, int n_theta, int optimize
   const double nl = std::sqrt(s2 / D);
   for (int d = 0; d < D; ++d) lm[d] /= nl;
   for (int k = 0; k < K; ++k) sg[k] *= nl;
-  if (o_w) {
+  if (tm.o_w()) {
     double ws = 0.0;
     for (int k = 0; k < K; ++k) ws += w[k];
     for (int k = 0; k < K; ++k) w[k] /= ws;
   }
+  return 0;
+}
+
+void ctx_pack_aux(const vbmc_ctx* ctx, double* dst) {
+  for (const std::vector<double>* v : {&ctx->mu, &ctx->sigma, &ctx->lambd, &ctx->w, &ctx->eta}) dst = std::copy(v->begin(), v->end(), dst);
+}
+
+void ctx_unpack_aux(vbmc_ctx* ctx, const double* src) {
+  for (std::vector<double>* v : {&ctx->mu, &ctx->sigma, &ctx->lambd, &ctx->w, &ctx->eta}) {
+    std::copy(src, src + v->size(), v->begin());
+    src += v->size();
+  }
+}
+
+int resolve_row_slice(vbmc_ctx* ctx, const vbmc_elbo_opts* opts, const char* who, int64_t* row_begin, int64_t* row_count) {
+  const int64_t n_half = opts->ns_per_comp / 2;
+  *row_begin = opts->row_begin;
+  *row_count = opts->row_count;
+  if (*row_count < 0) {
+    *row_begin = n_half * ctx->rank / ctx->world;
+    *row_count = n_half * (ctx->rank + 1) / ctx->world - *row_begin;
+  }
+  if (*row_begin < 0 || *row_begin + *row_count > n_half) return vbmc_fail(ctx, VBMC_E_ARG, "%s: bad row slice", who);
+  if (opts->eps_mode == VBMC_EPS_RESIDENT &&
+      (!ctx->d_eps || ctx->eps_K != ctx->K || ctx->eps_D != ctx->D || ctx->eps_n_half != n_half ||
+       ctx->eps_row_begin != *row_begin || ctx->eps_rows != *row_count))
+    return vbmc_fail(ctx, VBMC_E_ARG, "%s: resident eps does not match the request", who);
   return 0;
 }
 
