@@ -13,6 +13,8 @@
 
 #include "common.h"
 #include "fastmath.h"
+#include "gp_dev.h"
+#include "mixture_dev.h"
 
 namespace {
 
@@ -67,23 +69,8 @@ __global__ __launch_bounds__(256) void acq_combine_kernel(
     double* __restrict__ var_tot_out) {
   const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= M) return;
-  // abstract_acq_fcn.py:82-97
-  double fsum = 0.0, vsum = 0.0;
-  for (int s = 0; s < S; ++s) {
-    fsum += fmu[(size_t)s * ld + m];
-    vsum += fs2[(size_t)s * ld + m];
-  }
-  const double f_bar = fsum / S, var_bar = vsum / S;
-  double var_f = 0.0;
-  if (S > 1) {
-    double q = 0.0;
-    for (int s = 0; s < S; ++s) {
-      const double t = fmu[(size_t)s * ld + m] - f_bar;
-      q += t * t;
-    }
-    var_f = q / (S - 1);
-  }
-  const double var_tot = var_f + var_bar;
+  double f_bar, var_tot;
+  gp_sample_moments(fmu, fs2, S, ld, m, f_bar, var_tot);
   acq[m] = acq_value(kind, f_bar, var_tot, dens[m], kind == VBMC_ACQ_NOISY ? sn2[m] : 0.0, y_max, tol_var);
   if (f_bar_out) f_bar_out[m] = f_bar;
   if (var_tot_out) var_tot_out[m] = var_tot;
@@ -98,8 +85,9 @@ __global__ __launch_bounds__(256) void acq_combine_kernel(
 struct AcqTail {
   const double* part;  // predict partials [S][2][ntiles][M]
   int64_t pstride;
-  int ntiles, M, D, P, S, mean_kind, kind, log_dens;
-  const double *hyp, *smeta, *xs, *mix, *sn2;
+  int ntiles, M, S, kind, log_dens;
+  PredView pv;  // (add_noise 0)
+  const double *mix, *sn2;
   MixLayout ml;
   double y_max, tol_var;
   double *acq, *f_bar, *var_tot;  // pinned host memory (device addresses); f_bar / var_tot nullable
@@ -108,40 +96,26 @@ struct AcqTail {
   int* cnt;  // zero between launches: workgroups that have stored their results
 };
 
+template <int DP>
 __global__ __launch_bounds__(256) void acq_tail_small_kernel(AcqTail a) {
   // wave = point: lanes over the GP samples for predict's finish, lanes over the components for the density
   __shared__ int s_last;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int m = blockIdx.x * 4 + wave, M = a.M, D = a.D, S = a.S;
+  const int m = blockIdx.x * 4 + wave, M = a.M, D = a.pv.D, S = a.S;
   if (m < M) {
-    // ---- predict's finish (gp.hip predict_finish_kernel), lane = GP sample ----
+    // ---- predict's finish, lane = GP sample ----
     double fmu = 0.0, fs2 = 0.0;
     if (lane < S) {
-      const int smp = lane;
-      const double* part = a.part + (size_t)smp * a.pstride;
+      const double* part = a.part + (size_t)lane * a.pstride;
       const double* fpart = part + (size_t)a.ntiles * M;
-      const double* hyp = a.hyp + (size_t)smp * a.P;
-      const bool chol = a.smeta[3 * smp] != 0.0;
-      const double sf2 = exp(2.0 * hyp[D]);
       double sv = 0.0, f = 0.0;
       for (int t = 0; t < a.ntiles; ++t) {
         sv += part[(size_t)t * M + m];
         f += fpart[(size_t)t * M + m];
       }
-      fs2 = fmax(chol ? sf2 - sv : sf2 + sv, 0.0);
-      double mean = 0.0;
-      const double* hm = hyp + D + 2;
-      if (a.mean_kind == VBMC_MEAN_CONST) mean = hm[0];
-      if (a.mean_kind == VBMC_MEAN_NEGQUAD) {
-        mean = hm[0];
-        for (int d = 0; d < D; ++d) {
-          const double t = (a.xs[m * D + d] - hm[1 + d]) * exp(-hm[1 + D + d]);
-          mean -= 0.5 * t * t;
-        }
-      }
-      fmu = mean + f;
+      predict_point_moments(a.pv, lane, m, sv, f, fmu, fs2);
     }
-    // ---- abstract_acq_fcn.py:82-97 ----
+    // ---- abstract_acq_fcn.py:82-97 (the samples sit in lanes: wave sums, a tree, not gp_sample_moments' running sums) ----
     const double f_bar = fm::wave_sum_dpp(fmu) / S, var_bar = fm::wave_sum_dpp(fs2) / S;
     double var_f = 0.0;
     if (S > 1) {
@@ -149,22 +123,17 @@ __global__ __launch_bounds__(256) void acq_tail_small_kernel(AcqTail a) {
       var_f = fm::wave_sum_dpp(t * t) / (S - 1);
     }
     const double var_tot = var_f + var_bar;
-    // ---- the mixture density at the point (variational_posterior.py:450-463), lane = component ----
-    const int K = a.ml.K;
-    const double* mup = a.mix + a.ml.o_mup;
-    const double* is2 = a.mix + a.ml.o_is2;
-    const double* wc = a.mix + a.ml.o_wc;
+    // ---- the mixture density at the point (mixture.hip's wave-per-point form), lane = first component ----
+    const MixGauss mg = mix_gauss(a.mix, a.ml);
     const double* ilam = a.mix + a.ml.o_ilam;
-    double y = 0.0;
-    for (int k = lane; k < K; k += 64) {
-      const double* mk = mup + k * D;
-      double d2 = 0.0;
-      for (int d = 0; d < D; ++d) {
-        const double u = a.xs[m * D + d] * ilam[d] - mk[d];
-        d2 = fma(u, u, d2);
-      }
-      y += wc[k] * fm::exp2_fast((-0.5 * 0x1.71547652b82fep+0 * is2[k]) * d2);
+    double xs[DP], g[DP];
+#pragma unroll
+    for (int d = 0; d < DP; ++d) {
+      xs[d] = (d < D) ? scaled_coord<false>(a.pv.xs[m * D + d], ilam[d]) : 0.0;
+      g[d] = 0.0;
     }
+    double y = 0.0;
+    mix_gauss_accumulate<DP, false, 64>(mg, xs, lane, y, g);
     y = fm::wave_sum_dpp(y);
     if (lane == 0) {
       const double dens = a.log_dens ? ((y == 0.0) ? -INFINITY : log(y)) : y;
@@ -205,25 +174,14 @@ extern "C" int vbmc_acq_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, int
   const GpState& g = ctx->gp;
   const int N = g.N, D = g.D, S = g.S;
   if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "acq_eval: D=%d > 32 not supported", D);
-  const int ntiles = (N + 63) / 64;
-  int64_t mb = ((int64_t)1 << 27) / ((int64_t)S * N);  // S kernel matrices of a batch under 1 GiB
-  mb = mb > 65536 ? 65536 : (mb < 64 ? 64 : (mb / 64) * 64);
-  if (M < mb) mb = M;
-  // scratch: xs | Ks [S] | part,fpart [S] | fmu[S] | fs2[S] | dens | sn2 | acq | f_bar | var_tot
-  const size_t ks_n = predict_ks_elems(S, mb, N);
-  const size_t need = align32((size_t)mb * D) + ks_n + 2 * (size_t)S * ntiles * mb + 2 * (size_t)S * mb + 5 * (size_t)mb;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, need);
+  // S kernel matrices of a batch under 1 GiB; extra: dens | sn2 | acq | f_bar | var_tot (the last three contiguous)
+  PredictPlan p;
+  int rc = predict_plan(ctx, M, (int64_t)1 << 27, (int64_t)S * N, 65536, 5, 3, p);
   if (rc) return rc;
-  rc = ensure_pinned(ctx, 3 * (size_t)mb);
-  if (rc) return rc;
-  double* d_xs = ctx->d_scratch;
-  double* d_Ks = d_xs + align32((size_t)mb * D);  // 256-byte aligned: read by 16-byte LDS-direct loads
-  double* d_part = d_Ks + ks_n;
-  double* d_fmu = d_part + 2 * (size_t)S * ntiles * mb;
-  double* d_fs2 = d_fmu + (size_t)S * mb;
-  double* d_dens = d_fs2 + (size_t)S * mb;
-  double* d_sn2 = d_dens + mb;
-  double* d_acq = d_sn2 + mb;  // acq | f_bar | var_tot, contiguous
+  const int64_t mb = p.mb;
+  const int ntiles = p.ntiles;
+  double *d_xs = p.xs, *d_Ks = p.Ks, *d_part = p.part, *d_fmu = p.fmu, *d_fs2 = p.fs2;
+  double *d_dens = p.extra, *d_sn2 = d_dens + mb, *d_acq = d_sn2 + mb;
   // ---- small batches (a CMA-ES population, a single point): the CPU writes the points straight into host-writable
   // device memory, the last kernel writes the results into pinned host memory and publishes a completion word that the
   // CPU polls: no copy calls and no stream synchronisation around ~30 us of kernels ----
@@ -255,15 +213,10 @@ extern "C" int vbmc_acq_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, int
     t.ntiles = ntiles;
     t.pstride = 2 * (int64_t)ntiles * m;
     t.M = (int)m;
-    t.D = D;
-    t.P = g.P;
     t.S = S;
-    t.mean_kind = g.mean_kind;
     t.kind = kind;
     t.log_dens = kind == VBMC_ACQ_LOG;
-    t.hyp = g.d_hyp;
-    t.smeta = g.d_smeta;
-    t.xs = x_dev;
+    t.pv = gp_pred_view(g, x_dev, 0);
     t.mix = ctx->d_mix;
     t.sn2 = ctx->d_acq_fg + 256 * 32;
     t.ml = ctx->ml;
@@ -275,7 +228,9 @@ extern "C" int vbmc_acq_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, int
     t.flag = ctx->hd_done + 7;
     t.seq = seq;
     t.cnt = ctx->d_done_cnt + 4;
-    hipLaunchKernelGGL(acq_tail_small_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream, t);
+#define CALL(DP) hipLaunchKernelGGL(acq_tail_small_kernel<DP>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream, t)
+    VBMC_DISPATCH_DP(D, CALL);
+#undef CALL
     HIP_TRY(ctx, hipGetLastError());
     const auto t0 = std::chrono::steady_clock::now();
     bool seen = false;

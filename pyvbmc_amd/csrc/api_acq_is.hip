@@ -19,10 +19,9 @@
 
 #include "common.h"
 #include "fastmath.h"
+#include "gp_dev.h"
 
 namespace {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 struct IsState {
   int64_t Na = 0;
@@ -46,58 +45,6 @@ __global__ __launch_bounds__(256) void se_cross_kernel(const double* __restrict_
     d2 = fma(t, t, d2);
   }
   K[idx] = exp(2.0 * hyp[D] - 0.5 * d2);
-}
-
-// C[M x NC] = A[M x KD] B[KD x NC], row-major, FP64 matrix cores; 64 x 64 tiles, 16-deep LDS panels
-// (the layout of predict_var_mfma_kernel in gp.hip without its triangular skip and row epilogue).
-constexpr int GT = 64, GK = 16, GLA = GK + 1, GLB = GT + 16;
-__global__ __launch_bounds__(256) void gemm_nn_mfma_kernel(const double* __restrict__ A,
-                                                           const double* __restrict__ B,
-                                                           double* __restrict__ C, int64_t M, int KD,
-                                                           int NC) {
-  __shared__ double sA[GT * GLA];
-  __shared__ double sB[GK * GLB];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wc = wave & 1, li = lane & 15, lk = lane >> 4;
-  const int64_t m0 = (int64_t)blockIdx.y * GT;
-  const int c0 = blockIdx.x * GT;
-  double4_t acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < KD; k0 += GK) {
-    for (int idx = tid; idx < GT * GK; idx += 256) {
-      const int r = idx / GK, kk = idx - r * GK;
-      const int64_t m = m0 + r;
-      sA[r * GLA + kk] = (m < M && k0 + kk < KD) ? A[(size_t)m * KD + k0 + kk] : 0.0;
-      const int kb = idx / GT, cc = idx - kb * GT;
-      sB[kb * GLB + cc] = (k0 + kb < KD && c0 + cc < NC) ? B[(size_t)(k0 + kb) * NC + c0 + cc] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kq = 0; kq < GK / 4; ++kq) {
-      const double a0 = sA[(wm * 32 + li) * GLA + kq * 4 + lk];
-      const double a1 = sA[(wm * 32 + 16 + li) * GLA + kq * 4 + lk];
-      const double b0 = sB[(kq * 4 + lk) * GLB + wc * 32 + li];
-      const double b1 = sB[(kq * 4 + lk) * GLB + wc * 32 + 16 + li];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t m = m0 + wm * 32 + mt * 16 + lk + 4 * r;
-        const int c = c0 + wc * 32 + ct * 16 + li;
-        if (m < M && c < NC) C[(size_t)m * NC + c] = acc[mt][ct][r];
-      }
 }
 
 // One wave per point m: acq_s[m] = logsumexp_a zz(m, a) for GP sample s.
@@ -159,20 +106,8 @@ __global__ void is_combine_kernel(const double* __restrict__ acq_s, int S, int64
                                   const double* __restrict__ fs2, double* __restrict__ var_tot) {
   const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= M) return;
-  {
-    double fsum = 0.0, vsum = 0.0;
-    for (int s = 0; s < S; ++s) {
-      fsum += fmu[(size_t)s * ld + m];
-      vsum += fs2[(size_t)s * ld + m];
-    }
-    const double f_bar = fsum / S;
-    double q = 0.0;
-    for (int s = 0; s < S; ++s) {
-      const double t = fmu[(size_t)s * ld + m] - f_bar;
-      q += t * t;
-    }
-    var_tot[m] = (S > 1 ? q / (S - 1) : 0.0) + vsum / S;
-  }
+  double f_bar;
+  gp_sample_moments(fmu, fs2, S, ld, m, f_bar, var_tot[m]);
   if (S == 1) {
     acq[m] = acq_s[m];
     return;
@@ -249,27 +184,13 @@ extern "C" int vbmc_acq_is_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, 
   const int N = g.N, D = g.D, S = g.S;
   const int64_t Na = st->Na;
   if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "acq_is_eval: D=%d > 32 not supported", D);
-  const int ntiles = (N + 63) / 64;
-  int64_t mb = ((int64_t)1 << 26) / ((int64_t)S * N + N + Na);
-  mb = mb > 16384 ? 16384 : (mb < 64 ? 64 : (mb / 64) * 64);
-  if (M < mb) mb = M;
-  // scratch: xs | Ks [S] | part [S] | fmu [S] | fs2 [S] | sn2 | Kx (mb x N) | T (mb x Na) | acq_s [S] | acq
-  const size_t ks_n = predict_ks_elems(S, mb, N);
-  const size_t need = align32((size_t)mb * D) + ks_n + 2 * (size_t)S * ntiles * mb + 2 * (size_t)S * mb +
-                      (size_t)mb + (size_t)mb * N + (size_t)mb * Na + (size_t)S * mb + 2 * (size_t)mb;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, need);
+  // extra: sn2 | Kx (mb x N) | T (mb x Na) | acq_s [S] | acq | var_tot
+  PredictPlan p;
+  int rc = predict_plan(ctx, M, (int64_t)1 << 26, (int64_t)S * N + N + Na, 16384, 1 + (size_t)N + Na + S + 2, 2, p);
   if (rc) return rc;
-  rc = ensure_pinned(ctx, 2 * (size_t)mb);
-  if (rc) return rc;
-  double* d_xs = ctx->d_scratch;
-  double* d_Ks = d_xs + align32((size_t)mb * D);  // 256-byte aligned: read by 16-byte LDS-direct loads
-  double* d_part = d_Ks + ks_n;
-  double* d_fmu = d_part + 2 * (size_t)S * ntiles * mb;
-  double* d_fs2 = d_fmu + (size_t)S * mb;
-  double* d_sn2 = d_fs2 + (size_t)S * mb;
-  double* d_Kx = d_sn2 + mb;
-  double* d_T = d_Kx + (size_t)mb * N;
-  double* d_as = d_T + (size_t)mb * Na;
+  const int64_t mb = p.mb;
+  double *d_xs = p.xs, *d_Ks = p.Ks, *d_part = p.part, *d_fmu = p.fmu, *d_fs2 = p.fs2;
+  double *d_sn2 = p.extra, *d_Kx = d_sn2 + mb, *d_T = d_Kx + (size_t)mb * N, *d_as = d_T + (size_t)mb * Na;
   double* d_acq = d_as + (size_t)S * mb;
   for (int64_t o = 0; o < M; o += mb) {
     const int64_t m = (M - o) < mb ? (M - o) : mb;
@@ -281,9 +202,8 @@ extern "C" int vbmc_acq_is_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, 
       const double* hyp = g.d_hyp + (size_t)s * g.P;
       hipLaunchKernelGGL(se_cross_kernel, dim3((unsigned)((m * N + 255) / 256)), dim3(256), 0, ctx->stream,
                          (const double*)d_xs, m, (const double*)g.d_X, N, D, hyp, d_Kx);
-      hipLaunchKernelGGL(gemm_nn_mfma_kernel, dim3((unsigned)((Na + GT - 1) / GT), (unsigned)((m + GT - 1) / GT)),
-                         dim3(256), 0, ctx->stream, (const double*)d_Kx,
-                         (const double*)(st->d + st->o_C + (size_t)s * N * Na), d_T, m, N, (int)Na);
+      rc = launch_gp_panel_product(ctx, d_Kx, st->d + st->o_C + (size_t)s * N * Na, d_T, m, N, (int)Na);
+      if (rc) return rc;
       const double* Xa = st->d + (st->per_sample ? (size_t)s * Na * D : 0);
       hipLaunchKernelGGL(is_reduce_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream,
                          (const double*)d_xs, m, D, Xa, Na, hyp, (const double*)d_T,

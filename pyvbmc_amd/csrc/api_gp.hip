@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "gp_dev.h"
 
 static const double kTiny = 2.220446049250313e-16;  // np.spacing(1)
 
@@ -301,78 +302,33 @@ extern "C" int vbmc_gp_predict(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, i
   const GpState& g = ctx->gp;
   const int N = g.N, D = g.D, S = g.S;
   if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "gp_predict: D=%d > 32 not supported", D);
-  const int ntiles = (N + 63) / 64;
   // batch so that the S kernel matrices of a batch stay under 1 GiB
-  int64_t mb = ((int64_t)1 << 27) / ((int64_t)S * N);
-  mb = mb > 65536 ? 65536 : (mb < 64 ? 64 : (mb / 64) * 64);
-  if (M < mb) mb = M;
-  // scratch: xs (mb*D) | Ks [S](mb*N) | part, fpart [S](2*ntiles*mb) | fmu [S][mb] | fs2 [S][mb]
-  const size_t ks_n = predict_ks_elems(S, mb, N);
-  const size_t need = align32((size_t)mb * D) + ks_n + 2 * (size_t)S * ntiles * mb + 2 * (size_t)S * mb;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, need);
+  PredictPlan p;
+  int rc = predict_plan(ctx, M, (int64_t)1 << 27, (int64_t)S * N, 65536, 0, 2 * (size_t)S, p);
   if (rc) return rc;
-  rc = ensure_pinned(ctx, 2 * (size_t)S * mb);
-  if (rc) return rc;
-  double* d_xs = ctx->d_scratch;
-  double* d_Ks = d_xs + align32((size_t)mb * D);  // 256-byte aligned: read by 16-byte LDS-direct loads
-  double* d_part = d_Ks + ks_n;
-  double* d_fmu = d_part + 2 * (size_t)S * ntiles * mb;
-  double* d_fs2 = d_fmu + (size_t)S * mb;
-  std::vector<double> mu_s, s2_s;
-  if (!separate_samples) {
-    mu_s.resize((size_t)mb * S);
-    s2_s.resize((size_t)mb * S);
-  }
+  const int64_t mb = p.mb;
   for (int64_t o = 0; o < M; o += mb) {
     const int64_t m = (M - o) < mb ? (M - o) : mb;
-    HIP_TRY(ctx, hipMemcpyAsync(d_xs, xs_MxD + o * D, sizeof(double) * m * D, hipMemcpyHostToDevice,
-                                ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(p.xs, xs_MxD + o * D, sizeof(double) * m * D, hipMemcpyHostToDevice, ctx->stream));
     // every hyper-parameter sample in the same three launches (grid.z = sample)
     if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-    rc = launch_gp_predict_all(ctx, m, d_xs, d_Ks, d_part, add_noise, d_fmu, d_fs2, mb);
+    rc = launch_gp_predict_all(ctx, m, p.xs, p.Ks, p.part, add_noise, p.fmu, p.fs2, mb);
     if (rc) return rc;
     if (ctx->timing) {
       HIP_TRY(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
       ctx->ev_valid[3] = true;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, d_fmu, sizeof(double) * 2 * S * mb, hipMemcpyDeviceToHost,
-                                ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, p.fmu, sizeof(double) * 2 * S * mb, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, stream_wait(ctx));
-    for (int s = 0; s < S; ++s) {
-      const double* hm = ctx->h_pinned + (size_t)s * mb;
-      const double* hv = ctx->h_pinned + (size_t)(S + s) * mb;
+    const double *hm = ctx->h_pinned, *hv = ctx->h_pinned + (size_t)S * mb;  // [S][mb] each
+    for (int64_t i = 0; i < m; ++i) {
       if (separate_samples) {
-        for (int64_t i = 0; i < m; ++i) {
-          fmu[(o + i) * S + s] = hm[i];
-          fs2[(o + i) * S + s] = hv[i];
+        for (int s = 0; s < S; ++s) {
+          fmu[(o + i) * S + s] = hm[(size_t)s * mb + i];
+          fs2[(o + i) * S + s] = hv[(size_t)s * mb + i];
         }
       } else {
-        for (int64_t i = 0; i < m; ++i) {
-          mu_s[(size_t)i * S + s] = hm[i];
-          s2_s[(size_t)i * S + s] = hv[i];
-        }
-      }
-    }
-    if (!separate_samples) {
-      // mean over s; fs2 = mean_s fs2 + var_s(fmu, ddof=1)
-      for (int64_t i = 0; i < m; ++i) {
-        double a = 0.0, v = 0.0;
-        for (int s = 0; s < S; ++s) {
-          a += mu_s[(size_t)i * S + s];
-          v += s2_s[(size_t)i * S + s];
-        }
-        a /= S;
-        v /= S;
-        if (S > 1) {
-          double q = 0.0;
-          for (int s = 0; s < S; ++s) {
-            const double t = mu_s[(size_t)i * S + s] - a;
-            q += t * t;
-          }
-          v += q / (S - 1);
-        }
-        fmu[o + i] = a;
-        fs2[o + i] = v;
+        gp_sample_moments(hm, hv, S, mb, i, fmu[o + i], fs2[o + i]);
       }
     }
   }

@@ -578,8 +578,43 @@ inline int predict_ld(int N) { return (N + 63) / 64 * 64; }
 inline size_t predict_ks_elems(int S, int64_t mb, int N) {
   return (size_t)S * (size_t)((mb + 63) / 64 * 64) * (size_t)predict_ld(N);
 }
+// The batch plan of an entry point that runs predict on M points: mb points per batch -- budget / cost doubles,
+// in whole 64-row tiles, at most cap and at most M -- and the scratch of one batch carved up as
+//   xs (mb x D) | Ks [S] (256-byte aligned: read by 16-byte LDS-direct loads) | part, fpart [S][ntiles][mb] |
+//   fmu [S][mb] | fs2 [S][mb] | extra (extra_per_point x mb, the caller's own),
+// with the device scratch and pinned_per_point x mb doubles of pinned memory ensured.
+struct PredictPlan {
+  int64_t mb = 0;
+  int ntiles = 0;
+  size_t total = 0;
+  double *xs = nullptr, *Ks = nullptr, *part = nullptr, *fmu = nullptr, *fs2 = nullptr, *extra = nullptr;
+};
+inline int predict_plan(vbmc_ctx* ctx, int64_t M, int64_t budget, int64_t cost, int64_t cap, size_t extra_per_point,
+                        size_t pinned_per_point, PredictPlan& p) {
+  const int S = ctx->gp.S, N = ctx->gp.N, D = ctx->gp.D;
+  p.ntiles = (N + 63) / 64;
+  int64_t mb = budget / cost;
+  mb = mb > cap ? cap : (mb < 64 ? 64 : (mb / 64) * 64);
+  p.mb = mb = M < mb ? M : mb;
+  const size_t n_xs = align32((size_t)mb * D), n_ks = predict_ks_elems(S, mb, N);
+  const size_t n_part = 2 * (size_t)S * p.ntiles * mb, n_mom = (size_t)S * mb;
+  p.total = n_xs + n_ks + n_part + 2 * n_mom + extra_per_point * (size_t)mb;
+  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, p.total);
+  if (rc) return rc;
+  rc = ensure_pinned(ctx, pinned_per_point * (size_t)mb);
+  if (rc) return rc;
+  p.xs = ctx->d_scratch;
+  p.Ks = p.xs + n_xs;
+  p.part = p.Ks + n_ks;
+  p.fmu = p.part + n_part;
+  p.fs2 = p.fmu + n_mom;
+  p.extra = p.fs2 + n_mom;
+  return 0;
+}
 int launch_gp_predict_products(vbmc_ctx* ctx, int64_t M, const double* d_xs, double* d_Ks, double* d_part,
                                const void* fin = nullptr, bool* fin_done = nullptr);
+// C (M x NC) = A (M x KD) B (KD x NC), row-major: the panel-product kernel of predict, store only
+int launch_gp_panel_product(vbmc_ctx* ctx, const double* d_A, const double* d_B, double* d_C, int64_t M, int KD, int NC);
 int launch_gp_predict_all(vbmc_ctx* ctx, int64_t M, const double* d_xs, double* d_Ks, double* d_part,
                           int add_noise, double* d_fmu, double* d_fs2, int64_t ld);
 // c[n][m] = |a_n - b_m|^2 (centred expansion, cross term on the FP64 matrix cores), optional

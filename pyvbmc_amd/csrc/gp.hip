@@ -15,6 +15,8 @@
 #include "common.h"
 #include <type_traits>
 #include "fastmath.h"
+#include "gp_dev.h"
+#include "mfma_tile.h"
 
 namespace {
 #if defined(DMA_ABL_TIMES) || defined(KSTAR_ABL_TIMES)
@@ -22,7 +24,8 @@ __device__ unsigned long long g_dma_times[8192 * 4];
 #endif
 
 constexpr int WAVES = 4;
-typedef double double4_t __attribute__((ext_vector_type(4)));
+using mfma_tile::double4_t;
+using mfma_tile::TS;
 
 __device__ inline double wave_sum(double v) {
   return fm::wave_sum_dpp(v);
@@ -236,29 +239,23 @@ __global__ __launch_bounds__(256) void gram_kernel(const double* __restrict__ Z,
 }
 
 // ---------------------------------------------------------------------------
-// predict, stage 2: T = A (M x N) * B (N x N) on the FP64 matrix cores, fused row epilogue
+// The panel product T = A (M x KD) * B (KD x NC) on the FP64 matrix cores (mfma_tile.h: 64 x 64 output tile per
+// workgroup, 16-deep LDS panels), with predict's stage 2 as a fused row epilogue where KD = NC = N:
 //   mode 0 (L_chol): B = L^-1 upper triangular; part[ct][m] = sum_{c in tile} T[m][c]^2
 //   mode 1         : B = L (full, symmetric);   part[ct][m] = sum_{c in tile} A[m][c] T[m][c]
-//   Cout != null   : also/only store T (used by the log-joint variance: V = Z L^-1 or Z L)
-// v_mfma_f64_16x16x4_f64: lane l holds A[i=l&15][k=l>>4], B[k=l>>4][j=l&15] and 4 results
-// C[row=(l>>4)+4r][col=l&15]  (cdna_hip_programming.md section 3, f64 layout).
-// Workgroup = 64 x 64 output tile, 4 waves x (2 x 2) MFMA tiles, 16-deep LDS panels:
-//   sA[64][17]  (row-major, +1 pad: the 16 rows of an A fragment hit distinct banks)
-//   sB[16][80]  (row stride = 32 banks mod 64: the 4 k-rows of a B fragment do not collide)
-// On gfx950 the FP64 MFMA peak equals the FP64 vector peak (78.6 TFLOP/s); what the
-// matrix instruction buys here is issue efficiency: 1024 FMAs per instruction and no
-// per-FMA operand traffic.
-constexpr int TS = 64, TKD = 16, LDA = TKD + 1, LDB = TS + 16;
+//   Cout != null   : also/only store T (the log-joint variance: V = Z L^-1 or Z L; the importance-sampled
+//                    acquisitions: K(Xs, X) C_tmp, mode 1 without part)
 // blockIdx.z (predict only): GP sample -- A, part advance by their strides, B is the sample's
 // L^-1 or L according to smeta[3z] (smeta == null: single problem, B and mode as given).
 __global__ __launch_bounds__(256) void predict_var_mfma_kernel(const double* __restrict__ A,
                                                                const double* __restrict__ B,
-                                                               int64_t M, int N, int mode,
+                                                               int64_t M, int KD, int NC, int mode,
                                                                double* __restrict__ part,
                                                                double* __restrict__ Cout,
                                                                const double* __restrict__ Bfull,
                                                                const double* __restrict__ smeta,
                                                                int64_t part_stride) {
+  using namespace mfma_tile;
   // XCD-aware tile order: the dispatcher places workgroup b (x fastest, then y, z) on XCD b % 8
   // (MI355X_MICROARCH.md, workgroup dispatch), each XCD has its own 4 MiB L2, and the nct column
   // tiles of one row tile all re-read the same rows of A.  Remap the linear id (bijectively) so
@@ -282,26 +279,22 @@ __global__ __launch_bounds__(256) void predict_var_mfma_kernel(const double* __r
   if (smeta) {
     const int z = tile_z;
     const bool chol = smeta[3 * z] != 0.0;
-    A += (size_t)z * M * N;
-    if (Cout) Cout += (size_t)z * M * N;
-    B = (chol ? B : Bfull) + (size_t)z * N * N;
+    A += (size_t)z * M * KD;
+    if (Cout) Cout += (size_t)z * M * NC;
+    B = (chol ? B : Bfull) + (size_t)z * KD * NC;
     mode = chol ? 0 : 1;
     part += (size_t)z * part_stride;
   }
   __shared__ double sA[TS * LDA];
   __shared__ double sB[TKD * LDB];
-  __shared__ double sRow[TS][2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wc = wave & 1;
-  const int li = lane & 15, lk = lane >> 4;
+  __shared__ double sRow[TS * 2];
+  const int tid = threadIdx.x;
+  const Lanes L = lanes(tid);
   const int64_t m0 = tile_r * TS;
   const int c0 = tile_c * TS;
-  double4_t acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  const int nmax = (mode == 0) ? min(N, c0 + TS) : N;  // upper-triangular B: n <= c
+  Acc acc;
+  zero(acc);
+  const int nmax = (mode == 0) ? min(KD, c0 + TS) : KD;  // upper-triangular B: n <= c
   // software pipeline: the next panel's global loads are issued into registers before the
   // MFMAs of the current panel and written to LDS afterwards, so HBM/L2 latency hides
   // behind the matrix work
@@ -314,10 +307,10 @@ __global__ __launch_bounds__(256) void predict_var_mfma_kernel(const double* __r
       const int r = idx / TKD, kk = idx - r * TKD;
       const int64_t m = m0 + r;
       const int n = n0 + kk;
-      ra[i] = (m < M && n < N) ? A[(size_t)m * N + n] : 0.0;
+      ra[i] = (m < M && n < KD) ? A[(size_t)m * KD + n] : 0.0;
       const int kb = idx / TS, cc = idx - kb * TS;
       const int nb = n0 + kb, c = c0 + cc;
-      rb[i] = (nb < N && c < N) ? B[(size_t)nb * N + c] : 0.0;
+      rb[i] = (nb < KD && c < NC) ? B[(size_t)nb * NC + c] : 0.0;
     }
   };
   auto stash = [&]() {
@@ -336,52 +329,28 @@ __global__ __launch_bounds__(256) void predict_var_mfma_kernel(const double* __r
     __syncthreads();
     if (n0 + TKD < nmax) fetch(n0 + TKD);
 #pragma unroll
-    for (int kq = 0; kq < TKD / 4; ++kq) {
-      const double a0 = sA[(wm * 32 + li) * LDA + kq * 4 + lk];
-      const double a1 = sA[(wm * 32 + 16 + li) * LDA + kq * 4 + lk];
-      const double b0 = sB[(kq * 4 + lk) * LDB + wc * 32 + li];
-      const double b1 = sB[(kq * 4 + lk) * LDB + wc * 32 + 16 + li];
-      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
+    for (int kq = 0; kq < TKD / 4; ++kq) step_panel(acc, L, sA, sB, kq);
     __syncthreads();
   }
-  if (Cout) {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t m = m0 + wm * 32 + mt * 16 + lk + 4 * r;
-          const int c = c0 + wc * 32 + ct * 16 + li;
-          if (m < M && c < N) Cout[(size_t)m * N + c] = acc[mt][ct][r];
-        }
-  }
-  if (!part) return;
-  // epilogue: per-row reduction over this wave's 32 columns, then over the two column waves
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = wm * 32 + mt * 16 + lk + 4 * r;
+  if (Cout)
+    walk(acc, L, [&](int row, int col, double t) {
       const int64_t m = m0 + row;
-      double v = 0.0;
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct) {
-        const int c = c0 + wc * 32 + ct * 16 + li;
-        if (c < N && m < M) {
-          const double t = acc[mt][ct][r];
-          v += (mode == 0) ? t * t : A[(size_t)m * N + c] * t;
-        }
-      }
-      v = fm::row16_sum_dpp(v);
-      if (li == 0) sRow[row][wc] = v;
-    }
+      const int c = c0 + col;
+      if (m < M && c < NC) Cout[(size_t)m * NC + c] = t;
+    }, [](int) {});
+  if (!part) return;
+  // epilogue (KD = NC): per-row reduction over the tile's columns
+  double v = 0.0;
+  walk(acc, L, [&](int row, int col, double t) {
+    const int64_t m = m0 + row;
+    const int c = c0 + col;
+    if (c < NC && m < M) v += (mode == 0) ? t * t : A[(size_t)m * KD + c] * t;
+  }, [&](int row) {
+    row_sum_put(sRow, L, row, v);
+    v = 0.0;
+  });
   __syncthreads();
-  if (tid < TS && m0 + tid < M) part[(size_t)tile_c * M + m0 + tid] = sRow[tid][0] + sRow[tid][1];
+  if (tid < TS && m0 + tid < M) part[(size_t)tile_c * M + m0 + tid] = row_sum(sRow, tid);
 }
 
 // ---------------------------------------------------------------------------
@@ -407,38 +376,14 @@ __global__ __launch_bounds__(256) void predict_var_mfma_kernel(const double* __r
 //   * column tiles are folded so that every workgroup has (nearly) the same number of panels
 //     (see the kernel); a workgroup's items are one panel sequence through the pipeline.
 // One barrier per panel; the DMA of panel i+1 is in flight during the matrix work of panel i.
-// predict, stage 3 for one point (also predict_finish_kernel's body): fmu = mean(x*) + the stage-1 partial means,
-// fs2 = max(0, sf^2 -/+ the stage-2 partial row sums) (+ noise); s and f are those sums.
+// predict, stage 3: predict_point_moments (gp_dev.h) of a point's summed partials, stored as fmu / fs2 [S][ld]
 struct PredFin {
   int* tick = nullptr;  // non-null: predict_var_dma_kernel finishes the points itself (arrival ticket per row tile)
-  const double* hyp_all = nullptr;
-  const double* smeta = nullptr;
-  const double* xs = nullptr;
+  PredView v;
   double* fmu = nullptr;
   double* fs2 = nullptr;
   int64_t ld = 0;
-  int D = 0, P = 0, mean_kind = 0, add_noise = 0;
 };
-__device__ __forceinline__ void predict_point_finish(const PredFin& fin, int smp, int64_t m, double s, double f) {
-  const double* hyp = fin.hyp_all + (size_t)smp * fin.P;
-  const int D = fin.D;
-  const bool chol = fin.smeta[3 * smp] != 0.0;
-  const double sf2 = exp(2.0 * hyp[D]);
-  const double add = fin.add_noise ? exp(2.0 * hyp[D + 1]) * fin.smeta[3 * smp + 1] : 0.0;
-  fin.fs2[(size_t)smp * fin.ld + m] = fmax(chol ? sf2 - s : sf2 + s, 0.0) + add;
-  // mean function at x* (variational_optimization.py:1383-1392 layout)
-  double mean = 0.0;
-  const double* hm = hyp + D + 2;
-  if (fin.mean_kind == VBMC_MEAN_CONST) mean = hm[0];
-  if (fin.mean_kind == VBMC_MEAN_NEGQUAD) {
-    mean = hm[0];
-    for (int d = 0; d < D; ++d) {
-      const double t = (fin.xs[m * D + d] - hm[1 + d]) * exp(-hm[1 + D + d]);
-      mean -= 0.5 * t * t;
-    }
-  }
-  fin.fmu[(size_t)smp * fin.ld + m] = mean + f;
-}
 
 constexpr int DK = 32;                        // panel depth
 constexpr int DMA_STAGE = 2 * TS * DK * 8;    // bytes of one stage: A panel, then B panel
@@ -595,10 +540,7 @@ __global__ __launch_bounds__(256, 2) void predict_var_dma_kernel(const double* _
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[cur][0][h], fb[cur][h][0], acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[cur][0][h], fb[cur][h][1], acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[cur][1][h], fb[cur][h][0], acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[cur][1][h], fb[cur][h][1], acc[1][1], 0, 0, 0);
+        mfma_tile::step(acc, fa[cur][0][h], fa[cur][1][h], fb[cur][h][0], fb[cur][h][1]);
 #ifndef DMA_ABL_NODMA
         if constexpr (decltype(prefetch)::value) dma(2 * t + h, stage ^ 1, ag, bg);
 #endif
@@ -663,7 +605,11 @@ __global__ __launch_bounds__(256, 2) void predict_var_dma_kernel(const double* _
         sv += __hip_atomic_load(pz + (size_t)t * M + m0 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         fv += __hip_atomic_load(pz + (size_t)(nct + t) * M + m0 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // stage 1's partial means
       }
-      predict_point_finish(fin, z, m0 + tid, sv, fv);
+      // (into registers, then stored: handing over the addresses costs this kernel two VGPRs)
+      double mu, s2;
+      predict_point_moments(fin.v, z, m0 + tid, sv, fv, mu, s2);
+      fin.fmu[(size_t)z * fin.ld + m0 + tid] = mu;
+      fin.fs2[(size_t)z * fin.ld + m0 + tid] = s2;
     }
   };
   {
@@ -796,17 +742,12 @@ __global__ __launch_bounds__(64 * NW) void predict_var_small_kernel(const double
 // Both sets are shifted by the column means of X first, as the reference's _sq_dist shifts by
 // a common mean.  Cancellation: |d2 error| <= ~1e-16 (|a|^2+|b|^2), i.e. a relative error of
 // the same size in Ks -- far inside the 1e-10 budget of the predictive variance.
-// LDS row stride of the staged coordinate tiles.  The MFMA fragments are read as ds_read_b64 with lane =
-// (row li = lane & 15, k-index lk = lane >> 4): a 32-lane group covers li = 0..15, lk = 0..1, dword bank
-// (2 (stride li + lk)) mod 64.  An ODD stride (33, rounds 1-2) always puts some (li, lk = 1) on the
-// bank of another (li', lk = 0) -- 38 % of the kernel's LDS cycles were conflict cycles (PMC, r02);
-// stride = 2 mod 4 gives banks 4 li + 2 lk: 32 distinct ones.
-constexpr int KDP = 32 + 2;
 __global__ __launch_bounds__(256) void predict_kstar_mfma_kernel(
     const double* __restrict__ X, const double* __restrict__ xs, const double* __restrict__ alpha,
     const double* __restrict__ sW, const double* __restrict__ hyp, const double* __restrict__ cen,
     const double* __restrict__ smeta, int P, int N, int D, int64_t M, double* __restrict__ Ks,
     int lda, int64_t ks_stride, double* __restrict__ fpart, int64_t part_stride, int* __restrict__ tick) {
+  using namespace mfma_tile;
   // tick (may be null): arrival tickets of predict_var_dma_kernel's fused finish, one per row tile and sample, zeroed here
   if (tick != nullptr && blockIdx.x == 0 && threadIdx.x == 0) tick[(size_t)blockIdx.z * gridDim.y + blockIdx.y] = 0;
   // blockIdx.z = GP hyper-parameter sample: all S samples in one launch.  Ks: row stride lda,
@@ -827,10 +768,9 @@ __global__ __launch_bounds__(256) void predict_kstar_mfma_kernel(
   __shared__ double sAm[TS * KDP];  // [64 m][d]
   __shared__ double sBn[TS * KDP];  // [64 n][d]
   __shared__ double sA2[TS], sB2[TS], sAl[TS], sSc[TS];
-  __shared__ double sF[TS][2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 15, lk = lane >> 4;
+  __shared__ double sF[TS * 2];
+  const int tid = threadIdx.x;
+  const Lanes L = lanes(tid);
   const int64_t m0 = (int64_t)blockIdx.y * TS;
   const int n0 = blockIdx.x * TS;
   const int DQ = (D + 3) / 4;  // k-steps of 4
@@ -886,53 +826,34 @@ __global__ __launch_bounds__(256) void predict_kstar_mfma_kernel(
 #ifdef KSTAR_ABL_TIMES
   const unsigned long long ks_t1 = wall_clock64();
 #endif
-  double4_t acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  for (int kq = 0; kq < DQ; ++kq) {
-    const double a0 = sAm[(wm * 32 + li) * KDP + kq * 4 + lk];
-    const double a1 = sAm[(wm * 32 + 16 + li) * KDP + kq * 4 + lk];
-    const double b0 = sBn[(wn * 32 + li) * KDP + kq * 4 + lk];
-    const double b1 = sBn[(wn * 32 + 16 + li) * KDP + kq * 4 + lk];
-    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-  }
+  Acc acc;
+  zero(acc);
+  for (int kq = 0; kq < DQ; ++kq) step_rows(acc, L, sAm, sBn, KDP, kq);
 #ifdef KSTAR_ABL_TIMES
   const unsigned long long ks_t2 = wall_clock64();
 #endif
   // epilogue: kernel values, store, partial means
   const double l2sf2 = 2.0 * hyp[D] * 0x1.71547652b82fep+0;  // log2(sf^2)
   const double c = -0.5 * 0x1.71547652b82fep+0;              // -log2(e)/2
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = wm * 32 + mt * 16 + lk + 4 * r;
-      const int64_t m = m0 + row;
-      double f = 0.0;
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        const int col = wn * 32 + nt * 16 + li;
-        const int n = n0 + col;
-        const double d2 = fmax(fma(-2.0, acc[mt][nt][r], sA2[row] + sB2[col]), 0.0);
-        const double kv = fm::exp2_fast(fma(c, d2, l2sf2));
+  double f = 0.0;
+  walk(acc, L, [&](int row, int col, double ab) {
+    const int64_t m = m0 + row;
+    const int n = n0 + col;
+    const double d2 = fmax(fma(-2.0, ab, sA2[row] + sB2[col]), 0.0);
+    const double kv = fm::exp2_fast(fma(c, d2, l2sf2));
 #ifndef KSTAR_ABL_NOSTORE
-        // (sSc is 0 beyond N.)  Streaming store: the 8 N M bytes of K* are read next by another
-        // kernel on other XCDs; written through now they overlap with this kernel's arithmetic
-        // instead of being flushed from the L2s at its end.
-        if (m < M && n < lda) __builtin_nontemporal_store(kv * sSc[col], Ks + (size_t)m * lda + n);
+    // (sSc is 0 beyond N.)  Streaming store: the 8 N M bytes of K* are read next by another
+    // kernel on other XCDs; written through now they overlap with this kernel's arithmetic
+    // instead of being flushed from the L2s at its end.
+    if (m < M && n < lda) __builtin_nontemporal_store(kv * sSc[col], Ks + (size_t)m * lda + n);
 #endif
-        f = fma(kv, sAl[col], f);  // alpha is 0 beyond N
-      }
-      f = fm::row16_sum_dpp(f);
-      if (li == 0) sF[row][wn] = f;
-    }
+    f = fma(kv, sAl[col], f);  // alpha is 0 beyond N
+  }, [&](int row) {
+    row_sum_put(sF, L, row, f);
+    f = 0.0;
+  });
   __syncthreads();
-  if (tid < TS && m0 + tid < M) fpart[(size_t)blockIdx.x * M + m0 + tid] = sF[tid][0] + sF[tid][1];
+  if (tid < TS && m0 + tid < M) fpart[(size_t)blockIdx.x * M + m0 + tid] = row_sum(sF, tid);
 #ifdef KSTAR_ABL_TIMES
   if (threadIdx.x == 0 && kb_ < 2048) {
     g_dma_times[kb_ * 4 + 1] = wall_clock64();
@@ -958,14 +879,14 @@ __global__ __launch_bounds__(256) void sq_dist_mfma_kernel(
     const double* __restrict__ A, const double* __restrict__ B, const double* __restrict__ cen,
     int64_t NA, int NB, int D, double* __restrict__ C, double* __restrict__ pmin,
     int* __restrict__ pidx) {
+  using namespace mfma_tile;
   __shared__ double sAm[TS * KDP];
   __shared__ double sBn[TS * KDP];
   __shared__ double sA2[TS], sB2[TS];
   __shared__ double sMin[TS][2];
   __shared__ int sIdx[TS][2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int li = lane & 15, lk = lane >> 4;
+  const int tid = threadIdx.x;
+  const Lanes L = lanes(tid);
   const int64_t m0 = (int64_t)blockIdx.y * TS;
   const int n0 = blockIdx.x * TS;
   const int DQ = (D + 3) / 4;
@@ -988,64 +909,47 @@ __global__ __launch_bounds__(256) void sq_dist_mfma_kernel(
     sB2[tid] = b2;
   }
   __syncthreads();
-  double4_t acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  for (int kq = 0; kq < DQ; ++kq) {
-    const double a0 = sAm[(wm * 32 + li) * KDP + kq * 4 + lk];
-    const double a1 = sAm[(wm * 32 + 16 + li) * KDP + kq * 4 + lk];
-    const double b0 = sBn[(wn * 32 + li) * KDP + kq * 4 + lk];
-    const double b1 = sBn[(wn * 32 + 16 + li) * KDP + kq * 4 + lk];
-    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-  }
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = wm * 32 + mt * 16 + lk + 4 * r;
-      const int64_t m = m0 + row;
-      double best = INFINITY;
-      int bidx = 0x7fffffff;
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        const int col = wn * 32 + nt * 16 + li;
-        const int n = n0 + col;
-        // the reference's association: |a|^2 + (|b|^2 - 2 a.b)
-        const double d2 = fmax(sA2[row] + fma(-2.0, acc[mt][nt][r], sB2[col]), 0.0);
-        if (m < NA && n < NB) {
-          if (C) C[(size_t)m * NB + n] = d2;
-          if (d2 < best) {  // nt ascending: ties keep the smaller column
-            best = d2;
-            bidx = n;
-          }
-        }
-      }
-      // first minimum over the 16 lanes that share this row
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) {
-        const double ob = __shfl_xor(best, off, 64);
-        const int oi = __shfl_xor(bidx, off, 64);
-        if (ob < best || (ob == best && oi < bidx)) {
-          best = ob;
-          bidx = oi;
-        }
-      }
-      if (li == 0) {
-        sMin[row][wn] = best;
-        sIdx[row][wn] = bidx;
+  Acc acc;
+  zero(acc);
+  for (int kq = 0; kq < DQ; ++kq) step_rows(acc, L, sAm, sBn, KDP, kq);
+  double best = INFINITY;
+  int bidx = 0x7fffffff;
+  walk(acc, L, [&](int row, int col, double ab) {
+    const int64_t m = m0 + row;
+    const int n = n0 + col;
+    // the reference's association: |a|^2 + (|b|^2 - 2 a.b)
+    const double d2 = fmax(sA2[row] + fma(-2.0, ab, sB2[col]), 0.0);
+    if (m < NA && n < NB) {
+      if (C) C[(size_t)m * NB + n] = d2;
+      if (d2 < best) {  // columns ascending: ties keep the smaller column
+        best = d2;
+        bidx = n;
       }
     }
+  }, [&](int row) {
+    // first minimum over the 16 lanes that share this row
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+      const double ob = __shfl_xor(best, off, 64);
+      const int oi = __shfl_xor(bidx, off, 64);
+      if (ob < best || (ob == best && oi < bidx)) {
+        best = ob;
+        bidx = oi;
+      }
+    }
+    if (L.li == 0) {
+      sMin[row][L.wc] = best;
+      sIdx[row][L.wc] = bidx;
+    }
+    best = INFINITY;
+    bidx = 0x7fffffff;
+  });
   if (!pmin) return;
   __syncthreads();
   if (tid < TS && m0 + tid < NA) {
     double best = sMin[tid][0];
     int bidx = sIdx[tid][0];
-    if (sMin[tid][1] < best) {  // columns of wn = 1 are larger: ties keep wn = 0
+    if (sMin[tid][1] < best) {  // columns of wc = 1 are larger: ties keep wc = 0
       best = sMin[tid][1];
       bidx = sIdx[tid][1];
     }
@@ -1084,7 +988,7 @@ __global__ void predict_finish_kernel(const double* __restrict__ part_all, int64
     s += part[(size_t)t * M + m];
     f += fpart[(size_t)t * M + m];
   }
-  predict_point_finish(fin, smp, m, s, f);
+  predict_point_moments(fin.v, smp, m, s, f, fin.fmu[(size_t)smp * fin.ld + m], fin.fs2[(size_t)smp * fin.ld + m]);
 }
 
 }  // namespace
@@ -1126,7 +1030,7 @@ int launch_gp_var(vbmc_ctx* ctx, const double* d_Z, double* d_V, double* d_Q) {
   // V = Z L^-1 (upper-triangular skip) or Z L on the FP64 matrix cores, then the K x K Gram
   // matrix; every GP sample in the same two launches
   hipLaunchKernelGGL(predict_var_mfma_kernel, dim3((N + TS - 1) / TS, (K + TS - 1) / TS, S), dim3(256), 0,
-                     ctx->stream, d_Z, (const double*)g.d_Linv, (int64_t)K, N, 0, (double*)nullptr, d_V,
+                     ctx->stream, d_Z, (const double*)g.d_Linv, (int64_t)K, N, N, 0, (double*)nullptr, d_V,
                      (const double*)g.d_L, (const double*)g.d_smeta, (int64_t)0);
   hipLaunchKernelGGL(gram_kernel, dim3((K * K + WAVES - 1) / WAVES, S), dim3(256), 0, ctx->stream, d_Z,
                      (const double*)d_V, (const double*)ctx->d_mix, ctx->ml, (const double*)g.d_hyp, g.P, N,
@@ -1237,7 +1141,7 @@ int launch_gp_predict_products(vbmc_ctx* ctx, int64_t M, const double* d_xs, dou
                        (const double*)g.d_smeta, pstride);
   } else {
     hipLaunchKernelGGL(predict_var_mfma_kernel, grid, dim3(256), 0, ctx->stream, (const double*)d_Ks,
-                       (const double*)g.d_Linv, M, N, 0, d_part, (double*)nullptr, (const double*)g.d_L,
+                       (const double*)g.d_Linv, M, N, N, 0, d_part, (double*)nullptr, (const double*)g.d_L,
                        (const double*)g.d_smeta, pstride);
   }
   if (ctx->timing >= 2) {
@@ -1255,26 +1159,29 @@ int launch_gp_predict_products(vbmc_ctx* ctx, int64_t M, const double* d_xs, dou
 int launch_gp_predict_all(vbmc_ctx* ctx, int64_t M, const double* d_xs, double* d_Ks, double* d_part,
                           int add_noise, double* d_fmu, double* d_fs2, int64_t ld) {
   const GpState& g = ctx->gp;
-  const int N = g.N, D = g.D, S = g.S;
+  const int N = g.N, S = g.S;
   const int ntiles = (N + TS - 1) / TS;
   const int64_t pstride = 2 * (int64_t)ntiles * M;
   PredFin fin;
-  fin.hyp_all = g.d_hyp;
-  fin.smeta = g.d_smeta;
-  fin.xs = d_xs;
+  fin.v = gp_pred_view(g, d_xs, add_noise);
   fin.fmu = d_fmu;
   fin.fs2 = d_fs2;
   fin.ld = ld;
-  fin.D = D;
-  fin.P = g.P;
-  fin.mean_kind = g.mean_kind;
-  fin.add_noise = add_noise;
   bool done = false;
   const int rc = launch_gp_predict_products(ctx, M, d_xs, d_Ks, d_part, &fin, &done);
   if (rc) return rc;
   if (!done)
     hipLaunchKernelGGL(predict_finish_kernel, dim3((unsigned)((M + 255) / 256), S), dim3(256), 0, ctx->stream,
                        (const double*)d_part, pstride, ntiles, M, fin);
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
+// C (M x NC) = A (M x KD) B (KD x NC), row-major, all of B: the panel product alone
+int launch_gp_panel_product(vbmc_ctx* ctx, const double* d_A, const double* d_B, double* d_C, int64_t M, int KD, int NC) {
+  hipLaunchKernelGGL(predict_var_mfma_kernel, dim3((NC + TS - 1) / TS, (unsigned)((M + TS - 1) / TS)), dim3(256), 0,
+                     ctx->stream, d_A, d_B, M, KD, NC, 1, (double*)nullptr, d_C, (const double*)nullptr,
+                     (const double*)nullptr, (int64_t)0);
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }

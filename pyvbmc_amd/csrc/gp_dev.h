@@ -1,0 +1,61 @@
+// GP predict's finish for one point and the moments over the GP hyper-parameter samples: the single definition of
+// both.  gp.hip's predict kernels, the acquisition kernels and vbmc_gp_predict's host loop call these.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "common.h"
+
+// what the finish of a point reads: every sample's hyper-parameters [S][P], smeta [S][3], the points [M][D]
+struct PredView {
+  const double* hyp_all = nullptr;
+  const double* smeta = nullptr;
+  const double* xs = nullptr;
+  int D = 0, P = 0, mean_kind = 0, add_noise = 0;
+};
+
+inline PredView gp_pred_view(const GpState& g, const double* d_xs, int add_noise) {
+  return {g.d_hyp, g.d_smeta, d_xs, g.D, g.P, g.mean_kind, add_noise};
+}
+
+// predict, stage 3 for point m under GP sample smp: fmu = mean(x*) + f, fs2 = max(0, sf^2 -/+ s) (+ noise), with
+// s / f the sums of the stage-2 partial row sums / the stage-1 partial means.
+__device__ __forceinline__ void predict_point_moments(const PredView& v, int smp, int64_t m, double s, double f,
+                                                      double& fmu, double& fs2) {
+  const double* hyp = v.hyp_all + (size_t)smp * v.P;
+  const int D = v.D;
+  const bool chol = v.smeta[3 * smp] != 0.0;
+  const double sf2 = exp(2.0 * hyp[D]);
+  const double add = v.add_noise ? exp(2.0 * hyp[D + 1]) * v.smeta[3 * smp + 1] : 0.0;
+  fs2 = fmax(chol ? sf2 - s : sf2 + s, 0.0) + add;
+  // mean function at x* (variational_optimization.py:1383-1392 layout)
+  double mean = 0.0;
+  const double* hm = hyp + D + 2;
+  if (v.mean_kind == VBMC_MEAN_CONST) mean = hm[0];
+  if (v.mean_kind == VBMC_MEAN_NEGQUAD) {
+    mean = hm[0];
+    for (int d = 0; d < D; ++d) {
+      const double t = (v.xs[m * D + d] - hm[1 + d]) * exp(-hm[1 + D + d]);
+      mean -= 0.5 * t * t;
+    }
+  }
+  fmu = mean + f;
+}
+
+// abstract_acq_fcn.py:82-97 / gpyreg predict without separate_samples, from fmu[s * ld + m], fs2[s * ld + m]:
+// f_bar = mean_s fmu, var_tot = var_s(fmu, ddof = 1) + mean_s fs2.  Sums over s ascending, then / S, q / (S - 1).
+__host__ __device__ inline void gp_sample_moments(const double* fmu, const double* fs2, int S, int64_t ld, int64_t m,
+                                                  double& f_bar, double& var_tot) {
+  double fsum = 0.0, vsum = 0.0;
+  for (int s = 0; s < S; ++s) {
+    fsum += fmu[(size_t)s * ld + m];
+    vsum += fs2[(size_t)s * ld + m];
+  }
+  f_bar = fsum / S;
+  double q = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const double t = fmu[(size_t)s * ld + m] - f_bar;
+    q += t * t;
+  }
+  var_tot = (S > 1 ? q / (S - 1) : 0.0) + vsum / S;
+}
