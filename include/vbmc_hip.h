@@ -559,6 +559,34 @@ int vbmc_acq_is_set(vbmc_ctx* ctx, int64_t Na, const double* Xa, int per_sample_
 int vbmc_acq_is_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, const double* sn2_M, double u,
                      double* acq_M, double* var_tot_M /* nullable: for the variance regularisation */);
 
+/* Preparing that state on the device: vbmc/active_importance_sampling.py, for the GP of vbmc_set_gp.
+ *
+ * vbmc_is_proposal is active_sample_proposal_pdf (:317-390) for Na points of the transformed space:
+ * gp.predict(Xa, separate_samples=True) (:351); the log density of the smoothed posterior -- the mixture
+ * (K2, mu2, sigma2, lambd2, w2), e.g. the 4 K components step 1 builds (:126-137) -- plus log w_vp (:361-366);
+ * the box-uniform mixture around the training points, half-widths rect_delta_D, strict inequalities (:372-378);
+ * their max-shifted log-sum-exp and ln_w = ln_y - l_pdf (:380-388), ln_y = f_mu when ln_y_is_fmu (IMIQR's
+ * is_log_base) else 0 (VIQR's).  w_vp = 0: no mixture needed (NULLs); w_vp = 1: no boxes (rect_delta_D NULL),
+ * ln_w = ln_y - lpdf directly.  Outputs lnw_NaxS and fs2_NaxS, (Na, S) as the reference returns them.
+ * *invalid_out = 1 when some point lies in no box and has zero density: the reference raises
+ * ValueError("Invalid value.") there (:381-382).  D <= 32 (VBMC_E_UNSUP above).
+ *
+ * vbmc_is_box_sample draws n_box box-uniform proposals (:164-168) from the Philox stream 5 of csrc/sample.hip:
+ * sample n picks training point floor(u N) and adds (2 u_d - 1) rect_delta_d in every dimension.
+ *
+ * vbmc_acq_is_build is vbmc_acq_is_set with step 3 (:264-308) done on the device: from Xa (Na x D, or
+ * S x Na x D with per_sample_xa), f_s2 (Na x S) and ln_weights (S x Na, NULL for VIQR) it forms, per GP sample,
+ * K_Xa_X[s] = k_s(Xa, X) (:287) and C_tmp[s] = (L'L)^-1 K(X, Xa) / sn2_eff (:294-304, two products against
+ * the resident L^-1) or L K(X, Xa) (:306), straight into the resident state vbmc_acq_is_eval reads.
+ * K_out_SxNaxN / C_out_SxNxNa (nullable) receive copies, as the reference's dict holds them. */
+int vbmc_is_proposal(vbmc_ctx* ctx, int64_t Na, const double* Xa_NaxD, int K2, const double* mu2_KxD,
+                     const double* sigma2_K, const double* lambd2_D, const double* w2_K, double w_vp,
+                     const double* rect_delta_D, int ln_y_is_fmu, double* lnw_NaxS, double* fs2_NaxS,
+                     int* invalid_out);
+int vbmc_is_box_sample(vbmc_ctx* ctx, int64_t n_box, uint64_t seed, const double* rect_delta_D, double* x_NboxxD);
+int vbmc_acq_is_build(vbmc_ctx* ctx, int64_t Na, const double* Xa, int per_sample_xa, const double* fs2a_NaxS,
+                      const double* lnw_SxNa, double* K_out_SxNaxN, double* C_out_SxNxNa);
+
 /* AbstractAcqFcn._sq_dist (acquisition_functions/abstract_acq_fcn.py:195-222):
  * c[i][j] = max(|a_i - mu|^2 + |b_j - mu|^2 - 2 (a_i - mu).(b_j - mu), 0), mu the common
  * mean the reference subtracts first.  argmin_n (nullable) = np.argmin(c, axis=1), the

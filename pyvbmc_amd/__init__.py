@@ -8,8 +8,17 @@ hot path, behind the reference's own Python names.
 Host code is plain Python calling hand-written HIP kernels through the C ABI of
 libvbmc_hip.so (include/vbmc_hip.h) via ctypes.  No PyTorch, no CPU fallback.
 """
-from .dropin import patch, unpatch  # noqa: F401  (pyvbmc_amd.patch(vo): the whole drop-in in one call)
+from .active_importance_sampling import (  # noqa: F401
+    active_importance_sampling,
+    active_sample_proposal_pdf,
+    fess,
+    get_mcmc_opts,
+    renormalize_weights,
+)
+from .dropin import patch, patch_active_sampling, unpatch, unpatch_active_sampling  # noqa: F401  (pyvbmc_amd.patch(vo): the whole drop-in in one call)
 from .entropy import entlb_vbmc, entmc_vbmc  # noqa: F401
 from .variational_posterior import VariationalPosterior  # noqa: F401
 
-__all__ = ["VariationalPosterior", "entmc_vbmc", "entlb_vbmc", "patch", "unpatch"]
+__all__ = ["VariationalPosterior", "entmc_vbmc", "entlb_vbmc", "patch", "unpatch", "active_importance_sampling",
+           "active_sample_proposal_pdf", "fess", "get_mcmc_opts", "renormalize_weights", "patch_active_sampling",
+           "unpatch_active_sampling"]

@@ -13,8 +13,10 @@ The two importance-sampled members for noisy targets, ``AcqFcnVIQR`` and ``AcqFc
 (reference acq_fcn_viqr.py, acq_fcn_imiqr.py), evaluate through ``vbmc_acq_is_set`` /
 ``vbmc_acq_is_eval`` (csrc/api_acq_is.hip): the importance state the reference prepares once per
 active-sampling round (``optim_state["active_importance_sampling"]``) is uploaded once and stays
-in HBM while the acquisition is evaluated thousands of times.  Preparing that state
-(``active_importance_sampling``) is the reference's own code and out of scope here.
+in HBM while the acquisition is evaluated thousands of times.  Preparing that state is
+``pyvbmc_amd.active_importance_sampling`` (the mirror of the reference's function of that name): it forms
+``K_Xa_X`` / ``C_tmp`` on the device and leaves them installed in the context (``vbmc_acq_is_build``), so a dict it
+returned is recognised here and nothing is uploaded; a dict from the reference is uploaded as before.
 """
 import ctypes as C
 
@@ -145,6 +147,13 @@ class AcqFcnNoisy(AbstractAcqFcn):
     _kind = ACQ_NOISY
 
 
+def _is_state_key(ais, ctx):
+    """(key, keyed arrays) of an importance-state dict: every array the device state is built from, and the
+    content-aware key of the GP that ``upload_gp`` left in the context."""
+    parts = tuple(ais.get(k) for k in ("X", "f_s2", "ln_weights", "C_tmp", "K_Xa_X"))
+    return (id(ais),) + tuple(id(a) for a in parts) + tuple(ctx.__dict__.get("_gp_key") or ()), parts
+
+
 class _QuantileAcq(AbstractAcqFcn):
     """Shared parts of AcqFcnVIQR / AcqFcnIMIQR (reference acq_fcn_viqr.py, acq_fcn_imiqr.py)."""
 
@@ -187,18 +196,25 @@ class _QuantileAcq(AbstractAcqFcn):
         # every array the device state is built from, and the content-aware key of the GP that
         # upload_gp (called just before) left in the context: a posterior record replaced in place
         # (active_importance_sampling.py:207-209) or a re-bound ais["C_tmp"] uploads the state again
-        parts = tuple(ais.get(k) for k in ("X", "f_s2", "ln_weights", "C_tmp", "K_Xa_X"))
-        key = (id(ais),) + tuple(id(a) for a in parts) + tuple(ctx.__dict__.get("_gp_key") or ())
+        # (a dict the mirror's active_importance_sampling returned finds its own key here: that call left the state
+        # installed)
+        key, parts = _is_state_key(ais, ctx)
         if ctx.__dict__.get("_acq_is_key") == key:
             return
         Xa = _lib.f64(ais["X"])
         per_sample = Xa.ndim == 3
         Na = Xa.shape[-2]
-        ctmp = _lib.f64(self._c_tmp(gp, ais))
         fs2a = _lib.f64(ais["f_s2"])
         lnw = None if self.acq_info.get("variational_importance_sampling") else _lib.f64(ais["ln_weights"])
-        ctx.check(ctx._lib.vbmc_acq_is_set(ctx._h, Na, _lib.ptr(Xa), int(per_sample), _lib.ptr(ctmp),
-                                           _lib.ptr(fs2a), _lib.ptr(lnw)))
+        ctx.__dict__["_acq_is_key"] = None  # (a call that fails half way leaves no key naming an overwritten state)
+        if ais.get("C_tmp") is None and ais.get("K_Xa_X") is None:
+            # the mirror's dict with products=False whose state another GP or dict has displaced: formed again on the device
+            ctx.check(ctx._lib.vbmc_acq_is_build(ctx._h, Na, _lib.ptr(Xa), int(per_sample), _lib.ptr(fs2a),
+                                                 _lib.ptr(lnw), None, None))
+        else:
+            ctmp = _lib.f64(self._c_tmp(gp, ais))
+            ctx.check(ctx._lib.vbmc_acq_is_set(ctx._h, Na, _lib.ptr(Xa), int(per_sample), _lib.ptr(ctmp),
+                                               _lib.ptr(fs2a), _lib.ptr(lnw)))
         # (the held references keep every keyed object alive, so an id cannot be recycled)
         ctx.__dict__["_acq_is_key"], ctx.__dict__["_acq_is_ref"] = key, (ais, gp.posteriors, parts)
 

@@ -29,6 +29,7 @@ SOURCES = [
     "adam_fused.hip",
     "api_acq.hip",
     "api_acq_is.hip",
+    "acq_is_prep.hip",
     "sample.hip",
     "transform.hip",
     "kde.hip",

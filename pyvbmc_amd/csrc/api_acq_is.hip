@@ -14,6 +14,9 @@
 // Kernels: the predictive variance at Xs through the predict launches of gp.hip; K(Xs, X) by direct
 // differences; the M x N x Na product on the FP64 matrix cores; one wave per (point, sample) for
 // the cross-kernel K(Xs, Xa), the integrand and its log-sum-exp.
+// vbmc_acq_is_build forms the same state on the device from Xa alone (step 3 of active_importance_sampling,
+// :264-308): K_Xa_X[s] by direct differences and C_tmp[s] as two panel products against the resident L^-1
+// (L^-1 (K_Xa_X L^-1)^T / sn2_eff, the intermediate transposed in between) or one against L.
 #include <cmath>
 #include <cstring>
 
@@ -120,9 +123,81 @@ __global__ void is_combine_kernel(const double* __restrict__ acq_s, int S, int64
   acq[m] = mx + log(sum / S);
 }
 
+// B[c][r] = A[r][c] / div, A (R x C) row-major: the orientation the second factor of C_tmp needs
+__global__ __launch_bounds__(256) void transpose_div_kernel(const double* __restrict__ A, int64_t R, int C, double div,
+                                                            double* __restrict__ B) {
+  __shared__ double t[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+  const int64_t r0 = (int64_t)blockIdx.y * 32;
+  const int c0 = blockIdx.x * 32;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t r = r0 + ty + 8 * k;
+    const int c = c0 + tx;
+    t[ty + 8 * k][tx] = (r < R && c < C) ? A[(size_t)r * C + c] : 0.0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = c0 + ty + 8 * k;
+    const int64_t r = r0 + tx;
+    if (r < R && c < C) B[(size_t)c * R + r] = t[tx][ty + 8 * k] / div;
+  }
+}
+
 IsState* is_of(vbmc_ctx* ctx) {
   if (!ctx->acq_is) ctx->acq_is = new IsState();
   return (IsState*)ctx->acq_is;
+}
+
+// the state's allocation and layout for Na importance points of the context's GP
+int is_reserve(vbmc_ctx* ctx, IsState* st, int64_t Na, int per_sample_xa, bool has_lnw) {
+  const GpState& g = ctx->gp;
+  const int S = g.S, N = g.N, D = g.D;
+  const size_t n_xa = (size_t)(per_sample_xa ? S : 1) * Na * D, n_C = (size_t)S * N * Na, n_f = (size_t)S * Na;
+  const size_t need = n_xa + n_C + 2 * n_f;
+  HIP_TRY(ctx, stream_wait(ctx));
+  if (st->cap < need) {
+    if (st->d) HIP_TRY(ctx, hipFree(st->d));
+    st->d = nullptr;
+    st->cap = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&st->d, sizeof(double) * (need + need / 8)));
+    st->cap = need + need / 8;
+  }
+  st->Na = Na; st->S = S; st->N = N; st->D = D; st->per_sample = per_sample_xa ? 1 : 0;
+  st->has_lnw = has_lnw ? 1 : 0;
+  st->o_C = n_xa; st->o_f = n_xa + n_C; st->o_w = st->o_f + n_f;
+  return 0;
+}
+
+// Xa, f_s2 at Xa (arrives (Na, S) as the reference stores it; kept [S][Na]) and ln_weights into the state
+int is_upload_small(vbmc_ctx* ctx, IsState* st, const double* Xa, const double* fs2a_NaxS, const double* lnw_SxNa) {
+  const int S = st->S;
+  const int64_t Na = st->Na;
+  const size_t n_f = (size_t)S * Na;
+  HIP_TRY(ctx, hipMemcpyAsync(st->d, Xa, sizeof(double) * st->o_C, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<double> ft(n_f);
+  for (int64_t a = 0; a < Na; ++a)
+    for (int s = 0; s < S; ++s) ft[(size_t)s * Na + a] = fs2a_NaxS[(size_t)a * S + s];
+  HIP_TRY(ctx, hipMemcpyAsync(st->d + st->o_f, ft.data(), sizeof(double) * n_f, hipMemcpyHostToDevice, ctx->stream));
+  if (lnw_SxNa)
+    HIP_TRY(ctx, hipMemcpyAsync(st->d + st->o_w, lnw_SxNa, sizeof(double) * n_f, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, stream_wait(ctx));  // (ft is a local; the caller's arrays are pageable)
+  return 0;
+}
+
+// n doubles of device memory to the host through the pinned buffer, in chunks
+int download_chunked(vbmc_ctx* ctx, const double* d_src, double* dst, size_t n) {
+  const size_t chunk = (size_t)1 << 20;  // 8 MiB
+  int rc = ensure_pinned(ctx, n < chunk ? n : chunk);
+  if (rc) return rc;
+  for (size_t o = 0; o < n; o += chunk) {
+    const size_t m = (n - o) < chunk ? (n - o) : chunk;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, d_src + o, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, stream_wait(ctx));
+    memcpy(dst + o, ctx->h_pinned, sizeof(double) * m);
+  }
+  return 0;
 }
 
 }  // namespace
@@ -142,30 +217,59 @@ extern "C" int vbmc_acq_is_set(vbmc_ctx* ctx, int64_t Na, const double* Xa, int 
   NEED_DEVICE(ctx);
   if (!ctx->gp.set) return vbmc_fail(ctx, VBMC_E_ARG, "acq_is_set: GP not set");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const GpState& g = ctx->gp;
   IsState* st = is_of(ctx);
+  int rc = is_reserve(ctx, st, Na, per_sample_xa, lnw_SxNa != nullptr);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(st->d + st->o_C, Ctmp_SxNxNa, sizeof(double) * (st->o_f - st->o_C), hipMemcpyHostToDevice,
+                              ctx->stream));
+  if ((rc = is_upload_small(ctx, st, Xa, fs2a_NaxS, lnw_SxNa))) return rc;
+  return VBMC_OK;
+}
+
+// Step 3 of active_importance_sampling (vbmc/active_importance_sampling.py:264-308) on the device.
+extern "C" int vbmc_acq_is_build(vbmc_ctx* ctx, int64_t Na, const double* Xa, int per_sample_xa,
+                                 const double* fs2a_NaxS, const double* lnw_SxNa, double* K_out_SxNaxN,
+                                 double* C_out_SxNxNa) {
+  if (!ctx || Na < 1 || !Xa || !fs2a_NaxS) return VBMC_E_ARG;
+  NEED_DEVICE(ctx);
+  if (!ctx->gp.set) return vbmc_fail(ctx, VBMC_E_ARG, "acq_is_build: GP not set");
+  const GpState& g = ctx->gp;
   const int S = g.S, N = g.N, D = g.D;
-  const size_t n_xa = (size_t)(per_sample_xa ? S : 1) * Na * D, n_C = (size_t)S * N * Na, n_f = (size_t)S * Na;
-  const size_t need = n_xa + n_C + 2 * n_f;
-  HIP_TRY(ctx, stream_wait(ctx));
-  if (st->cap < need) {
-    if (st->d) HIP_TRY(ctx, hipFree(st->d));
-    st->d = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&st->d, sizeof(double) * (need + need / 8)));
-    st->cap = need + need / 8;
+  if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "acq_is_build: D=%d > 32 not supported", D);
+  // (Na / 32 and Na / 64 are grid.y of the transpose and of the panel product: below 65536)
+  if (Na > ((int64_t)1 << 20) || (int64_t)N * Na > ((int64_t)1 << 31) - 1)
+    return vbmc_fail(ctx, VBMC_E_UNSUP, "acq_is_build: Na=%lld importance points with N=%d not supported", (long long)Na, N);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  IsState* st = is_of(ctx);
+  int rc = is_reserve(ctx, st, Na, per_sample_xa, lnw_SxNa != nullptr);
+  if (rc) return rc;
+  const size_t nk = (size_t)Na * N;
+  if ((rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, 3 * nk))) return rc;
+  if ((rc = is_upload_small(ctx, st, Xa, fs2a_NaxS, lnw_SxNa))) return rc;
+  double *d_K = ctx->d_scratch, *d_T = d_K + nk, *d_TT = d_T + nk;
+  const dim3 tgrid((unsigned)((N + 31) / 32), (unsigned)((Na + 31) / 32));
+  for (int s = 0; s < S; ++s) {
+    const double* hyp = g.d_hyp + (size_t)s * g.P;
+    const double* d_Xa = st->d + (st->per_sample ? (size_t)s * Na * D : 0);
+    double* d_C = st->d + st->o_C + (size_t)s * N * Na;
+    hipLaunchKernelGGL(se_cross_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, ctx->stream, d_Xa, Na,
+                       (const double*)g.d_X, N, D, hyp, d_K);
+    if (g.L_chol[s]) {
+      // (L'L)^-1 K(X, Xa) / sn2_eff = L^-1 (K_Xa_X L^-1)^T / sn2_eff   (:294-304)
+      if ((rc = launch_gp_panel_product(ctx, d_K, g.d_Linv + (size_t)s * N * N, d_T, Na, N, N, true))) return rc;
+      hipLaunchKernelGGL(transpose_div_kernel, tgrid, dim3(256), 0, ctx->stream, (const double*)d_T, Na, N, g.sn2_eff[s],
+                         d_TT);
+      if ((rc = launch_gp_panel_product(ctx, g.d_Linv + (size_t)s * N * N, d_TT, d_C, N, N, (int)Na))) return rc;
+    } else {
+      // L K(X, Xa)   (:306)
+      hipLaunchKernelGGL(transpose_div_kernel, tgrid, dim3(256), 0, ctx->stream, (const double*)d_K, Na, N, 1.0, d_TT);
+      if ((rc = launch_gp_panel_product(ctx, g.d_L + (size_t)s * N * N, d_TT, d_C, N, N, (int)Na))) return rc;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    // (the copies wait for the stream: d_K is reused by the next sample, whose kernels start behind this download)
+    if (K_out_SxNaxN && (rc = download_chunked(ctx, d_K, K_out_SxNaxN + (size_t)s * nk, nk))) return rc;
+    if (C_out_SxNxNa && (rc = download_chunked(ctx, d_C, C_out_SxNxNa + (size_t)s * nk, nk))) return rc;
   }
-  st->Na = Na; st->S = S; st->N = N; st->D = D; st->per_sample = per_sample_xa ? 1 : 0;
-  st->has_lnw = lnw_SxNa ? 1 : 0;
-  st->o_C = n_xa; st->o_f = n_xa + n_C; st->o_w = st->o_f + n_f;
-  HIP_TRY(ctx, hipMemcpyAsync(st->d, Xa, sizeof(double) * n_xa, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(st->d + st->o_C, Ctmp_SxNxNa, sizeof(double) * n_C, hipMemcpyHostToDevice, ctx->stream));
-  // f_s2 at Xa arrives (Na, S) as the reference stores it; keep it [S][Na]
-  std::vector<double> ft(n_f);
-  for (int64_t a = 0; a < Na; ++a)
-    for (int s = 0; s < S; ++s) ft[(size_t)s * Na + a] = fs2a_NaxS[(size_t)a * S + s];
-  HIP_TRY(ctx, hipMemcpyAsync(st->d + st->o_f, ft.data(), sizeof(double) * n_f, hipMemcpyHostToDevice, ctx->stream));
-  if (lnw_SxNa)
-    HIP_TRY(ctx, hipMemcpyAsync(st->d + st->o_w, lnw_SxNa, sizeof(double) * n_f, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));
   return VBMC_OK;
 }

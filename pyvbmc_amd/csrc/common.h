@@ -613,8 +613,10 @@ inline int predict_plan(vbmc_ctx* ctx, int64_t M, int64_t budget, int64_t cost, 
 }
 int launch_gp_predict_products(vbmc_ctx* ctx, int64_t M, const double* d_xs, double* d_Ks, double* d_part,
                                const void* fin = nullptr, bool* fin_done = nullptr);
-// C (M x NC) = A (M x KD) B (KD x NC), row-major: the panel-product kernel of predict, store only
-int launch_gp_panel_product(vbmc_ctx* ctx, const double* d_A, const double* d_B, double* d_C, int64_t M, int KD, int NC);
+// C (M x NC) = A (M x KD) B (KD x NC), row-major: the panel-product kernel of predict, store only; upper_b: B is upper
+// triangular (KD = NC) and the panels below the diagonal of a column tile are skipped
+int launch_gp_panel_product(vbmc_ctx* ctx, const double* d_A, const double* d_B, double* d_C, int64_t M, int KD, int NC,
+                            bool upper_b = false);
 int launch_gp_predict_all(vbmc_ctx* ctx, int64_t M, const double* d_xs, double* d_Ks, double* d_part,
                           int add_noise, double* d_fmu, double* d_fs2, int64_t ld);
 // c[n][m] = |a_n - b_m|^2 (centred expansion, cross term on the FP64 matrix cores), optional

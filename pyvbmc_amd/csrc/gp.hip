@@ -1177,10 +1177,11 @@ int launch_gp_predict_all(vbmc_ctx* ctx, int64_t M, const double* d_xs, double* 
   return 0;
 }
 
-// C (M x NC) = A (M x KD) B (KD x NC), row-major, all of B: the panel product alone
-int launch_gp_panel_product(vbmc_ctx* ctx, const double* d_A, const double* d_B, double* d_C, int64_t M, int KD, int NC) {
+// C (M x NC) = A (M x KD) B (KD x NC), row-major: the panel product alone, over all of B or (upper_b) its upper triangle
+int launch_gp_panel_product(vbmc_ctx* ctx, const double* d_A, const double* d_B, double* d_C, int64_t M, int KD, int NC,
+                            bool upper_b) {
   hipLaunchKernelGGL(predict_var_mfma_kernel, dim3((NC + TS - 1) / TS, (unsigned)((M + TS - 1) / TS)), dim3(256), 0,
-                     ctx->stream, d_A, d_B, M, KD, NC, 1, (double*)nullptr, d_C, (const double*)nullptr,
+                     ctx->stream, d_A, d_B, M, KD, NC, upper_b ? 0 : 1, (double*)nullptr, d_C, (const double*)nullptr,
                      (const double*)nullptr, (int64_t)0);
   HIP_TRY(ctx, hipGetLastError());
   return 0;

@@ -25,6 +25,11 @@ entropy/entmc_vbmc.py:64-112 -- or a GP beyond the LDS plans) goes back to the R
 ``patch`` replaced, with the reference's own arguments: the drop-in never turns a run the reference could do
 into an error, and never routes anywhere but to the reference's own code.  ``unpatch(vo)`` restores the
 module.  Nothing here imports the reference: ``vo`` is passed in (or imported on request).
+
+``patch_active_sampling(mod)`` is a separate, explicit step (``patch`` does not take it): it rebinds
+``active_importance_sampling`` on ``pyvbmc.vbmc.active_sample`` -- the name that module binds by value at import
+(active_sample.py:15) -- to this package's mirror, with the same fallback to the reference's function for shapes the
+kernels do not cover; ``unpatch_active_sampling(mod)`` puts the reference's function back.
 """
 import numpy as np
 
@@ -32,12 +37,13 @@ from . import _lib
 from . import entropy as _entropy
 from . import minimize_adam as _adam
 from . import variational_optimization as _avo
+from .active_importance_sampling import active_importance_sampling as _ais_mirror
 
 _SAVED = "_pyvbmc_amd_saved"
 _LEAVES = ("entmc_vbmc", "entlb_vbmc", "_gp_log_joint", "_neg_elcbo")
 
 
-_MIRROR_ONLY_KW = ("rng", "seed", "eps_half", "ctx", "rows", "return_raw")  # keyword-only extras of the mirrors
+_MIRROR_ONLY_KW = ("rng", "seed", "eps_half", "ctx", "rows", "return_raw", "sampler", "products")  # keyword-only extras of the mirrors
 
 
 def _with_reference_fallback(fast, ref):
@@ -219,3 +225,36 @@ def unpatch(vo):
     delattr(vo, _SAVED)
     _avo.clear_fast_path()  # (the repeat record holds the last call's vp, gp and context)
     return vo
+
+
+_SAVED_AIS = "_pyvbmc_amd_saved_ais"
+
+
+def patch_active_sampling(mod=None):
+    """Rebind ``active_importance_sampling`` on ``mod`` (default: ``pyvbmc.vbmc.active_sample``, which binds the name by
+    value, active_sample.py:15) to the device mirror, with the reference's function behind it for
+    ``_lib.UnsupportedShape``.  Idempotent; returns ``mod``."""
+    if mod is None:
+        import importlib
+
+        mod = importlib.import_module("pyvbmc.vbmc.active_sample")
+    if hasattr(mod, _SAVED_AIS):
+        unpatch_active_sampling(mod)
+    ref = getattr(mod, "active_importance_sampling", None)
+    setattr(mod, _SAVED_AIS, ref)
+    fast = _ais_mirror
+    mod.active_importance_sampling = _with_reference_fallback(fast, ref) if callable(ref) else fast
+    return mod
+
+
+def unpatch_active_sampling(mod):
+    """Put back what ``patch_active_sampling`` replaced."""
+    if not hasattr(mod, _SAVED_AIS):
+        return mod
+    ref = getattr(mod, _SAVED_AIS)
+    if ref is None:
+        delattr(mod, "active_importance_sampling")
+    else:
+        mod.active_importance_sampling = ref
+    delattr(mod, _SAVED_AIS)
+    return mod
