@@ -45,6 +45,8 @@ enum {
   VBMC_E_UNSUP = -5,   /* combination the reference raises NotImplemented on */
   VBMC_E_NONFINITE = -6, /* non-finite input where the path needs finite    */
   VBMC_E_NOMEM = -7,    /* host allocation failed (vbmc_mt19937_randn)       */
+  VBMC_E_NOTPD = -8,    /* vbmc_gp_posterior / vbmc_gp_append: a pivot of the Cholesky factorisation is not a
+                           positive finite number; the GP state installed before the call is unchanged */
   VBMC_W_GP_CHANGED = 1, /* vbmc_neg_elcbo only: the watched GP arrays changed (vbmc_set_gp_watch);
                            the outputs were computed on the GP of the last vbmc_set_gp: discard them,
                            upload the GP again and repeat the call                               */
@@ -123,7 +125,8 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on);
  *        5 = gp_predict's variance product kernel alone -- recorded at vbmc_set_timing(ctx, 2) ONLY, and that pass runs
  *            the product WITHOUT the finish in its epilogue (three launches where production runs two): it measures
  *            the product kernel, not the production configuration; a predict at level 0 / 1 invalidates the record
- *            (VBMC_E_ARG "no timed launch recorded", never a stale interval). */
+ *            (VBMC_E_ARG "no timed launch recorded", never a stale interval).
+ *        6 = vbmc_gp_posterior's blocked Cholesky factorisation alone (all its block steps). */
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out);
 
 /* Host-side wall-clock breakdown (microseconds) of the most recent vbmc_neg_elcbo:
@@ -388,6 +391,31 @@ int vbmc_set_gp(vbmc_ctx* ctx, int N, int D, int S, int P, int mean_kind,
                 const double* X_NxD, const double* hyp_SxP, const double* alpha_SxN,
                 const double* L_SxNxN, const int32_t* L_chol_S, const double* sW_SxN,
                 const double* sn2_mult_S);
+
+/* The same state BUILT on the device.  Replaces pyvbmc_amd/gp.py GP._posterior (gpyreg's posterior, SURVEY
+ * Appendix A "Posterior"; gpyreg is not part of the reference tree) followed by vbmc_set_gp: per sample
+ *   A = K(X, X) / sl + diag(sn2 / sn2_div),  U^T U = A (upper Cholesky),  alpha = U^-1 U^-T (y - m(X)) / sl,
+ * with sl = sn2_div (sn2_mult = 1), sW = 1 / sqrt(sl), L = U, L_chol = 1.  The noise scalars are the caller's: sn2
+ * (S x N, noise variance per point) and sn2_div (S, its minimum).  Afterwards the context's GP state is what
+ * vbmc_set_gp would have left for those records, and y and sn2 stay on the device for vbmc_gp_append.  alpha_SxN and
+ * L_SxNxN are nullable: only what is asked for is copied back.  VBMC_E_UNSUP when a sample has sn2_div < 1e-6 (the
+ * non-Cholesky branch stays on the host), VBMC_E_ARG on bad shapes, VBMC_E_NOTPD when a sample does not factorise --
+ * the state installed before is then unchanged.  FP64, fixed summation order: bit-reproducible. */
+int vbmc_gp_posterior(vbmc_ctx* ctx, int N, int D, int S, int P, int mean_kind, const double* X_NxD,
+                      const double* y_N, const double* sn2_SxN, const double* sn2_div_S, const double* hyp_SxP,
+                      double* alpha_SxN, double* L_SxNxN);
+
+/* One more training point (x, y) for the posterior vbmc_gp_posterior (or an earlier append) installed, in O(S N^2):
+ * what gpyreg's gp.update(xnew, ynew, compute_posterior=True) does after every acquired point
+ * (vbmc/active_sample.py:584), which gp.py answers with a full GP._posterior.  With k = K(X, x) / sl, l = U^-T k,
+ * d = sqrt(sf^2 / sl + sn2 / sn2_div - l.l):  U' = [[U, l], [0, d]],  U'^-1 = [[U^-1, -U^-1 l / d], [0, 1 / d]].
+ * Constant noise only: VBMC_E_UNSUP when the resident state has per-point noise, VBMC_E_ARG when it was not built
+ * on the device, VBMC_E_NOTPD (state unchanged) when d^2 is not positive and finite.  Outputs nullable, of the
+ * N + 1 points. */
+int vbmc_gp_append(vbmc_ctx* ctx, const double* x_D, double y, double* alpha_SxN1, double* L_SxN1xN1);
+
+/* Copy the resident posterior out: alpha (S x N) and L (S x N x N), both nullable. */
+int vbmc_gp_fetch(vbmc_ctx* ctx, double* alpha_SxN, double* L_SxNxN);
 
 /* ---- a8: vbmc/variational_optimization.py:1238-1606 _gp_log_joint ------- */
 

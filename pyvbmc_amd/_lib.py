@@ -18,6 +18,7 @@ LIB_PATH = Path(os.environ.get("VBMC_HIP_LIB", _HERE / "libvbmc_hip.so"))
 EPS_RESIDENT, EPS_PHILOX = 0, 1
 MEAN_ZERO, MEAN_CONST, MEAN_NEGQUAD = 0, 1, 2
 E_ARG, E_HIP, E_RCCL, E_NODEV, E_UNSUP, E_NONFINITE = -1, -2, -3, -4, -5, -6
+E_NOTPD = -8  # vbmc_gp_posterior / vbmc_gp_append: not positive definite
 W_GP_CHANGED = 1  # vbmc_neg_elcbo: the watched GP arrays changed under it (vbmc_set_gp_watch)
 W_NOT_FUSED = 2   # vbmc_adam_run_auto: the one-launch loop does not apply (or gave up): run batches with vbmc_adam_run
 
@@ -155,6 +156,12 @@ SIGNATURES = {
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp,
          C.POINTER(C.c_int32), _dp, _dp],
     ),
+    "vbmc_gp_posterior": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
+    ),
+    "vbmc_gp_append": (C.c_int, [_vp, _dp, C.c_double, _dp, _dp]),
+    "vbmc_gp_fetch": (C.c_int, [_vp, _dp, _dp]),
     "vbmc_gp_log_joint": (
         C.c_int,
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp],
@@ -306,6 +313,8 @@ class Context:
                 raise ValueError(msg)
             if rc == E_NODEV:
                 raise NoDeviceError(rc, msg)
+            if rc == E_NOTPD:
+                raise np.linalg.LinAlgError(msg)  # what the host route's scipy.linalg.cholesky raises
             raise VbmcHipError(rc, msg)
 
     # -- thin typed wrappers --------------------------------------------------

@@ -23,6 +23,8 @@ SOURCES = [
     "mixture.hip",
     "gp.hip",
     "api_gp.hip",
+    "gp_post.hip",
+    "api_gp_post.hip",
     "api_elbo.hip",
     "api_batch.hip",
     "adam.hip",

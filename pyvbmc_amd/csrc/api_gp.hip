@@ -8,6 +8,32 @@
 
 static const double kTiny = 2.220446049250313e-16;  // np.spacing(1)
 
+int gp_state_grow(vbmc_ctx* ctx, GpState& g, int N, int D, int S, int P, bool with_post) {
+  const size_t nn = (size_t)N * N, ld = (size_t)predict_ld(N);
+  auto grow = [&](double** p, size_t* cap, size_t n) -> int {
+    if (*p && *cap >= n) return 0;
+    if (*p) HIP_TRY(ctx, hipFree(*p));
+    *p = nullptr;
+    const size_t want = n + n / 8 + 64;
+    HIP_TRY(ctx, hipMalloc((void**)p, sizeof(double) * want));
+    *cap = want;
+    return 0;
+  };
+  int rc;
+  if ((rc = grow(&g.d_X, &g.cap_X, (size_t)N * D)) || (rc = grow(&g.d_XT, &g.cap_XT, (size_t)N * D)) ||
+      (rc = grow(&g.d_alpha, &g.cap_alpha, (size_t)S * N)) ||
+      (rc = grow(&g.d_L, &g.cap_L, (size_t)S * nn)) || (rc = grow(&g.d_Linv, &g.cap_Linv, (size_t)S * nn)) ||
+      (rc = grow(&g.d_LinvP, &g.cap_LinvP, (size_t)S * ld * ld)) ||
+      (rc = grow(&g.d_sW, &g.cap_sW, (size_t)S * N)) || (rc = grow(&g.d_hyp, &g.cap_hyp, (size_t)S * P)) ||
+      (rc = grow(&g.d_xc, &g.cap_xc, (size_t)D)) || (rc = grow(&g.d_smeta, &g.cap_smeta, (size_t)3 * S)))
+    return rc;
+  if (with_post &&
+      ((rc = grow(&g.d_y, &g.cap_y, (size_t)N)) || (rc = grow(&g.d_r, &g.cap_r, (size_t)S * N)) ||
+       (rc = grow(&g.d_sn2, &g.cap_sn2, (size_t)S * N)) || (rc = grow(&g.d_sl, &g.cap_sl, (size_t)S))))
+    return rc;
+  return 0;
+}
+
 extern "C" int vbmc_set_gp(vbmc_ctx* ctx, int N, int D, int S, int P, int mean_kind,
                            const double* X_NxD, const double* hyp_SxP, const double* alpha_SxN,
                            const double* L_SxNxN, const int32_t* L_chol_S, const double* sW_SxN,
@@ -26,26 +52,10 @@ extern "C" int vbmc_set_gp(vbmc_ctx* ctx, int N, int D, int S, int P, int mean_k
   HIP_TRY(ctx, stream_wait(ctx));
   GpState& g = ctx->gp;
   g.set = false;
-  // device buffers are kept across GP updates and only grown (active sampling updates the GP after
-  // every new point: N creeps up by one)
+  g.dev_built = false;
   const size_t nn = (size_t)N * N;
-  auto grow = [&](double** p, size_t* cap, size_t n) -> int {
-    if (*p && *cap >= n) return 0;
-    if (*p) HIP_TRY(ctx, hipFree(*p));
-    *p = nullptr;
-    const size_t want = n + n / 8 + 64;
-    HIP_TRY(ctx, hipMalloc((void**)p, sizeof(double) * want));
-    *cap = want;
-    return 0;
-  };
-  int rc;
-  if ((rc = grow(&g.d_X, &g.cap_X, (size_t)N * D)) || (rc = grow(&g.d_XT, &g.cap_XT, (size_t)N * D)) ||
-      (rc = grow(&g.d_alpha, &g.cap_alpha, (size_t)S * N)) ||
-      (rc = grow(&g.d_L, &g.cap_L, (size_t)S * nn)) || (rc = grow(&g.d_Linv, &g.cap_Linv, (size_t)S * nn)) ||
-      (rc = grow(&g.d_LinvP, &g.cap_LinvP, (size_t)S * predict_ld(N) * predict_ld(N))) ||
-      (rc = grow(&g.d_sW, &g.cap_sW, (size_t)S * N)) || (rc = grow(&g.d_hyp, &g.cap_hyp, (size_t)S * P)) ||
-      (rc = grow(&g.d_xc, &g.cap_xc, (size_t)D)) || (rc = grow(&g.d_smeta, &g.cap_smeta, (size_t)3 * S)))
-    return rc;
+  int rc = gp_state_grow(ctx, g, N, D, S, P, false);
+  if (rc) return rc;
   g.N = N; g.D = D; g.S = S; g.P = P; g.mean_kind = mean_kind;
   g.hyp.assign(hyp_SxP, hyp_SxP + (size_t)S * P);
   g.L_chol.assign(L_chol_S, L_chol_S + S);

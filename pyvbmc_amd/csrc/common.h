@@ -115,6 +115,15 @@ struct GpState {
   size_t cap_X = 0, cap_XT = 0, cap_alpha = 0, cap_L = 0, cap_Linv = 0, cap_LinvP = 0, cap_sW = 0, cap_hyp = 0, cap_xc = 0, cap_smeta = 0;
   std::vector<double> h_small;  // host source of the xc / smeta uploads
   std::vector<double> h_XT;     // host source of the d_XT upload
+  // a posterior built on the device (api_gp_post.hip): what vbmc_gp_append needs on top of the above
+  bool dev_built = false;       // installed by vbmc_gp_posterior / vbmc_gp_append (vbmc_set_gp clears it)
+  bool homo = false;            // every point's noise variance is its sample's constant: a point can be appended
+  double* d_y = nullptr;        // N
+  double* d_r = nullptr;        // S x N : y - m_s(X)
+  double* d_sn2 = nullptr;      // S x N : noise variance per point
+  double* d_sl = nullptr;       // S : sn2_div * sn2_mult, the scale of A = K / sl + diag(sn2 / sn2_div)
+  size_t cap_y = 0, cap_r = 0, cap_sn2 = 0, cap_sl = 0;
+  std::vector<double> h_X, h_y, h_sl;  // host copies: X (N x D), y (N), sl (S)
 };
 
 // per-sample results of the GP expected log joint on the host (api_gp.hip glj_finalize)
@@ -136,8 +145,8 @@ struct ElboScratch {
 struct vbmc_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[12] = {};  // pairs: (0,1) entmc, (2,3) glj, (4,5) pdf, (6,7) predict, (8,9) elbo, (10,11) predict's variance product
-  bool ev_valid[6] = {false, false, false, false, false, false};
+  hipEvent_t ev[14] = {};  // pairs: (0,1) entmc, (2,3) glj, (4,5) pdf, (6,7) predict, (8,9) elbo, (10,11) predict's variance product, (12,13) the GP posterior's factorisation
+  bool ev_valid[7] = {false, false, false, false, false, false, false};
   std::string err;
   hipDeviceProp_t prop;
 
@@ -264,6 +273,9 @@ struct vbmc_ctx {
   int last_raw_n = 0;
 
   GpState gp;
+  GpState gp_next;             // vbmc_gp_posterior / vbmc_gp_append build here and swap it with `gp` when the build succeeded
+  double* d_post_ws = nullptr;  // their workspace: inverted diagonal blocks, the append's vectors, the per-sample flags
+  size_t d_post_ws_cap = 0;
 
   ncclComm* comm = nullptr;
   int rank = 0, world = 1;
@@ -570,7 +582,21 @@ int launch_kl_terms(vbmc_ctx* ctx, const double* d_y_own, const double* d_y_othe
 // gp
 int launch_gp_log_joint(vbmc_ctx* ctx, int want_grad, double* d_res, double* d_Z);
 int launch_gp_var(vbmc_ctx* ctx, const double* d_Z, double* d_V, double* d_Q);
-int launch_trinv(vbmc_ctx* ctx);
+// d_Dinv: the inverted 64 x 64 diagonal blocks [S][nb] when the caller has them already (gp_post.hip's factorisation
+// forms them); the first stage is then skipped
+int launch_trinv(vbmc_ctx* ctx, const double* d_Dinv = nullptr);
+int launch_pad_linv(vbmc_ctx* ctx);
+// gp_post.hip: the posterior of ctx->gp's X, y, hyp, noise built in ctx->gp's buffers (covariance, blocked upper
+// Cholesky, L^-1, alpha); d_flag[s] != 0 afterwards: sample s met a pivot that is not a positive finite number
+int launch_gp_post_build(vbmc_ctx* ctx, double* d_Dinv, int* d_flag);
+// one point appended: `from` (N points, live) -> ctx->gp (N + 1 points, X / XT / hyp / sl / sn2 already in place);
+// ws: 3 S N + 4 S + S (N + 1) doubles
+int launch_gp_post_append(vbmc_ctx* ctx, const GpState& from, double y_new, double* ws, int* d_flag);
+void gp_post_free(vbmc_ctx* ctx);
+// api_gp.hip: the device buffers of a GP state of N points, D dimensions, S samples, P hyper-parameters, kept across GP
+// updates and only grown (capacity n + n / 8 + 64: active sampling makes N creep up by one); with_post: also what a
+// device-built posterior keeps (y, residuals, noise variances, sl)
+int gp_state_grow(vbmc_ctx* ctx, GpState& g, int N, int D, int S, int P, bool with_post);
 // leading dimension of the padded operands of predict's variance product, and the size of the
 // K* scratch of a batch of mb points (rows rounded up to whole 64-row tiles)
 inline size_t align32(size_t n) { return (n + 31) & ~(size_t)31; }

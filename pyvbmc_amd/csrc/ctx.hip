@@ -204,7 +204,7 @@ int vbmc_ctx_create(int device_id, vbmc_ctx** out) {
   if (e == hipSuccess) e = hipGetDeviceProperties(&ctx->prop, device_id);
   if (e == hipSuccess) bind_host_thread(ctx);  // (before the pinned allocations below: they follow the thread's node)
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-  for (int i = 0; i < 12 && e == hipSuccess; ++i) e = hipEventCreate(&ctx->ev[i]);
+  for (int i = 0; i < 14 && e == hipSuccess; ++i) e = hipEventCreate(&ctx->ev[i]);
   if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_done, 64, hipHostMallocDefault);
   if (e == hipSuccess) {
     for (int i = 0; i < 8; ++i) ctx->h_done[i] = 0;
@@ -248,6 +248,7 @@ void vbmc_ctx_destroy(vbmc_ctx* ctx) {
   acq_is_free(ctx);
   randn_dev_free(ctx);
   xf_free(ctx);
+  gp_post_free(ctx);
   double* bufs[] = {ctx->d_mix, ctx->d_mix_fg, ctx->d_acq_fg, ctx->d_stage, ctx->d_eps, ctx->d_scratch, ctx->d_out, ctx->d_ptick, ctx->gp.d_X, ctx->gp.d_XT,
                     ctx->gp.d_alpha, ctx->gp.d_L, ctx->gp.d_Linv, ctx->gp.d_LinvP, ctx->gp.d_sW, ctx->gp.d_hyp,
                     ctx->gp.d_xc, ctx->gp.d_smeta};
@@ -356,7 +357,7 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on) {
 }
 
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out) {
-  if (!ctx || which < 0 || which > 5 || !ms_out) return VBMC_E_ARG;
+  if (!ctx || which < 0 || which > 6 || !ms_out) return VBMC_E_ARG;
   NEED_DEVICE(ctx);
   if (!ctx->ev_valid[which])
     return vbmc_fail(ctx, VBMC_E_ARG, which == 5 ? "no timed launch recorded for 5 (gp_predict's product alone is timed at vbmc_set_timing(ctx, 2) only)"

@@ -53,41 +53,7 @@ __global__ __launch_bounds__(64) void trinv_diag_kernel(const double* __restrict
   if (smeta[3 * s] == 0.0) return;  // not a Cholesky sample: nothing to invert
   __shared__ double sUT[TRB][TRB];  // sUT[r][m] = u_mr: the column above the diagonal element r, contiguous
   __shared__ double sRinv[TRB];     // 1 / u_rr
-  const double* A = L + (size_t)s * N * N;
-  const int r0 = b * TRB;
-  {
-    // all 64 row loads in flight at once (clamped addresses, the padding is patched in afterwards)
-    double u[TRB];
-    const int gc = r0 + c, gcc = min(gc, N - 1);
-#pragma unroll
-    for (int r = 0; r < TRB; ++r) u[r] = A[(size_t)min(r0 + r, N - 1) * N + gcc];
-#pragma unroll
-    for (int r = 0; r < TRB; ++r) {
-      const int gr = r0 + r;
-      const double v = (gr < N && gc < N) ? (gc >= gr ? u[r] : 0.0) : (gr == gc ? 1.0 : 0.0);
-      sUT[c][r] = v;  // element (r, c) of the block
-      if (r == c) sRinv[c] = 1.0 / v;
-    }
-  }
-  __syncthreads();
-  // Column c of the inverse by back substitution, column-oriented so that the multiply-adds of a
-  // step are independent of each other: with s_m = delta_mc to start,
-  //   for r = 63 .. 0:   x_r = s_r / u_rr;   s_m -= u_mr x_r  for all m < r.
-  // Everything is unrolled and lives in registers (x_r = 0 for r > c comes out by itself); the
-  // u_mr of a step are contiguous broadcast LDS reads that do not depend on the arithmetic.
-  double x[TRB];
-#pragma unroll
-  for (int m = 0; m < TRB; ++m) x[m] = (m == c) ? 1.0 : 0.0;
-#pragma unroll
-  for (int r = TRB - 1; r >= 0; --r) {
-    const double xr = x[r] * sRinv[r];
-    x[r] = xr;
-#pragma unroll
-    for (int m = 0; m < r; ++m) x[m] = fma(-sUT[r][m], xr, x[m]);
-  }
-  double* out = Dinv + ((size_t)s * nb + b) * TRB * TRB;
-#pragma unroll
-  for (int r = 0; r < TRB; ++r) out[r * TRB + c] = x[r];
+  tri_block_inverse(L + (size_t)s * N * N, N, b * TRB, c, sUT, sRinv, Dinv + ((size_t)s * nb + b) * TRB * TRB);
 }
 
 __global__ __launch_bounds__(256) void trinv_strip_kernel(const double* __restrict__ L, int N,
@@ -1040,7 +1006,7 @@ int launch_gp_var(vbmc_ctx* ctx, const double* d_Z, double* d_V, double* d_Q) {
 }
 
 // the zero-padded copy of L^-1 predict_var_dma_kernel reads (leading dimension N rounded up to 64)
-static int launch_pad_linv(vbmc_ctx* ctx) {
+int launch_pad_linv(vbmc_ctx* ctx) {
   GpState& g = ctx->gp;
   if (!g.d_LinvP) return 0;
   const int ld = predict_ld(g.N);
@@ -1050,7 +1016,7 @@ static int launch_pad_linv(vbmc_ctx* ctx) {
   return 0;
 }
 
-int launch_trinv(vbmc_ctx* ctx) {
+int launch_trinv(vbmc_ctx* ctx, const double* d_Dinv) {
   GpState& g = ctx->gp;
   const int N = g.N, S = g.S;
   const int nb = (N + TRB - 1) / TRB;
@@ -1060,11 +1026,14 @@ int launch_trinv(vbmc_ctx* ctx) {
     HIP_TRY(ctx, hipGetLastError());
     return launch_pad_linv(ctx);
   }
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, (size_t)S * nb * TRB * TRB);
-  if (rc) return rc;
-  double* Dinv = ctx->d_scratch;
-  hipLaunchKernelGGL(trinv_diag_kernel, dim3(nb, S), dim3(64), 0, ctx->stream, (const double*)g.d_L, N,
-                     (const double*)g.d_smeta, Dinv, nb);
+  const double* Dinv = d_Dinv;
+  if (!Dinv) {
+    int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, (size_t)S * nb * TRB * TRB);
+    if (rc) return rc;
+    hipLaunchKernelGGL(trinv_diag_kernel, dim3(nb, S), dim3(64), 0, ctx->stream, (const double*)g.d_L, N,
+                       (const double*)g.d_smeta, ctx->d_scratch, nb);
+    Dinv = ctx->d_scratch;
+  }
   static size_t lds_set[64] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -1073,7 +1042,7 @@ int launch_trinv(vbmc_ctx* ctx) {
     lds_set[dev & 63] = lds;
   }
   hipLaunchKernelGGL(trinv_strip_kernel, dim3((N + TRS - 1) / TRS, S), dim3(256), lds, ctx->stream,
-                     (const double*)g.d_L, N, (const double*)g.d_smeta, (const double*)Dinv, nb, g.d_Linv);
+                     (const double*)g.d_L, N, (const double*)g.d_smeta, Dinv, nb, g.d_Linv);
   HIP_TRY(ctx, hipGetLastError());
   return launch_pad_linv(ctx);
 }

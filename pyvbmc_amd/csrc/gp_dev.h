@@ -59,3 +59,44 @@ __host__ __device__ inline void gp_sample_moments(const double* fmu, const doubl
   }
   var_tot = (S > 1 ? q / (S - 1) : 0.0) + vsum / S;
 }
+
+// Inverse of one 64 x 64 diagonal block of an upper-triangular factor: the single definition, for trinv_diag_kernel
+// (gp.hip, every block of an uploaded factor) and chol_dinv_kernel (gp_post.hip, block by block while the factor is
+// formed).  A: the factor of one sample, row stride N; the block starts at row / column r0 and is padded with the identity
+// past N (addresses are clamped, never out of bounds).  Called by the 64 threads of a workgroup, thread c = column c:
+// back substitution, column-oriented so that the multiply-adds of a step are independent of each other -- with
+// s_m = delta_mc to start,   for r = 63 .. 0:   x_r = s_r / u_rr;   s_m -= u_mr x_r  for all m < r.
+// Everything is unrolled and lives in registers (x_r = 0 for r > c comes out by itself); the u_mr of a step are contiguous
+// broadcast LDS reads that do not depend on the arithmetic.  sUT[r][m] = u_mr (64 x 64), sRinv[r] = 1 / u_rr; out: the
+// block's inverse, row-major 64 x 64.
+constexpr int TRI_B = 64;
+__device__ __forceinline__ void tri_block_inverse(const double* __restrict__ A, int N, int r0, int c,
+                                                  double (*sUT)[TRI_B], double* sRinv, double* __restrict__ out) {
+  {
+    // all 64 row loads in flight at once (clamped addresses, the padding is patched in afterwards)
+    double u[TRI_B];
+    const int gc = r0 + c, gcc = min(gc, N - 1);
+#pragma unroll
+    for (int r = 0; r < TRI_B; ++r) u[r] = A[(size_t)min(r0 + r, N - 1) * N + gcc];
+#pragma unroll
+    for (int r = 0; r < TRI_B; ++r) {
+      const int gr = r0 + r;
+      const double v = (gr < N && gc < N) ? (gc >= gr ? u[r] : 0.0) : (gr == gc ? 1.0 : 0.0);
+      sUT[c][r] = v;  // element (r, c) of the block
+      if (r == c) sRinv[c] = 1.0 / v;
+    }
+  }
+  __syncthreads();
+  double x[TRI_B];
+#pragma unroll
+  for (int m = 0; m < TRI_B; ++m) x[m] = (m == c) ? 1.0 : 0.0;
+#pragma unroll
+  for (int r = TRI_B - 1; r >= 0; --r) {
+    const double xr = x[r] * sRinv[r];
+    x[r] = xr;
+#pragma unroll
+    for (int m = 0; m < r; ++m) x[m] = fma(-sUT[r][m], xr, x[m]);
+  }
+#pragma unroll
+  for (int r = 0; r < TRI_B; ++r) out[r * TRI_B + c] = x[r];
+}

@@ -12,6 +12,9 @@ names so the hot-path functions accept either it or a real ``gpyreg.GP``:
   (SURVEY 8a row a11), not part of it; hyper-parameter fitting itself (slice
   sampling) is out of scope.
 * ``predict`` runs on the MI355X (vbmc_gp_predict).
+* ``update(..., device=True)``, ``append`` and ``device_posterior`` build the same records on the device instead
+  (vbmc_gp_posterior / vbmc_gp_append: batched FP64 Cholesky, one-point append) and leave them installed there, so
+  the ``upload_gp`` that follows ships nothing.  Opt-in: the default path and its bits are unchanged.
 """
 import ctypes as C
 import sys
@@ -139,7 +142,9 @@ def _gp_ids(gp):
     for p in ps:
         L = p.L
         ids += (id(p), id(p.alpha), id(L), id(p.hyp))
-        tail += (L.item(-1), p.L_chol)
+        # (L = None: a record whose factor stayed on the device -- ``device_posterior(fetch=False)``; its identity,
+        # already in ``ids``, is the key)
+        tail += (L.item(-1) if L is not None else None, p.L_chol)
     return ids, tail
 
 
@@ -177,7 +182,7 @@ def invalidate_gp(ctx=None):
     """Forget the GP the context holds: the next call uploads it again.  Only needed after
     editing GP arrays in place in a way the fingerprint cannot see (see ``_gp_fingerprint``)."""
     ctx = _lib.default_context() if ctx is None else ctx
-    ctx._gp_key = ctx._gp_ref = ctx._gp_ck = ctx._gp_quick = None
+    ctx._gp_key = ctx._gp_ref = ctx._gp_ck = ctx._gp_quick = ctx._gp_dev = None
     vo = sys.modules.get(__package__ + ".variational_optimization")
     if vo is not None:
         vo.clear_fast_path()
@@ -207,9 +212,16 @@ def upload_gp(gp, ctx, lazy=False):
     if getattr(ctx, "_gp_key", None) == key:
         return
     ctx._gp_quick = None
+    posts = list(gp.posteriors)
+    if any(p.L is None for p in posts):
+        # records of a device-built posterior whose L was not fetched, and the context holds something else by now:
+        # built again on the device from X, y, hyp (bit-reproducible: the records' alpha stays what it is)
+        if _device_build(gp, np.stack([np.ravel(p.hyp) for p in posts]), ctx, want_L=False) is None:
+            raise ValueError("upload_gp: posterior records without L that the device cannot rebuild")
+        _adopt(gp, ctx, dev=True)
+        return
     X = _lib.f64(gp.X)
     N, D = X.shape
-    posts = list(gp.posteriors)
     S = len(posts)
     hyp = _lib.f64(np.stack([np.ravel(p.hyp) for p in posts]))
     alpha = _lib.f64(np.stack([np.ravel(p.alpha) for p in posts]))
@@ -227,6 +239,12 @@ def upload_gp(gp, ctx, lazy=False):
     )
     # the held references keep every fingerprinted object alive, so an id cannot be recycled (and the
     # watched buffers stay allocated)
+    ctx._gp_dev = None
+    _keyed(gp, ctx, key, plan)
+
+
+def _keyed(gp, ctx, key, plan):
+    """Record that the context holds ``gp`` under ``key`` and have the library watch the arrays' contents."""
     ctx._gp_key, ctx._gp_ref = key, plan.held
     if not plan.slow and plan.n > 0:
         ctx.check(ctx._lib.vbmc_set_gp_watch(ctx._h, plan.ptrs, plan.lens, plan.n, C.c_uint64(key[-1])))
@@ -234,6 +252,113 @@ def upload_gp(gp, ctx, lazy=False):
         for p in gp.posteriors:
             quick += (id(p), id(p.alpha), id(p.hyp))
         ctx._gp_quick = quick  # (set only while the library watches the arrays' contents)
+
+
+def _adopt(gp, ctx, dev):
+    """Key the context to ``gp`` as it stands, after a call that installed its posterior there itself; ``dev``: the
+    state was built on the device (``GP.append`` may extend it)."""
+    ctx._gp_key = ctx._gp_quick = None
+    ids, tail = _gp_ids(gp)
+    plan = _gp_plan(gp, ctx, ids)
+    key = ids + tail + [plan.checksum()]
+    _keyed(gp, ctx, key, plan)
+    ctx._gp_dev = key if dev else None
+
+
+def _noise_var(gp, hyp_noise):
+    """Noise variance per training point for one sample, as ``GP._posterior`` takes it: the GP's own noise function
+    where it has one, else constant noise exp(2 hyp) plus the user-provided ``s2`` where the GP carries it."""
+    X = np.atleast_2d(gp.X)
+    s2 = getattr(gp, "s2", None)
+    noise = getattr(gp, "noise", None)
+    if noise is not None and hasattr(noise, "compute"):
+        return np.asarray(noise.compute(hyp_noise, X, gp.y, s2), dtype=np.float64).ravel() * np.ones(X.shape[0])
+    sn2 = np.full(X.shape[0], np.exp(2 * hyp_noise[0]))
+    if s2 is not None and np.size(s2):
+        sn2 = sn2 + np.reshape(s2, -1)
+    return sn2
+
+
+def _device_build(gp, hyp, ctx, want_L):
+    """vbmc_gp_posterior for a GP duck type: ``(alpha (S, N), L (S, N, N) or None, sn2_div (S))``, or None when the
+    device route does not apply (a sample on the non-Cholesky branch, VBMC_E_UNSUP) and the caller takes the host path.
+    Raises ``numpy.linalg.LinAlgError`` when a sample is not positive definite (the context's GP is then unchanged)."""
+    X = _lib.f64(np.atleast_2d(gp.X))
+    y = _lib.f64(np.ravel(gp.y))
+    N, D = X.shape
+    hyp = _lib.f64(np.atleast_2d(hyp))
+    S, P = hyp.shape
+    sn2 = _lib.f64(np.stack([_noise_var(gp, h[D + 1 : D + 2]) for h in hyp]))
+    sn2_div = _lib.f64(np.min(sn2, axis=1))
+    sn2_mult = 1.0
+    if not np.all(sn2_div * sn2_mult >= 1e-6):
+        return None
+    alpha = np.empty((S, N))
+    L = np.empty((S, N, N)) if want_L else None
+    rc = ctx._lib.vbmc_gp_posterior(ctx._h, N, D, S, P, mean_kind_of(gp), _lib.ptr(X), _lib.ptr(y), _lib.ptr(sn2),
+                                    _lib.ptr(sn2_div), _lib.ptr(hyp), _lib.ptr(alpha), _lib.ptr(L))
+    if rc == _lib.E_UNSUP:
+        return None
+    ctx.check(rc)
+    return alpha, L, sn2_div
+
+
+def _records(hyp, alpha, L, sW0):
+    posts = np.empty(len(hyp), dtype=object)
+    N = alpha.shape[1]
+    for s in range(len(hyp)):
+        posts[s] = SimpleNamespace(hyp=np.array(hyp[s], dtype=np.float64), alpha=alpha[s].reshape(-1, 1).copy(),
+                                   sW=np.ones(N) * sW0[s], L=None if L is None else L[s], sn2_mult=1.0, L_chol=True)
+    return posts
+
+
+def device_posterior(gp, hyp=None, *, ctx=None, fetch=True):
+    """Build the posterior records of ``gp`` on the device and leave them installed there.
+
+    ``gp``: this package's ``GP``, an attribute-only stand-in or a real ``gpyreg.GP``; read are ``X``, ``y``, ``s2``,
+    ``mean`` and ``noise``.  Noise rule: where ``gp.noise`` has a ``compute`` method it decides the noise variance per
+    point; a stand-in WITHOUT a noise object gets constant noise exp(2 hyp_noise) plus ``gp.s2`` whenever ``s2`` is
+    present and not empty -- so a stand-in whose records were built without user noise must not carry an ``s2``.  ``hyp`` (S, P): the hyper-parameter samples (default: those of the present records).  The
+    noise scalars ``sn2``, ``sn2_div`` are computed here with ``GP._posterior``'s arithmetic; covariance, Cholesky
+    factor, its inverse and ``alpha`` on the device (vbmc_gp_posterior).  Sets ``gp.posteriors`` to records
+    ``hyp, alpha, sW, L, sn2_mult, L_chol`` and keys the context to them: the next ``upload_gp(gp, ctx)`` ships nothing.
+
+    ``fetch=False``: ``alpha`` still comes back (S N doubles) but ``L`` stays on the device and the records carry
+    ``L = None``; ``fetch_posteriors`` fills it in later.
+
+    Returns True, or False -- with ``gp`` untouched -- when the device route does not apply (a sample takes the
+    non-Cholesky branch): the caller then uses the host path.  ``numpy.linalg.LinAlgError`` when a sample is not
+    positive definite, as ``scipy.linalg.cholesky`` raises on the host path."""
+    ctx = (getattr(gp, "ctx", None) or _lib.default_context()) if ctx is None else ctx
+    if hyp is None:
+        hyp = np.stack([np.ravel(p.hyp) for p in gp.posteriors])
+    hyp = np.atleast_2d(np.asarray(hyp, dtype=np.float64))
+    out = _device_build(gp, hyp, ctx, want_L=fetch)
+    if out is None:
+        return False
+    alpha, L, sn2_div = out
+    gp.posteriors = _records(hyp, alpha, L, 1.0 / np.sqrt(sn2_div * 1.0))
+    _adopt(gp, ctx, dev=True)
+    return True
+
+
+def fetch_posteriors(gp, ctx=None):
+    """Fill in the ``L`` of records built with ``fetch=False`` from the device (vbmc_gp_fetch); the context stays keyed
+    to ``gp``.  Returns ``gp.posteriors``."""
+    ctx = (getattr(gp, "ctx", None) or _lib.default_context()) if ctx is None else ctx
+    posts = gp.posteriors
+    if all(p.L is not None for p in posts):
+        return posts
+    upload_gp(gp, ctx)  # (rebuilds on the device if the context holds something else by now)
+    dev = getattr(ctx, "_gp_dev", None) is not None
+    N = gp.X.shape[0]
+    L = np.empty((len(posts), N, N))
+    ctx.check(ctx._lib.vbmc_gp_fetch(ctx._h, None, _lib.ptr(L)))
+    for s, p in enumerate(posts):
+        if p.L is None:
+            p.L = L[s]
+    _adopt(gp, ctx, dev=dev)
+    return posts
 
 
 class GP:
@@ -292,7 +417,11 @@ class GP:
             sW=np.ones(N) / np.sqrt(sn2_div * sn2_mult), L=L, sn2_mult=sn2_mult, L_chol=L_chol,
         )
 
-    def update(self, X_new=None, y_new=None, s2_new=None, hyp=None, compute_posterior=True):
+    def update(self, X_new=None, y_new=None, s2_new=None, hyp=None, compute_posterior=True, *, device=False,
+               fetch=True):
+        """REPLACE the training data (when given) and rebuild the posterior records.  ``device=True``: the records are
+        built on the device and stay installed there (``device_posterior``; ``fetch`` as there); where that route does
+        not apply the call takes the host path below, with its bits."""
         if X_new is not None:
             self.X = np.atleast_2d(np.asarray(X_new, dtype=np.float64))
             self.y = np.asarray(y_new, dtype=np.float64).reshape(-1, 1)
@@ -300,10 +429,46 @@ class GP:
         if hyp is None:
             hyp = np.stack([p.hyp for p in self.posteriors])
         hyp = np.atleast_2d(np.asarray(hyp, dtype=np.float64))
+        if device and device_posterior(self, hyp, ctx=self.ctx, fetch=fetch):
+            return
         posts = np.empty(hyp.shape[0], dtype=object)
         for i, h in enumerate(hyp):
             posts[i] = self._posterior(h)
         self.posteriors = posts
+
+    def append(self, x_new, y_new, *, device=True, fetch=True):
+        """Add ONE training point: ``X``, ``y`` grow by a row and the posterior records follow.
+
+        This class's ``update(X_new, y_new)`` REPLACES the training data; gpyreg's ``update(xnew, ynew)`` -- what the
+        reference calls after every acquired point (vbmc/active_sample.py:584) -- APPENDS to it.  ``append`` is that
+        call for this class.  With ``device=True`` and the context holding this GP's posterior as the device built it
+        (``update(device=True)``, ``device_posterior`` or an earlier ``append``) under constant noise, the factor, its
+        inverse and ``alpha`` are extended on the device in O(S N^2) (vbmc_gp_append); otherwise the call is
+        ``update`` on the extended data.  ``fetch`` as in ``device_posterior``."""
+        x = _lib.f64(np.ravel(x_new))
+        if x.size != self.X.shape[1]:
+            raise ValueError("append: x_new must be one point of the GP's dimension")
+        if self.s2 is not None:
+            raise NotImplementedError("append under user-provided noise: call update with the extended X, y, s2")
+        y = float(np.ravel(y_new)[0])
+        X1 = np.vstack([self.X, x[None, :]])
+        y1 = np.vstack([self.y, [[y]]])
+        ctx = self.ctx
+        posts = self.posteriors
+        hyp = np.stack([p.hyp for p in posts])
+        dev_key = getattr(ctx, "_gp_dev", None)
+        if device and dev_key is not None and dev_key == _gp_fingerprint(self, ctx)[0]:
+            S, N1 = len(posts), X1.shape[0]
+            alpha = np.empty((S, N1))
+            L = np.empty((S, N1, N1)) if fetch else None
+            rc = ctx._lib.vbmc_gp_append(ctx._h, _lib.ptr(x), y, _lib.ptr(alpha), _lib.ptr(L))
+            if rc != _lib.E_UNSUP:
+                ctx.check(rc)
+                self.X, self.y = X1, y1
+                self.posteriors = _records(hyp, alpha, L, [p.sW[0] for p in posts])
+                _adopt(self, ctx, dev=True)
+                return
+        self.update(X1, y1, None, hyp, device=device, fetch=fetch)
 
     def get_hyperparameters(self, as_array=True):
         return np.stack([p.hyp for p in self.posteriors])
