@@ -1,4 +1,4 @@
-"""Build recipe for libvbmc_hip.so (gfx950 only, in-tree).
+"""Build recipe for libvbmc_hip.so and the tests' probe library libvbmc_devprobe.so (gfx950 only, in-tree).
 
     python -m pyvbmc_amd.build           # rebuild if sources are newer
     python -m pyvbmc_amd.build --force
@@ -40,6 +40,10 @@ SOURCES = [
     "host_randn.hip",
     "device_randn.hip",
 ]
+# Test infrastructure, a shared object of its own: entry points that run one fastmath.h primitive per thread
+# (tests/test_fastmath_gpu.py).  Same FLAGS, so the primitives compile as they do inside the kernels.
+PROBE_SRC = CSRC / "devprobe.hip"
+PROBE_LIB = HERE / "libvbmc_devprobe.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
     "--offload-arch=gfx950",
@@ -80,16 +84,38 @@ def _jobs(bdir):
     return jobs
 
 
+def _headers():
+    return list(CSRC.glob("*.h")) + [HERE.parent / "include" / "vbmc_hip.h"]
+
+
+def _stale(lib, deps):
+    return not lib.exists() or any(p.stat().st_mtime > lib.stat().st_mtime for p in deps)
+
+
+def _lib_stale():
+    return _stale(LIB, _sources() + [CSRC / "entropy_ws.hip", CSRC / "entropy_mfma.hip"] + _headers())
+
+
+def _probe_stale():
+    return _stale(PROBE_LIB, [PROBE_SRC] + _headers())
+
+
 def needs_build():
-    if not LIB.exists():
-        return True
-    t = LIB.stat().st_mtime
-    deps = _sources() + [CSRC / "entropy_ws.hip", CSRC / "entropy_mfma.hip"] + list(CSRC.glob("*.h")) + [HERE.parent / "include" / "vbmc_hip.h"]
-    return any(p.stat().st_mtime > t for p in deps)
+    return _lib_stale() or _probe_stale()
+
+
+def build_probe(verbose=True):
+    cmd = [HIPCC, *FLAGS, *ALL_EXTRA, "-shared", str(PROBE_SRC), "-o", str(PROBE_LIB), "-Wl,-rpath,/opt/rocm/lib"]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return PROBE_LIB
 
 
 def build(force=False, verbose=True):
-    if not force and not needs_build():
+    if force or _probe_stale():
+        build_probe(verbose)
+    if not force and not _lib_stale():
         return LIB
     objs = []
     procs = []
@@ -132,3 +158,4 @@ def build(force=False, verbose=True):
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     print(LIB)
+    print(PROBE_LIB)

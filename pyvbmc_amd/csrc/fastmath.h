@@ -3,8 +3,18 @@
 // The Monte-Carlo entropy spends most of its issue slots in exp(): ocml's exp() costs
 // ~110 cycles per wave (tools/ubench_fp64.hip), log() ~370.  These versions drop the
 // generality the kernels do not need (no NaN/Inf plumbing, known argument ranges) and
-// keep full double accuracy (<= 1-2 ulp; coefficients from tools/fit_polys.py, a
-// high-precision Chebyshev-node fit).
+// keep full double accuracy; coefficients from tools/fit_polys.py, a high-precision
+// Chebyshev-node fit (pinned by tests/test_fastmath_coeffs.py).
+//
+// Accuracy, measured on the MI355X by tests/test_fastmath_gpu.py (each function alone, through
+// csrc/devprobe.hip, against long double; ulps of float64 at the true value; inputs and figures
+// in profiles/fastmath_ulp.md), with the cap that test asserts:
+//   exp2_fast      0.92 ulp (cap 1), subnormal results included; 2^n exact for integer n
+//   log_fast       1.96 ulp (cap 2.5), worst in [1/2, sqrt(1/2)) where e ln2 and ln m cancel
+//   rcp_fast       0.50 ulp (cap 1); powers of two exact
+//   rsqrt_fast     1.00 ulp in a host model of this form, not yet measured on the device (cap 1.5; the form before,
+//                  which halved x, measured 1.57 in the lowest normal binade); 4^n exact
+//   sincospi_fast  1.68 / 1.70 ulp (cap 2), relative to the true value at the zeros as well
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,7 +60,7 @@ __device__ __forceinline__ double exp2_fast(double x) {
   {0x1.62e42fef84cf0p-1, 0x1.ebfbdff823cedp-3, 0x1.c6b08dd6fd234p-5, 0x1.3b2ab7181b755p-7, 0x1.5d8745a728441p-10, \
    0x1.4308ac85aa947p-13, 0x1.00dc4a532fb8ep-16, 0x1.63d136366db24p-20}
 
-// 1/x to ~1 ulp: v_rcp_f64 + two Newton steps.
+// 1/x where x and 1/x are normal (measured 0.50 ulp: above): v_rcp_f64 + two Newton steps.
 __device__ __forceinline__ double rcp_fast(double x) {
   double r = __builtin_amdgcn_rcp(x);
   r = fma(fma(-x, r, 1.0), r, r);
@@ -58,16 +68,18 @@ __device__ __forceinline__ double rcp_fast(double x) {
   return r;
 }
 
-// 1/sqrt(x) for normal x > 0 to ~1 ulp: v_rsq_f64 + two Newton steps.
+// 1/sqrt(x) for normal x > 0: v_rsq_f64 + two Newton steps r += (r / 2) (1 - x r^2).  The half is taken of the seed,
+// once (the second step's correction is 2^-50 of r, so the seed's 2^-25 does not show in it), never of x: 0.5 * x is
+// subnormal in the lowest normal binade and loses x's last bit there.
 __device__ __forceinline__ double rsqrt_fast(double x) {
   double r = __builtin_amdgcn_rsq(x);
-  const double h = 0.5 * x;
-  r = fma(r, fma(-h * r, r, 0.5), r);
-  r = fma(r, fma(-h * r, r, 0.5), r);
+  const double hr = 0.5 * r;
+  r = fma(hr, fma(-(x * r), r, 1.0), r);
+  r = fma(hr, fma(-(x * r), r, 1.0), r);
   return r;
 }
 
-// ln(x) for finite x > 0 (normal or subnormal); x == 0 -> -inf.
+// ln(x) for finite x > 0 (normal or subnormal); x == +-0 -> -inf.  Measured 1.96 ulp (above).
 // x = 2^e m, m in [sqrt(1/2), sqrt(2)); ln m = 2 atanh(s), s = (m-1)/(m+1).
 __device__ __forceinline__ double log_fast(double x) {
   if (x == 0.0) return -INFINITY;
@@ -95,7 +107,7 @@ __device__ __forceinline__ double log_fast(double x) {
   return fma(ed, 0x1.62e42fefa39efp-1, fma(ed, 0x1.abc9e3b39803fp-56, lm));  // e ln2 (hi+lo)
 }
 
-// sin(pi y), cos(pi y) for y in [0, 2).
+// sin(pi y), cos(pi y) for y in [0, 2); exact at y = 0, 1/2, 1, 3/2.  Measured 1.68 / 1.70 ulp (above).
 __device__ __forceinline__ void sincospi_fast(double y, double& s, double& c) {
   const double k = __builtin_rint(2.0 * y);  // 0..4
   const double r = fma(-0.5, k, y);          // [-1/4, 1/4], exact
@@ -122,7 +134,10 @@ __device__ __forceinline__ void sincospi_fast(double y, double& s, double& c) {
   c = ((q + 1) & 2) ? -cc : cc;
 }
 
-// Sum over the 64 lanes of a wave, result in every lane.  DPP row operations (no LDS traffic):
+// Sum over the 64 lanes of a wave, result in every lane.  Precondition of every reduction below: all 64 lanes of the
+// wave are active (every caller runs full waves; a partial EXEC mask is neither supported nor tested), and for
+// wave_max_dpp / wave_prod_dpp threadIdx.x & 63 is the lane (one-dimensional blocks of whole waves).
+// DPP row operations (no LDS traffic):
 // __shfl_xor compiles to ds_bpermute_b32 pairs with a wait after each step (~100 cycles per
 // step and double), this is 6 steps of two v_mov_dpp + one v_add_f64.
 //   quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror: every lane of a 16-lane

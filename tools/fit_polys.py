@@ -41,29 +41,53 @@ def show(name, coef):
     print("{" + ", ".join(float(c).hex() for c in coef) + "}")
 
 
-if __name__ == "__main__":
+# The fits fastmath.h takes its coefficients from (tests/test_fastmath_coeffs.py pins them to these definitions).
+
+
+def fit_exp2(n):
+    """2^f on |f| <= 1/2; exp2_fast uses degree 11, the entropy kernels degree 8 with c0 = 1."""
     half = mp.mpf(1) / 2
+    return cheb_fit(lambda x: mp.mpf(2) ** x, -half, half, n)
+
+
+def fit_atanh(n):
+    """atanh(s)/s in u = s^2 on 0 <= s <= (sqrt(2)-1)/(sqrt(2)+1); log_fast uses c[1:] of degree 8 (c0 = 1)."""
+    smax = (mp.sqrt(2) - 1) / (mp.sqrt(2) + 1)
+    return cheb_fit(lambda u: (mp.atanh(mp.sqrt(u)) / mp.sqrt(u)) if u > 0 else mp.mpf(1), mp.mpf(0), smax**2, n)
+
+
+def fit_sinpi(n):
+    """sin(pi x)/x in u = x^2 on |x| <= 1/4; sincospi_fast uses degree 6."""
+    q = mp.mpf(1) / 4
+    return cheb_fit(lambda u: (mp.sin(mp.pi * mp.sqrt(u)) / mp.sqrt(u)) if u > 0 else mp.pi, mp.mpf(0), q * q, n)
+
+
+def fit_cospi(n):
+    """cos(pi x) in u = x^2 on |x| <= 1/4; sincospi_fast uses degree 6 (c0 = 1)."""
+    q = mp.mpf(1) / 4
+    return cheb_fit(lambda u: mp.cos(mp.pi * mp.sqrt(u)), mp.mpf(0), q * q, n)
+
+
+if __name__ == "__main__":
     for n in (8, 9, 10, 11, 12):  # 8: the entropy kernels' (fastmath.h VBMC_ENT_EXP2_COEFFS, c0 = 1); 11: exp2_fast
-        c = cheb_fit(lambda x: mp.mpf(2) ** x, -half, half, n)
+        c = fit_exp2(n)
         f = np.linspace(-0.5, 0.5, 400001)
         err = np.max(np.abs(horner64(c, f) / np.exp2(f) - 1))
         show(f"exp2 degree {n}: max rel err {err:.3e}", c)
     # log: ln(m) = 2 s (1 + s^2/3 + s^4/5 + ...) , s = (m-1)/(m+1), m in [sqrt(1/2), sqrt(2)]
-    smax = (mp.sqrt(2) - 1) / (mp.sqrt(2) + 1)
     for n in (8, 9, 10):
-        c = cheb_fit(lambda u: (mp.atanh(mp.sqrt(u)) / mp.sqrt(u)) if u > 0 else mp.mpf(1), mp.mpf(0), smax**2, n)
+        c = fit_atanh(n)
         m = np.linspace(2**-0.5, 2**0.5, 400001)
         s = (m - 1) / (m + 1)
         val = 2 * s * horner64(c, s * s)
         ref = np.array([float(mp.log(mp.mpf(float(x)))) for x in m[::400]])
         err = np.max(np.abs(val[::400] - ref))
         show(f"atanh(s)/s in u=s^2 degree {n}: max abs err of ln m {err:.3e}", c)
-    q = mp.mpf(1) / 4
     for n in (6, 7):
-        c = cheb_fit(lambda u: (mp.sin(mp.pi * mp.sqrt(u)) / mp.sqrt(u)) if u > 0 else mp.pi, mp.mpf(0), q * q, n)
+        c = fit_sinpi(n)
         x = np.linspace(-0.25, 0.25, 200001)
         err = np.max(np.abs(x * horner64(c, x * x) - np.sin(np.pi * x)))
         show(f"sin(pi x)/x in u=x^2 degree {n}: max abs err {err:.3e}", c)
-        c = cheb_fit(lambda u: mp.cos(mp.pi * mp.sqrt(u)), mp.mpf(0), q * q, n)
+        c = fit_cospi(n)
         err = np.max(np.abs(horner64(c, x * x) - np.cos(np.pi * x)))
         show(f"cos(pi x) in u=x^2 degree {n}: max abs err {err:.3e}", c)
