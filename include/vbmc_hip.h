@@ -126,7 +126,8 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on);
  *            the product WITHOUT the finish in its epilogue (three launches where production runs two): it measures
  *            the product kernel, not the production configuration; a predict at level 0 / 1 invalidates the record
  *            (VBMC_E_ARG "no timed launch recorded", never a stale interval).
- *        6 = vbmc_gp_posterior's blocked Cholesky factorisation alone (all its block steps). */
+ *        6 = vbmc_gp_posterior's blocked Cholesky factorisation alone (all its block steps),
+ *        7 = vbmc_is_mcmc's launch (all S chains). */
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out);
 
 /* Host-side wall-clock breakdown (microseconds) of the most recent vbmc_neg_elcbo:
@@ -614,6 +615,24 @@ int vbmc_is_proposal(vbmc_ctx* ctx, int64_t Na, const double* Xa_NaxD, int K2, c
 int vbmc_is_box_sample(vbmc_ctx* ctx, int64_t n_box, uint64_t seed, const double* rect_delta_D, double* x_NboxxD);
 int vbmc_acq_is_build(vbmc_ctx* ctx, int64_t Na, const double* Xa, int per_sample_xa, const double* fs2a_NaxS,
                       const double* lnw_SxNa, double* K_out_SxNaxN, double* C_out_SxNxNa);
+
+/* The MCMC chains of step 2 (vbmc/active_importance_sampling.py:195-262) for the GP of vbmc_set_gp, all S of them in one
+ * launch (csrc/acq_is_mcmc.hip): chain s samples the acquisition's is_log_full over gp.predict(add_noise=True) of the
+ * one-sample GP s (:205-250),
+ *     f(x) = [ln_y_fmu ? f_mu(x) : 0] + u_q f_s + log1p(-exp(-2 u_q f_s)),   f_s = sqrt(f_s2(x) + sn2 sn2_mult),
+ * from x0_SxD[s] clipped into [lb_D, ub_D], with interval widths widths_D, and keeps n samples, one every `thin` sweeps
+ * after `burn_in` sweeps (:211-249).  The sampler is this library's own (gpyreg's is not part of the reference tree):
+ * Neal's coordinate-wise slice sampler, stepping out at most 32 evaluations a side and shrinking at most 64 times, on
+ * the Philox stream 6 of csrc/sample.hip with key `seed` -- tests/slice_host.py states it in NumPy.
+ * Outputs: X_SxnxD the kept points, logp_Sxn f at them, fmu_nxS / fs2_nxS the predictive mean and the noise-free
+ * variance at them (what the reference's second predict, :254, returns), stats_Sx4 per chain the evaluations of f, the
+ * draws consumed, and how often the step-out / the shrink cap ended a loop.  *invalid = 1 when f is not finite at some
+ * chain's start: that chain writes nothing (the caller raises the reference's ValueError("Invalid value.")).
+ * D <= 32 and N small enough for the chain's LDS (VBMC_E_UNSUP before anything is launched); n, thin >= 1, burn_in >= 0. */
+int vbmc_is_mcmc(vbmc_ctx* ctx, int ln_y_fmu, double u_q, const double* x0_SxD, const double* widths_D,
+                 const double* lb_D, const double* ub_D, int n, int thin, int burn_in, uint64_t seed,
+                 double* X_SxnxD, double* logp_Sxn, double* fmu_nxS, double* fs2_nxS,
+                 int64_t* stats_Sx4 /* evaluations, draws, step-out caps, shrink caps */, int* invalid);
 
 /* AbstractAcqFcn._sq_dist (acquisition_functions/abstract_acq_fcn.py:195-222):
  * c[i][j] = max(|a_i - mu|^2 + |b_j - mu|^2 - 2 (a_i - mu).(b_j - mu), 0), mu the common

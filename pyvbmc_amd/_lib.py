@@ -193,6 +193,8 @@ SIGNATURES = {
                                    C.POINTER(C.c_int)]),
     "vbmc_is_box_sample": (C.c_int, [_vp, C.c_int64, C.c_uint64, _dp, _dp]),
     "vbmc_acq_is_build": (C.c_int, [_vp, C.c_int64, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "vbmc_is_mcmc": (C.c_int, [_vp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_uint64, _dp, _dp,
+                               _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "vbmc_sq_dist": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
     "vbmc_mixture_sample": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, C.POINTER(C.c_int32)]),
     "vbmc_mixture_sample_t": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, C.c_double, _dp, C.POINTER(C.c_int32)]),

@@ -15,8 +15,18 @@ Where the work runs:
   context already holds (``vbmc_acq_is_build``, csrc/api_acq_is.hip).  The result stays in the context as the state
   ``vbmc_acq_is_eval`` reads, so the mirror acquisition classes upload nothing when they receive the returned dict;
   ``products=False`` also keeps ``K_Xa_X`` / ``C_tmp`` (S N Na doubles each) off the bus and out of the dict;
-* step 2, the optional MCMC (:195-262), stays a host loop around a slice sampler with the reference's data flow; its
-  ``log_p`` is the acquisition's ``is_log_full`` on the device ``gp.predict``.
+* step 2, the optional MCMC (:195-262), is by default a host loop around a slice-sampler class with the reference's data
+  flow; its ``log_p`` is the acquisition's ``is_log_full`` on the device ``gp.predict``, one point per call.  With
+  ``sampler="device"`` (or ``VBMC_HIP_AIS_SAMPLER=device`` when ``sampler`` is None) the S chains run as ONE launch
+  instead (``vbmc_is_mcmc``, csrc/acq_is_mcmc.hip): one batched ``predict`` on the old points, the resampling weights
+  and one ``np.random.choice`` per GP sample exactly as in the host loop, then all chains at once; the launch also
+  returns ``f_mu`` / ``f_s2`` at the kept points, so the second ``predict`` (:254) is not run.  The device sampler is
+  this package's own -- Neal's coordinate-wise slice sampler with stepping out and shrinkage on the Philox stream 6,
+  stated in NumPy by tests/slice_host.py -- and NOT gpyreg's: it targets the same density, but its draws are its own
+  stream, neither ``np.random``'s nor gpyreg's.  ``seed`` is taken as for ``rng="philox"``.  Cap counters that are not
+  zero come back under ``ais["mcmc_stats"]``.  Step 0's MCMC pass (VIQR with ``mcmc_importance_sampling``) hands a
+  matrix of walkers to the sampler and stays on the class route: ``sampler="device"`` there raises
+  ``NotImplementedError``.
 
 Draws: by default (``rng="numpy"``) ``np.random`` is consumed exactly as the reference consumes it -- the same calls in
 the same order -- so the same global state gives the reference's ``X``.  ``rng="philox"`` (or ``VBMC_HIP_RNG=philox``)
@@ -26,6 +36,7 @@ takes the smoothed-posterior samples from the device sampler and the box samples
 A shape the kernels do not cover (D > 32) raises ``_lib.UnsupportedShape`` before anything is drawn or changed.
 """
 import ctypes as C
+import os
 import sys
 from math import ceil
 
@@ -144,6 +155,15 @@ def _check_shape(D):
         raise _lib.UnsupportedShape(f"active_importance_sampling: D={D} > 32 not supported")
 
 
+MCMC_DEVICE_MAX_N = 9984  # a device chain keeps k and the product's stripe sums in LDS: 2 N doubles in 156 KiB
+
+
+def _check_mcmc_shape(N):
+    if N > MCMC_DEVICE_MAX_N:
+        raise _lib.UnsupportedShape(f"active_importance_sampling: sampler='device' with N={N} > {MCMC_DEVICE_MAX_N} "
+                                    "training points not supported")
+
+
 # ------------------------------------------------------------------------------------------------ the reference's names
 def fess(vp, gp, X=100):
     """Fractional effective sample size by importance sampling (:426-478): ``gp`` is a GP (its averaged predictive
@@ -205,6 +225,49 @@ def _default_sampler():
     return SliceSampler
 
 
+def _device_sampler(sampler):
+    """Whether step 2 runs as the device launch: ``sampler="device"``, or the environment's switch when it is None."""
+    if sampler is None:
+        return os.environ.get("VBMC_HIP_AIS_SAMPLER", "") == "device"
+    return isinstance(sampler, str) and sampler == "device"
+
+
+def _mcmc_device(ctx, gp, acq_fcn, old, n_mcmc, thin, burn_in, widths, lb, ub, seed):
+    """Step 2 (:195-262) with the chains on the device: ``(ais, stats)`` -- the new dict and the (S, 4) counters
+    [evaluations, draws, step-out caps, shrink caps] of ``vbmc_is_mcmc``."""
+    X = np.asarray(gp.X, dtype=np.float64)
+    S, D = len(gp.posteriors), X.shape[1]
+    # the resampling weights of every GP sample from one batched predict on the old points (:211-226)
+    f_mu, f_s2 = _predict(gp, ctx, old["X"], separate_samples=True)
+    x0 = np.empty((S, D))
+    for s in range(S):
+        ln_w = old["ln_weights"][s, :].reshape(-1, 1) + acq_fcn.is_log_added(f_mu=f_mu[:, s:s + 1], f_s2=f_s2[:, s:s + 1])
+        ln_w_max = np.amax(ln_w, axis=1).reshape(-1, 1)
+        if np.any(ln_w_max == -np.inf):
+            raise ValueError("Invalid value.")
+        weights = np.exp(ln_w - ln_w_max).ravel()
+        weights = weights / np.sum(weights)
+        index = np.random.choice(a=len(weights), p=weights, replace=False)
+        x0[s] = np.maximum(np.minimum(old["X"][index, :], ub), lb)
+    Xa, log_p = np.empty((S, n_mcmc, D)), np.empty((S, n_mcmc))
+    c_mu, c_s2 = np.empty((n_mcmc, S)), np.empty((n_mcmc, S))
+    stats = np.zeros((S, 4), dtype=np.int64)
+    invalid = C.c_int(0)
+    u_q = float(acq_fcn.u)
+    ln_y_fmu = 0 if acq_fcn.acq_info.get("variational_importance_sampling") else 1
+    ctx.check(ctx._lib.vbmc_is_mcmc(ctx._h, ln_y_fmu, u_q, _lib.ptr(_lib.f64(x0)), _lib.ptr(_lib.f64(widths)),
+                                    _lib.ptr(_lib.f64(lb)), _lib.ptr(_lib.f64(ub)), int(n_mcmc), int(thin), int(burn_in),
+                                    C.c_uint64(int(seed)), _lib.ptr(Xa), _lib.ptr(log_p), _lib.ptr(c_mu), _lib.ptr(c_s2),
+                                    stats.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(invalid)))
+    if invalid.value:
+        raise ValueError("Invalid value.")
+    ais = {"ln_weights": np.zeros((S, n_mcmc)), "X": Xa, "f_s2": c_s2}
+    for s in range(S):
+        ln_y = acq_fcn.is_log_base(Xa[s], f_mu=c_mu[:, s:s + 1], f_s2=c_s2[:, s:s + 1])
+        ais["ln_weights"][s, :] = ln_y.T - log_p[s]
+    return ais, stats
+
+
 def _box_samples(gp, ctx, n_box, rect_delta, mode, seed):
     """Box-uniform proposals around random training points (:164-168)."""
     X = gp.X
@@ -243,8 +306,9 @@ def active_importance_sampling(vp, gp, acq_fcn, options, *, rng=None, seed=None,
     ``ln_weights`` (S, Na, renormalised), ``K_Xa_X`` (S, Na, N) and ``C_tmp`` (S, N, Na).
 
     Keyword-only extras: ``rng`` / ``seed`` (the draw source, module docstring), ``sampler`` (the slice-sampler class
-    of step 2; default ``gpyreg.slice_sample.SliceSampler``) and ``products`` (False: ``K_Xa_X`` / ``C_tmp`` stay on the
-    device, for callers that evaluate with this package's acquisition classes)."""
+    of the MCMC steps, default ``gpyreg.slice_sample.SliceSampler``; or ``"device"``: step 2's chains as one launch,
+    module docstring) and ``products`` (False: ``K_Xa_X`` / ``C_tmp`` stay on the device, for callers that evaluate
+    with this package's acquisition classes)."""
     X = np.asarray(gp.X, dtype=np.float64)
     N, D = X.shape
     _check_shape(D)
@@ -259,8 +323,14 @@ def active_importance_sampling(vp, gp, acq_fcn, options, *, rng=None, seed=None,
     ub_tran = np.amax(X, axis=0) + 0.5 * diam
 
     ais = {"ln_weights": None, "X": None, "f_s2": None}
+    on_device = _device_sampler(sampler)
     if info.get("variational_importance_sampling", False):
         # step 0: samples of the variational posterior itself (:60-114)
+        if sampler is not None and on_device and info.get("mcmc_importance_sampling"):
+            raise NotImplementedError("active_importance_sampling: sampler='device' runs the chains of step 2; step 0's "
+                                      "MCMC pass hands a matrix of walkers to the sampler and needs a sampler class")
+        if on_device:
+            sampler = None  # (the environment's switch: step 0 keeps the class route)
         Na = ceil(_eval_option(options, "active_importance_sampling_mcmc_samples", {"K": vp.K, "n_vars": D, "D": D}))
         if not np.isfinite(Na) or not np.isscalar(Na) or Na <= 0:
             raise ValueError("options['active_importance_sampling_mcmc_samples']"
@@ -286,6 +356,8 @@ def active_importance_sampling(vp, gp, acq_fcn, options, *, rng=None, seed=None,
         n_vp = options["active_importance_sampling_vp_samples"]
         n_box = options["active_importance_sampling_box_samples"]
         n_mcmc = options["active_importance_sampling_mcmc_samples"]
+        if n_mcmc > 0 and on_device:
+            _check_mcmc_shape(N)  # (before anything is drawn)
         w_vp = n_vp / (n_vp + n_box)
         rect_delta = 2 * np.std(X, ddof=1, axis=0)
         ctx = ctx_of(vp)
@@ -304,7 +376,17 @@ def active_importance_sampling(vp, gp, acq_fcn, options, *, rng=None, seed=None,
         ais["f_s2"] = np.concatenate([p[2] for p in parts], axis=0)
         ais["ln_weights"][~np.isfinite(ais["ln_weights"])] = -np.inf
 
-        if n_mcmc > 0:
+        if n_mcmc > 0 and on_device:
+            # step 2 as one launch: every GP sample's chain at once (:195-262)
+            thin = options["active_importance_sampling_mcmc_thin"]
+            if mode != "philox":
+                seed = _seed_or_draw(seed)
+            ais, stats = _mcmc_device(ctx, gp, acq_fcn, ais, int(n_mcmc), thin, ceil(thin * n_mcmc / 2), widths, lb_tran,
+                                      ub_tran, seed)
+            ctx.__dict__["_is_mcmc_stats"] = stats  # (the last launch's counters, for measurement tools)
+            if np.any(stats[:, 2:]):
+                ais["mcmc_stats"] = stats
+        elif n_mcmc > 0:
             # step 2: one chain per GP sample, started from a resampled proposal (:195-262)
             old = ais
             ais = {"ln_weights": np.zeros((S, n_mcmc)), "X": np.zeros((S, n_mcmc, D)), "f_s2": np.zeros((n_mcmc, S))}

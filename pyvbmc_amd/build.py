@@ -32,6 +32,7 @@ SOURCES = [
     "api_acq.hip",
     "api_acq_is.hip",
     "acq_is_prep.hip",
+    "acq_is_mcmc.hip",
     "sample.hip",
     "transform.hip",
     "kde.hip",

@@ -42,12 +42,7 @@ __global__ __launch_bounds__(256) void se_cross_kernel(const double* __restrict_
   if (idx >= M * NB) return;
   const int64_t m = idx / NB;
   const int n = (int)(idx - m * NB);
-  double d2 = 0.0;
-  for (int d = 0; d < D; ++d) {
-    const double t = (A[m * D + d] - B[(size_t)n * D + d]) * exp(-hyp[d]);
-    d2 = fma(t, t, d2);
-  }
-  K[idx] = exp(2.0 * hyp[D] - 0.5 * d2);
+  K[idx] = se_ard_direct(A + m * D, B + (size_t)n * D, D, [&](int d) { return exp(-hyp[d]); }, 2.0 * hyp[D]);
 }
 
 // One wave per point m: acq_s[m] = logsumexp_a zz(m, a) for GP sample s.
@@ -328,5 +323,61 @@ extern "C" int vbmc_acq_is_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, 
     memcpy(acq_M + o, ctx->h_pinned, sizeof(double) * m);
     if (var_tot_M) memcpy(var_tot_M + o, ctx->h_pinned + mb, sizeof(double) * m);
   }
+  return VBMC_OK;
+}
+
+// Step 2 of active_importance_sampling (vbmc/active_importance_sampling.py:195-262): the S chains in one launch
+// (acq_is_mcmc.hip).  Scratch: [x0 S x D | widths | lb | ub] uploaded, [X | logp | fmu | fs2 | stats | invalid] downloaded.
+extern "C" int vbmc_is_mcmc(vbmc_ctx* ctx, int ln_y_fmu, double u_q, const double* x0_SxD, const double* widths_D,
+                            const double* lb_D, const double* ub_D, int n, int thin, int burn_in, uint64_t seed,
+                            double* X_SxnxD, double* logp_Sxn, double* fmu_nxS, double* fs2_nxS, int64_t* stats_Sx4,
+                            int* invalid) {
+  if (!ctx || !x0_SxD || !widths_D || !lb_D || !ub_D || !X_SxnxD || !logp_Sxn || !fmu_nxS || !fs2_nxS || !stats_Sx4 ||
+      !invalid || n < 1 || thin < 1 || burn_in < 0)
+    return VBMC_E_ARG;
+  NEED_DEVICE(ctx);
+  if (!ctx->gp.set) return vbmc_fail(ctx, VBMC_E_ARG, "is_mcmc: GP not set");
+  const GpState& g = ctx->gp;
+  const int S = g.S, N = g.N, D = g.D;
+  if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "is_mcmc: D=%d > 32 not supported", D);
+  if (is_mcmc_lds_bytes(N, ctx->opt_is_mcmc_threads) > 156 * 1024)
+    return vbmc_fail(ctx, VBMC_E_UNSUP, "is_mcmc: N=%d training points do not fit a chain's LDS", N);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t n_in = (size_t)S * D + 3 * (size_t)D, n_x = (size_t)S * n * D, n_sn = (size_t)S * n;
+  const size_t n_out = n_x + 3 * n_sn + 4 * (size_t)S + ((size_t)S + 1) / 2;  // (stats: 8-byte words; invalid: ints)
+  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, n_in + n_out);
+  if (rc) return rc;
+  if ((rc = ensure_pinned(ctx, n_out))) return rc;
+  std::vector<double> in(n_in);
+  memcpy(in.data(), x0_SxD, sizeof(double) * S * D);
+  memcpy(in.data() + (size_t)S * D, widths_D, sizeof(double) * D);
+  memcpy(in.data() + (size_t)S * D + D, lb_D, sizeof(double) * D);
+  memcpy(in.data() + (size_t)S * D + 2 * D, ub_D, sizeof(double) * D);
+  double* d_in = ctx->d_scratch;
+  double *d_X = d_in + n_in, *d_logp = d_X + n_x, *d_fmu = d_logp + n_sn, *d_fs2 = d_fmu + n_sn;
+  long long* d_stats = (long long*)(d_fs2 + n_sn);
+  int* d_inv = (int*)(d_stats + 4 * (size_t)S);
+  HIP_TRY(ctx, hipMemcpyAsync(d_in, in.data(), sizeof(double) * n_in, hipMemcpyHostToDevice, ctx->stream));
+  // (a chain whose start is invalid writes nothing: its rows come back as zeros)
+  HIP_TRY(ctx, hipMemsetAsync(d_X, 0, sizeof(double) * n_out, ctx->stream));
+  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[14], ctx->stream));
+  rc = launch_is_mcmc(ctx, ln_y_fmu ? 1 : 0, u_q, d_in, d_in + (size_t)S * D, d_in + (size_t)S * D + D,
+                      d_in + (size_t)S * D + 2 * D, n, thin, burn_in, seed, d_X, d_logp, d_fmu, d_fs2, d_stats, d_inv);
+  if (rc) return rc;
+  if (ctx->timing) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[15], ctx->stream));
+    ctx->ev_valid[7] = true;
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, d_X, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, stream_wait(ctx));  // (`in` is a local)
+  const double* h = ctx->h_pinned;
+  memcpy(X_SxnxD, h, sizeof(double) * n_x);
+  memcpy(logp_Sxn, h + n_x, sizeof(double) * n_sn);
+  memcpy(fmu_nxS, h + n_x + n_sn, sizeof(double) * n_sn);
+  memcpy(fs2_nxS, h + n_x + 2 * n_sn, sizeof(double) * n_sn);
+  memcpy(stats_Sx4, h + n_x + 3 * n_sn, sizeof(int64_t) * 4 * S);
+  const int* h_inv = (const int*)(h + n_x + 3 * n_sn + 4 * (size_t)S);
+  *invalid = 0;
+  for (int s = 0; s < S; ++s) *invalid |= h_inv[s] != 0;
   return VBMC_OK;
 }

@@ -145,8 +145,8 @@ struct ElboScratch {
 struct vbmc_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[14] = {};  // pairs: (0,1) entmc, (2,3) glj, (4,5) pdf, (6,7) predict, (8,9) elbo, (10,11) predict's variance product, (12,13) the GP posterior's factorisation
-  bool ev_valid[7] = {false, false, false, false, false, false, false};
+  hipEvent_t ev[16] = {};  // pairs: (0,1) entmc, (2,3) glj, (4,5) pdf, (6,7) predict, (8,9) elbo, (10,11) predict's variance product, (12,13) the GP posterior's factorisation, (14,15) the MCMC chains of vbmc_is_mcmc
+  bool ev_valid[8] = {false, false, false, false, false, false, false, false};
   std::string err;
   hipDeviceProp_t prop;
 
@@ -249,6 +249,7 @@ struct vbmc_ctx {
   int opt_predict_fused = 1;  // ... with predict's finish in its epilogue: 0 never, 1 for one-round product grids, 2 always (gp.hip)
   int opt_arm_late_test = 0;  // test hook: n > 0 = the n-th use of an armed evaluation from now takes the late-go recovery path
   int opt_acq_poll = 1;       // small acquisition batches: points written by the CPU, results polled (api_acq.hip)
+  int opt_is_mcmc_threads = 512;  // workgroup size of vbmc_is_mcmc's chains: 256, 512 or 768 (acq_is_mcmc.hip)
   void (*release_cb)(void*) = nullptr;  // vbmc_set_release_callback
   void* release_cb_user = nullptr;
   int opt_adam_fused = 1;     // the optimiser loop as one launch per batch where its shape applies (adam_fused.hip)
@@ -645,6 +646,12 @@ int launch_gp_panel_product(vbmc_ctx* ctx, const double* d_A, const double* d_B,
                             bool upper_b = false);
 int launch_gp_predict_all(vbmc_ctx* ctx, int64_t M, const double* d_xs, double* d_Ks, double* d_part,
                           int add_noise, double* d_fmu, double* d_fs2, int64_t ld);
+// acq_is_mcmc.hip: the S slice-sampling chains of active_importance_sampling's step 2, one workgroup each, on ctx->stream
+// (all pointers device memory; d_invalid [S] zeroed by the caller), and the dynamic LDS a workgroup of `threads` needs
+size_t is_mcmc_lds_bytes(int N, int threads);
+int launch_is_mcmc(vbmc_ctx* ctx, int ln_y_fmu, double u_q, const double* d_x0, const double* d_widths, const double* d_lb,
+                   const double* d_ub, int n, int thin, int burn_in, uint64_t seed, double* d_X, double* d_logp,
+                   double* d_fmu, double* d_fs2, long long* d_stats, int* d_invalid);
 // c[n][m] = |a_n - b_m|^2 (centred expansion, cross term on the FP64 matrix cores), optional
 // row-wise argmin; d_cen[D] = the centre subtracted from both sets
 int launch_sq_dist(vbmc_ctx* ctx, const double* d_a, int64_t n, const double* d_b, int m, int D,

@@ -204,7 +204,7 @@ int vbmc_ctx_create(int device_id, vbmc_ctx** out) {
   if (e == hipSuccess) e = hipGetDeviceProperties(&ctx->prop, device_id);
   if (e == hipSuccess) bind_host_thread(ctx);  // (before the pinned allocations below: they follow the thread's node)
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-  for (int i = 0; i < 14 && e == hipSuccess; ++i) e = hipEventCreate(&ctx->ev[i]);
+  for (int i = 0; i < 16 && e == hipSuccess; ++i) e = hipEventCreate(&ctx->ev[i]);
   if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_done, 64, hipHostMallocDefault);
   if (e == hipSuccess) {
     for (int i = 0; i < 8; ++i) ctx->h_done[i] = 0;
@@ -318,6 +318,7 @@ int vbmc_set_option(vbmc_ctx* ctx, const char* key, int value) {
   else if (!strcmp(key, "ws_front")) ctx->opt_ws_front = value < 0 ? 0 : value > 990 ? 990 : value;
   else if (!strcmp(key, "elbo_arm")) ctx->opt_elbo_arm = value < 0 ? 0 : value > 2 ? 2 : value;  // 1: only while this context is alone on its device; 2: always
   else if (!strcmp(key, "acq_poll")) ctx->opt_acq_poll = value != 0;
+  else if (!strcmp(key, "is_mcmc_threads")) ctx->opt_is_mcmc_threads = value <= 256 ? 256 : value >= 768 ? 768 : 512;  // workgroup size of vbmc_is_mcmc's chains
   else if (!strcmp(key, "randn_device")) ctx->opt_randn_dev = value < 0 ? 0 : value > 3 ? 3 : value;  // vbmc_set_eps_numpy: the NumPy stream on the device (device_randn.hip); 0 = strict parity (host generator, values bit-identical to np.random.randn); 2 = test hook: the device pass reports its margin exceeded; 3 = test hook: the window is always computed, never taken from the pass before
   else if (!strcmp(key, "adam_tail")) ctx->opt_adam_tail = value;  // the optimiser loop's two-launch iteration (adam.hip)
   else if (!strcmp(key, "adam_fused")) ctx->opt_adam_fused = value;  // 2: test hook, see FusedArgs::test_absent; 3: release / acquire flags (FusedArgs::rel_acq)
@@ -357,7 +358,7 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on) {
 }
 
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out) {
-  if (!ctx || which < 0 || which > 6 || !ms_out) return VBMC_E_ARG;
+  if (!ctx || which < 0 || which > 7 || !ms_out) return VBMC_E_ARG;
   NEED_DEVICE(ctx);
   if (!ctx->ev_valid[which])
     return vbmc_fail(ctx, VBMC_E_ARG, which == 5 ? "no timed launch recorded for 5 (gp_predict's product alone is timed at vbmc_set_timing(ctx, 2) only)"

@@ -18,6 +18,26 @@ inline PredView gp_pred_view(const GpState& g, const double* d_xs, int add_noise
   return {g.d_hyp, g.d_smeta, d_xs, g.D, g.P, g.mean_kind, add_noise};
 }
 
+// The squared-exponential ARD kernel by direct differences (no |a|^2 + |b|^2 - 2 a.b expansion):
+//   k(a, b) = exp(lsf2 - 1/2 sum_d ((a_d - b_d) iell(d))^2),  lsf2 = 2 hyp[D], iell(d) = exp(-hyp[d])
+// iell is a callable, so a caller that evaluates many pairs may hand over stored values instead of the exponentials.
+template <class InvEll>
+__device__ __forceinline__ double se_ard_direct(const double* __restrict__ a, const double* __restrict__ b, int D,
+                                                InvEll iell, double lsf2) {
+  double d2 = 0.0;
+  for (int d = 0; d < D; ++d) {
+    const double t = (a[d] - b[d]) * iell(d);
+    d2 = fma(t, t, d2);
+  }
+  return exp(lsf2 - 0.5 * d2);
+}
+
+// the observation noise predict(add_noise=True) adds under GP sample smp: sn2 sn2_mult
+__device__ __forceinline__ double predict_noise_add(const PredView& v, int smp) {
+  const double* hyp = v.hyp_all + (size_t)smp * v.P;
+  return exp(2.0 * hyp[v.D + 1]) * v.smeta[3 * smp + 1];
+}
+
 // predict, stage 3 for point m under GP sample smp: fmu = mean(x*) + f, fs2 = max(0, sf^2 -/+ s) (+ noise), with
 // s / f the sums of the stage-2 partial row sums / the stage-1 partial means.
 __device__ __forceinline__ void predict_point_moments(const PredView& v, int smp, int64_t m, double s, double f,
@@ -26,7 +46,7 @@ __device__ __forceinline__ void predict_point_moments(const PredView& v, int smp
   const int D = v.D;
   const bool chol = v.smeta[3 * smp] != 0.0;
   const double sf2 = exp(2.0 * hyp[D]);
-  const double add = v.add_noise ? exp(2.0 * hyp[D + 1]) * v.smeta[3 * smp + 1] : 0.0;
+  const double add = v.add_noise ? predict_noise_add(v, smp) : 0.0;
   fs2 = fmax(chol ? sf2 - s : sf2 + s, 0.0) + add;
   // mean function at x* (variational_optimization.py:1383-1392 layout)
   double mean = 0.0;

@@ -29,7 +29,10 @@ module.  Nothing here imports the reference: ``vo`` is passed in (or imported on
 ``patch_active_sampling(mod)`` is a separate, explicit step (``patch`` does not take it): it rebinds
 ``active_importance_sampling`` on ``pyvbmc.vbmc.active_sample`` -- the name that module binds by value at import
 (active_sample.py:15) -- to this package's mirror, with the same fallback to the reference's function for shapes the
-kernels do not cover; ``unpatch_active_sampling(mod)`` puts the reference's function back.
+kernels do not cover; ``unpatch_active_sampling(mod)`` puts the reference's function back.  The reference calls it
+without the mirror's keyword-only extras, so under the drop-in they are chosen by the environment: ``VBMC_HIP_RNG=philox``
+(the proposals drawn on the device) and ``VBMC_HIP_AIS_SAMPLER=device`` (the MCMC chains of step 2 as one launch, on the
+mirror's own slice sampler and stream).
 """
 import numpy as np
 

@@ -10,10 +10,21 @@ row is timed under both draw sources and with ``products`` on and off; the host 
 ``np.random`` and then uploads its state.  Median, minimum and maximum of --reps calls after two warm-up calls (host:
 of max(3, reps // 2) calls after one); ``host_over_device`` is the ratio of the medians.  One JSON line per row, also
 written to --out.  The last line holds the largest
-max|C_tmp(device) - C_tmp(host solves)| / max|C_tmp| over the rows' shapes (``ctmp_rel_err``)."""
+max|C_tmp(device) - C_tmp(host solves)| / max|C_tmp| over the rows' shapes (``ctmp_rel_err``).
+
+    python tools/ais_rows.py --mcmc [--limit 400]
+
+measures step 2, the MCMC, instead: IMIQR with 100 + 100 proposals and 100 MCMC samples at the reference's default thin
+(1) and burn-in (50), at (D, N, S) = (10, 400, 8) and (20, 800, 8).  Per shape, in a fresh child process under
+``timeout -k 10 <--limit>`` (after a child that does not exit with 0 nothing further is started): the whole call
+without MCMC; with step 2 through the mirror's host loop handed ``tests/slice_host.sampler_class`` (the device chains'
+algorithm, one device ``predict`` per evaluation); with ``sampler="device"`` at every workgroup size; the chains'
+evaluation counts; and the launch's time between HIP events (``vbmc_last_kernel_ms(7)``).  ``step2_*_ms`` is the call's
+time minus the call without MCMC.  The rows replace the ``mcmc_*`` rows of --out and leave its other rows alone."""
 import argparse
 import json
 import statistics
+import subprocess
 import sys
 import time
 from pathlib import Path
@@ -54,11 +65,97 @@ def timed(fn, reps, warm):
     return statistics.median(t), min(t), max(t)
 
 
+MCMC_SHAPES = [(10, 400, 8, 100), (20, 800, 8, 100)]  # (D, N, S, n_mcmc)
+
+
+def mcmc_shape(i, reps):
+    """(child) the rows of MCMC shape i, one JSON line each."""
+    import slice_host
+
+    D, N, S, n_mcmc = MCMC_SHAPES[i]
+    ogp, mix = make_case(D, N, S, 100 + S)
+    gp, vp, acq = PlainGP(ogp), PlainVP(mix), AcqFcnIMIQR()
+    ctx = _lib.Context(0)
+    _lib.set_default_context(ctx)
+
+    def opts(n):
+        return ais_host.Opts(active_importance_sampling_vp_samples=100, active_importance_sampling_box_samples=100,
+                             active_importance_sampling_mcmc_samples=n, active_importance_sampling_mcmc_thin=1)
+
+    def call(n, **kw):
+        np.random.seed(1)
+        t0 = time.perf_counter()
+        out = active_importance_sampling(vp, gp, acq, opts(n), products=False, **kw)
+        return (time.perf_counter() - t0) * 1e3, out
+
+    call(0)  # (uploads the GP)
+    base = statistics.median(call(0)[0] for _ in range(reps))
+    tag = f"mcmc_D{D}_N{N}_S{S}_n{n_mcmc}"
+    rows = [{"row": f"{tag}_no_mcmc", "call_ms": round(base, 3)}]
+    ctx.set_timing(1)
+    best = None
+    for nt in (256, 512, 768):
+        ctx.set_option("is_mcmc_threads", nt)
+        call(n_mcmc, sampler="device", seed=3)
+        ms, kms = [], []
+        for _ in range(reps):
+            ms.append(call(n_mcmc, sampler="device", seed=3)[0])
+            kms.append(ctx.last_kernel_ms(7))
+        st = ctx.__dict__["_is_mcmc_stats"]
+        row = {"row": f"{tag}_device_threads{nt}", "call_ms": round(statistics.median(ms), 3),
+               "step2_device_ms": round(statistics.median(ms) - base, 3), "kernel_ms": round(statistics.median(kms), 3),
+               "evaluations_per_chain": st[:, 0].tolist(), "caps_hit": int(st[:, 2:].sum()),
+               "us_per_evaluation": round(1e3 * statistics.median(kms) / float(st[:, 0].max()), 3)}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        best = row if best is None or row["kernel_ms"] < best["kernel_ms"] else best
+    ctx.set_timing(0)
+    ctx.set_option("is_mcmc_threads", 512)
+    cls = slice_host.sampler_class(3)
+    host_ms, _ = call(n_mcmc, sampler=cls)  # once: tens of seconds
+    row = {"row": f"{tag}_host_loop", "call_ms": round(host_ms, 3), "step2_host_loop_ms": round(host_ms - base, 3),
+           "evaluations_per_chain": [int(r["stats"][0]) for r in cls.results],
+           "host_loop_over_device": round((host_ms - base) / best["step2_device_ms"], 1), "device_row": best["row"]}
+    rows.append(row)
+    print(json.dumps(row), flush=True)
+    print(json.dumps(rows[0]), flush=True)
+    ctx.close()
+
+
+def mcmc_rows(a):
+    """(parent) every MCMC shape in a child of its own; the rows merged into --out."""
+    lines = []
+    for i, shape in enumerate(MCMC_SHAPES):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--mcmc-shape", str(i),
+               "--reps", str(a.reps)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+        got = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        print("\n".join(got), flush=True)
+        lines += got
+        if p.returncode != 0:
+            print(f"shape {shape}: child ended with status {p.returncode}; nothing further is started", file=sys.stderr)
+            lines.append(json.dumps({"row": "mcmc_D%d_N%d_S%d_n%d" % shape,
+                                     "status": f"not measured: the child process ended with status {p.returncode}"}))
+            break
+    out = Path(a.out)
+    keep = [ln for ln in out.read_text().splitlines() if ln.strip() and not json.loads(ln)["row"].startswith("mcmc_")] \
+        if out.exists() else []
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text("\n".join(keep + lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "ais_rows.json"))
+    ap.add_argument("--mcmc", action="store_true", help="measure step 2 (the MCMC) instead; rows merged into --out")
+    ap.add_argument("--limit", type=int, default=400, help="--mcmc: seconds a shape's child process may take")
+    ap.add_argument("--mcmc-shape", type=int, default=None, help="(child) run MCMC shape number MCMC_SHAPE in this process")
     a = ap.parse_args()
+    if a.mcmc_shape is not None:
+        return mcmc_shape(a.mcmc_shape, min(a.reps, 3))
+    if a.mcmc:
+        return mcmc_rows(a)
     ctx = _lib.Context(0)
     _lib.set_default_context(ctx)
     D, N = 20, 800
