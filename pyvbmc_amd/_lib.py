@@ -21,6 +21,8 @@ E_ARG, E_HIP, E_RCCL, E_NODEV, E_UNSUP, E_NONFINITE = -1, -2, -3, -4, -5, -6
 E_NOTPD = -8  # vbmc_gp_posterior / vbmc_gp_append: not positive definite
 W_GP_CHANGED = 1  # vbmc_neg_elcbo: the watched GP arrays changed under it (vbmc_set_gp_watch)
 W_NOT_FUSED = 2   # vbmc_adam_run_auto: the one-launch loop does not apply (or gave up): run batches with vbmc_adam_run
+# the timed intervals of Context.last_kernel_ms (csrc/common.h TimingPair; the numbers are ABI)
+T_ENTMC, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC = range(8)
 
 
 class VbmcHipError(RuntimeError):
@@ -339,7 +341,7 @@ class Context:
 
     def set_timing(self, on):
         """HIP event pair around the dominant kernels (off by default: each record costs ~6 us).  ``on=2`` also records
-        the pair around predict's variance product (``last_kernel_ms(5)``), which sits between predict's launches."""
+        the pair around predict's variance product (``last_kernel_ms(T_PREDICT_VAR)``), which sits between predict's launches."""
         self.check(self._lib.vbmc_set_timing(self._h, int(on) if on else 0))
 
     def set_option(self, key, value):
@@ -378,7 +380,7 @@ class Context:
         self.check(self._lib.vbmc_last_elbo_raw(self._h, ptr(out), out.size))
         return out
 
-    def last_kernel_ms(self, which=0):
+    def last_kernel_ms(self, which=T_ENTMC):
         v = C.c_double()
         self.check(self._lib.vbmc_last_kernel_ms(self._h, which, C.byref(v)))
         return v.value

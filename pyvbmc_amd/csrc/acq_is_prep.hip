@@ -152,7 +152,9 @@ extern "C" int vbmc_is_proposal(vbmc_ctx* ctx, int64_t Na, const double* Xa_NaxD
   int rc = ensure_dev(ctx, &ctx->d_out, &ctx->d_out_cap, fixed.size());
   if (rc) return rc;
   PredictPlan p;
-  rc = predict_plan(ctx, Na, (int64_t)1 << 27, (int64_t)S * N, 65536, 2 * (size_t)S, 2 * (size_t)S, p);
+  predict_plan(ctx, Na, (int64_t)1 << 27, (int64_t)S * N, 65536, p);
+  const auto p_lnw = p.sc.add((size_t)S * p.mb), p_fs2o = p.sc.add((size_t)S * p.mb);
+  rc = predict_reserve(ctx, p, 2 * (size_t)S);
   if (rc) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_out, fixed.data(), sizeof(double) * fixed.size(), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));  // (`fixed` is a local)
@@ -168,9 +170,11 @@ extern "C" int vbmc_is_proposal(vbmc_ctx* ctx, int64_t Na, const double* Xa_NaxD
   a.log_wvp = has_vp ? std::log(w_vp) : 0.0;
   a.log_box = log_box;
   a.fmu = p.fmu; a.fs2 = p.fs2; a.ld = mb;
-  a.lnw = p.extra;
-  a.fs2_out = p.extra + (size_t)S * mb;
+  a.lnw = p.sc.ptr(p_lnw);
+  a.fs2_out = p.sc.ptr(p_fs2o);
   a.invalid = (int*)(ctx->d_out + o_flag);
+  const double* const src[2] = {a.lnw, a.fs2_out};
+  double* const dst[2] = {lnw_NaxS, fs2_NaxS};
   for (int64_t o = 0; o < Na; o += mb) {
     const int64_t m = (Na - o) < mb ? (Na - o) : mb;
     HIP_TRY(ctx, hipMemcpyAsync(p.xs, Xa_NaxD + o * D, sizeof(double) * m * D, hipMemcpyHostToDevice, ctx->stream));
@@ -181,12 +185,7 @@ extern "C" int vbmc_is_proposal(vbmc_ctx* ctx, int64_t Na, const double* Xa_NaxD
     VBMC_DISPATCH_DP(D, CALL);
 #undef CALL
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, a.lnw, sizeof(double) * m * S, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned + (size_t)S * mb, a.fs2_out, sizeof(double) * m * S, hipMemcpyDeviceToHost,
-                                ctx->stream));
-    HIP_TRY(ctx, stream_wait(ctx));
-    memcpy(lnw_NaxS + o * S, ctx->h_pinned, sizeof(double) * m * S);
-    memcpy(fs2_NaxS + o * S, ctx->h_pinned + (size_t)S * mb, sizeof(double) * m * S);
+    if ((rc = fetch_vectors(ctx, 2, src, dst, (size_t)m * S, (size_t)S * mb, (size_t)o * S))) return rc;
   }
   int flag = 0;
   HIP_TRY(ctx, hipMemcpyAsync(&flag, a.invalid, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -205,10 +204,11 @@ extern "C" int vbmc_is_box_sample(vbmc_ctx* ctx, int64_t n_box, uint64_t seed, c
   if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "is_box_sample: D=%d > 32 not supported", D);
   if (n_box == 0) return VBMC_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, (size_t)n_box * D + D);
+  Scratch sc;
+  const auto p_x = sc.add((size_t)n_box * D), p_rect = sc.add((size_t)D);
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
-  double* d_x = ctx->d_scratch;
-  double* d_rect = d_x + (size_t)n_box * D;
+  double *d_x = sc.ptr(p_x), *d_rect = sc.ptr(p_rect);
   HIP_TRY(ctx, hipMemcpyAsync(d_rect, rect_delta_D, sizeof(double) * D, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(is_box_sample_kernel, dim3((unsigned)((n_box + 255) / 256)), dim3(256), 0, ctx->stream,
                      (const double*)g.d_X, N, D, (const double*)d_rect, n_box, seed, d_x);

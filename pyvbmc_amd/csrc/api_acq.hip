@@ -174,14 +174,18 @@ extern "C" int vbmc_acq_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, int
   const GpState& g = ctx->gp;
   const int N = g.N, D = g.D, S = g.S;
   if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "acq_eval: D=%d > 32 not supported", D);
-  // S kernel matrices of a batch under 1 GiB; extra: dens | sn2 | acq | f_bar | var_tot (the last three contiguous)
+  // S kernel matrices of a batch under 1 GiB; its own pieces: dens | sn2 | acq, f_bar, var_tot (one piece, mb apart)
   PredictPlan p;
-  int rc = predict_plan(ctx, M, (int64_t)1 << 27, (int64_t)S * N, 65536, 5, 3, p);
-  if (rc) return rc;
+  predict_plan(ctx, M, (int64_t)1 << 27, (int64_t)S * N, 65536, p);
   const int64_t mb = p.mb;
   const int ntiles = p.ntiles;
+  const auto p_dens = p.sc.add((size_t)mb), p_sn2 = p.sc.add((size_t)mb), p_acq = p.sc.add(3 * (size_t)mb);
+  int rc = predict_reserve(ctx, p, 3);
+  if (rc) return rc;
   double *d_xs = p.xs, *d_Ks = p.Ks, *d_part = p.part, *d_fmu = p.fmu, *d_fs2 = p.fs2;
-  double *d_dens = p.extra, *d_sn2 = d_dens + mb, *d_acq = d_sn2 + mb;
+  double *d_dens = p.sc.ptr(p_dens), *d_sn2 = p.sc.ptr(p_sn2), *d_acq = p.sc.ptr(p_acq);
+  const double* const res_src[3] = {d_acq, d_acq + mb, d_acq + 2 * mb};
+  double* const res_dst[3] = {acq_M, f_bar_M, var_tot_M};
   // ---- small batches (a CMA-ES population, a single point): the CPU writes the points straight into host-writable
   // device memory, the last kernel writes the results into pinned host memory and publishes a completion word that the
   // CPU polls: no copy calls and no stream synchronisation around ~30 us of kernels ----
@@ -268,17 +272,7 @@ extern "C" int vbmc_acq_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, int
                        (const double*)d_sn2, S, m, mb, kind, y_max, tol_gp_var, d_acq, d_acq + mb,
                        d_acq + 2 * mb);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, d_acq, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
-    if (f_bar_M)
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned + mb, d_acq + mb, sizeof(double) * m, hipMemcpyDeviceToHost,
-                                  ctx->stream));
-    if (var_tot_M)
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned + 2 * mb, d_acq + 2 * mb, sizeof(double) * m,
-                                  hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, stream_wait(ctx));
-    memcpy(acq_M + o, ctx->h_pinned, sizeof(double) * m);
-    if (f_bar_M) memcpy(f_bar_M + o, ctx->h_pinned + mb, sizeof(double) * m);
-    if (var_tot_M) memcpy(var_tot_M + o, ctx->h_pinned + 2 * mb, sizeof(double) * m);
+    if ((rc = fetch_vectors(ctx, 3, res_src, res_dst, (size_t)m, (size_t)mb, (size_t)o))) return rc;
   }
   return VBMC_OK;
 }
@@ -310,17 +304,16 @@ extern "C" int vbmc_sq_dist(vbmc_ctx* ctx, int64_t n, int64_t m, int D, const do
   int64_t nb = c_nxm ? ((int64_t)1 << 25) / (m > 0 ? m : 1) : ((int64_t)1 << 20);
   nb = nb < 64 ? 64 : nb;
   nb = nb > n ? n : nb;
-  const size_t n_c = c_nxm ? (size_t)nb * m : 0;
-  const size_t n_p = argmin_n ? 2 * (size_t)ntiles * nb + (size_t)nb : 0;  // tile minima/indices + int64 out
-  const size_t need = (size_t)D + (size_t)nb * D + (size_t)m * D + n_c + n_p;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, need);
+  Scratch sc;
+  const auto p_cen = sc.add((size_t)D), p_a = sc.add((size_t)nb * D), p_b = sc.add((size_t)m * D);
+  const auto p_c = sc.add(c_nxm ? (size_t)nb * m : 0);
+  const auto p_p = sc.add(argmin_n ? 2 * (size_t)ntiles * nb : 0);  // tile minima / indices
+  const auto p_am = sc.add<int64_t>(argmin_n ? (size_t)nb : 0);
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
-  double* d_cen = ctx->d_scratch;
-  double* d_a = d_cen + D;
-  double* d_b = d_a + (size_t)nb * D;
-  double* d_c = c_nxm ? d_b + (size_t)m * D : nullptr;
-  double* d_p = d_b + (size_t)m * D + n_c;
-  int64_t* d_am = argmin_n ? (int64_t*)(d_p + 2 * (size_t)ntiles * nb) : nullptr;
+  double *d_cen = sc.ptr(p_cen), *d_a = sc.ptr(p_a), *d_b = sc.ptr(p_b), *d_p = sc.ptr(p_p);
+  double* d_c = c_nxm ? sc.ptr(p_c) : nullptr;
+  int64_t* d_am = argmin_n ? sc.ptr(p_am) : nullptr;
   HIP_TRY(ctx, hipMemcpyAsync(d_cen, cen.data(), sizeof(double) * D, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_b, b_mxD, sizeof(double) * m * D, hipMemcpyHostToDevice, ctx->stream));
   for (int64_t o = 0; o < n; o += nb) {

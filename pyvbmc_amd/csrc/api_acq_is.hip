@@ -181,20 +181,6 @@ int is_upload_small(vbmc_ctx* ctx, IsState* st, const double* Xa, const double* 
   return 0;
 }
 
-// n doubles of device memory to the host through the pinned buffer, in chunks
-int download_chunked(vbmc_ctx* ctx, const double* d_src, double* dst, size_t n) {
-  const size_t chunk = (size_t)1 << 20;  // 8 MiB
-  int rc = ensure_pinned(ctx, n < chunk ? n : chunk);
-  if (rc) return rc;
-  for (size_t o = 0; o < n; o += chunk) {
-    const size_t m = (n - o) < chunk ? (n - o) : chunk;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, d_src + o, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, stream_wait(ctx));
-    memcpy(dst + o, ctx->h_pinned, sizeof(double) * m);
-  }
-  return 0;
-}
-
 }  // namespace
 
 void acq_is_free(vbmc_ctx* ctx) {
@@ -239,9 +225,11 @@ extern "C" int vbmc_acq_is_build(vbmc_ctx* ctx, int64_t Na, const double* Xa, in
   int rc = is_reserve(ctx, st, Na, per_sample_xa, lnw_SxNa != nullptr);
   if (rc) return rc;
   const size_t nk = (size_t)Na * N;
-  if ((rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, 3 * nk))) return rc;
+  Scratch sc;
+  const auto p_K = sc.add(nk), p_T = sc.add(nk), p_TT = sc.add(nk);
+  if ((rc = reserve(ctx, sc))) return rc;
   if ((rc = is_upload_small(ctx, st, Xa, fs2a_NaxS, lnw_SxNa))) return rc;
-  double *d_K = ctx->d_scratch, *d_T = d_K + nk, *d_TT = d_T + nk;
+  double *d_K = sc.ptr(p_K), *d_T = sc.ptr(p_T), *d_TT = sc.ptr(p_TT);
   const dim3 tgrid((unsigned)((N + 31) / 32), (unsigned)((Na + 31) / 32));
   for (int s = 0; s < S; ++s) {
     const double* hyp = g.d_hyp + (size_t)s * g.P;
@@ -283,14 +271,18 @@ extern "C" int vbmc_acq_is_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, 
   const int N = g.N, D = g.D, S = g.S;
   const int64_t Na = st->Na;
   if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "acq_is_eval: D=%d > 32 not supported", D);
-  // extra: sn2 | Kx (mb x N) | T (mb x Na) | acq_s [S] | acq | var_tot
+  // its own pieces: sn2 | Kx (mb x N) | T (mb x Na) | acq_s [S] | acq, var_tot (one piece, mb apart)
   PredictPlan p;
-  int rc = predict_plan(ctx, M, (int64_t)1 << 26, (int64_t)S * N + N + Na, 16384, 1 + (size_t)N + Na + S + 2, 2, p);
-  if (rc) return rc;
+  predict_plan(ctx, M, (int64_t)1 << 26, (int64_t)S * N + N + Na, 16384, p);
   const int64_t mb = p.mb;
+  const auto p_sn2 = p.sc.add((size_t)mb), p_Kx = p.sc.add((size_t)mb * N), p_T = p.sc.add((size_t)mb * Na);
+  const auto p_as = p.sc.add((size_t)S * mb), p_acq = p.sc.add(2 * (size_t)mb);
+  int rc = predict_reserve(ctx, p, 2);
+  if (rc) return rc;
   double *d_xs = p.xs, *d_Ks = p.Ks, *d_part = p.part, *d_fmu = p.fmu, *d_fs2 = p.fs2;
-  double *d_sn2 = p.extra, *d_Kx = d_sn2 + mb, *d_T = d_Kx + (size_t)mb * N, *d_as = d_T + (size_t)mb * Na;
-  double* d_acq = d_as + (size_t)S * mb;
+  double *d_sn2 = p.sc.ptr(p_sn2), *d_Kx = p.sc.ptr(p_Kx), *d_T = p.sc.ptr(p_T), *d_as = p.sc.ptr(p_as), *d_acq = p.sc.ptr(p_acq);
+  const double* const res_src[2] = {d_acq, d_acq + mb};
+  double* const res_dst[2] = {acq_M, var_tot_M};
   for (int64_t o = 0; o < M; o += mb) {
     const int64_t m = (M - o) < mb ? (M - o) : mb;
     HIP_TRY(ctx, hipMemcpyAsync(d_xs, xs_MxD + o * D, sizeof(double) * m * D, hipMemcpyHostToDevice, ctx->stream));
@@ -315,13 +307,7 @@ extern "C" int vbmc_acq_is_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, 
                        (const double*)d_as, S, m, mb, d_acq, (const double*)d_fmu, (const double*)d_fs2,
                        d_acq + mb);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, d_acq, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
-    if (var_tot_M)
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned + mb, d_acq + mb, sizeof(double) * m, hipMemcpyDeviceToHost,
-                                  ctx->stream));
-    HIP_TRY(ctx, stream_wait(ctx));
-    memcpy(acq_M + o, ctx->h_pinned, sizeof(double) * m);
-    if (var_tot_M) memcpy(var_tot_M + o, ctx->h_pinned + mb, sizeof(double) * m);
+    if ((rc = fetch_vectors(ctx, 2, res_src, res_dst, (size_t)m, (size_t)mb, (size_t)o))) return rc;
   }
   return VBMC_OK;
 }
@@ -344,8 +330,12 @@ extern "C" int vbmc_is_mcmc(vbmc_ctx* ctx, int ln_y_fmu, double u_q, const doubl
     return vbmc_fail(ctx, VBMC_E_UNSUP, "is_mcmc: N=%d training points do not fit a chain's LDS", N);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t n_in = (size_t)S * D + 3 * (size_t)D, n_x = (size_t)S * n * D, n_sn = (size_t)S * n;
-  const size_t n_out = n_x + 3 * n_sn + 4 * (size_t)S + ((size_t)S + 1) / 2;  // (stats: 8-byte words; invalid: ints)
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, n_in + n_out);
+  Scratch sc;
+  const auto p_in = sc.add(n_in), p_X = sc.add(n_x), p_logp = sc.add(n_sn), p_fmu = sc.add(n_sn), p_fs2 = sc.add(n_sn);
+  const auto p_stats = sc.add<long long>(4 * (size_t)S);
+  const auto p_inv = sc.add<int>((size_t)S);
+  const size_t n_out = sc.total - p_X.off;  // everything from X on comes back in one copy
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
   if ((rc = ensure_pinned(ctx, n_out))) return rc;
   std::vector<double> in(n_in);
@@ -353,30 +343,27 @@ extern "C" int vbmc_is_mcmc(vbmc_ctx* ctx, int ln_y_fmu, double u_q, const doubl
   memcpy(in.data() + (size_t)S * D, widths_D, sizeof(double) * D);
   memcpy(in.data() + (size_t)S * D + D, lb_D, sizeof(double) * D);
   memcpy(in.data() + (size_t)S * D + 2 * D, ub_D, sizeof(double) * D);
-  double* d_in = ctx->d_scratch;
-  double *d_X = d_in + n_in, *d_logp = d_X + n_x, *d_fmu = d_logp + n_sn, *d_fs2 = d_fmu + n_sn;
-  long long* d_stats = (long long*)(d_fs2 + n_sn);
-  int* d_inv = (int*)(d_stats + 4 * (size_t)S);
+  double *d_in = sc.ptr(p_in), *d_X = sc.ptr(p_X), *d_logp = sc.ptr(p_logp), *d_fmu = sc.ptr(p_fmu), *d_fs2 = sc.ptr(p_fs2);
+  long long* d_stats = sc.ptr(p_stats);
+  int* d_inv = sc.ptr(p_inv);
   HIP_TRY(ctx, hipMemcpyAsync(d_in, in.data(), sizeof(double) * n_in, hipMemcpyHostToDevice, ctx->stream));
   // (a chain whose start is invalid writes nothing: its rows come back as zeros)
   HIP_TRY(ctx, hipMemsetAsync(d_X, 0, sizeof(double) * n_out, ctx->stream));
-  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[14], ctx->stream));
+  if ((rc = timing_begin(ctx, T_IS_MCMC))) return rc;
   rc = launch_is_mcmc(ctx, ln_y_fmu ? 1 : 0, u_q, d_in, d_in + (size_t)S * D, d_in + (size_t)S * D + D,
                       d_in + (size_t)S * D + 2 * D, n, thin, burn_in, seed, d_X, d_logp, d_fmu, d_fs2, d_stats, d_inv);
   if (rc) return rc;
-  if (ctx->timing) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[15], ctx->stream));
-    ctx->ev_valid[7] = true;
-  }
+  if ((rc = timing_end(ctx, T_IS_MCMC))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, d_X, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));  // (`in` is a local)
-  const double* h = ctx->h_pinned;
+  const double* h = ctx->h_pinned;  // (the pinned copy keeps the pieces' spacing)
+  const size_t o0 = p_X.off;
   memcpy(X_SxnxD, h, sizeof(double) * n_x);
-  memcpy(logp_Sxn, h + n_x, sizeof(double) * n_sn);
-  memcpy(fmu_nxS, h + n_x + n_sn, sizeof(double) * n_sn);
-  memcpy(fs2_nxS, h + n_x + 2 * n_sn, sizeof(double) * n_sn);
-  memcpy(stats_Sx4, h + n_x + 3 * n_sn, sizeof(int64_t) * 4 * S);
-  const int* h_inv = (const int*)(h + n_x + 3 * n_sn + 4 * (size_t)S);
+  memcpy(logp_Sxn, h + (p_logp.off - o0), sizeof(double) * n_sn);
+  memcpy(fmu_nxS, h + (p_fmu.off - o0), sizeof(double) * n_sn);
+  memcpy(fs2_nxS, h + (p_fs2.off - o0), sizeof(double) * n_sn);
+  memcpy(stats_Sx4, h + (p_stats.off - o0), sizeof(int64_t) * 4 * S);
+  const int* h_inv = (const int*)(h + (p_inv.off - o0));
   *invalid = 0;
   for (int s = 0; s < S; ++s) *invalid |= h_inv[s] != 0;
   return VBMC_OK;

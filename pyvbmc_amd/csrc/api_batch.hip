@@ -273,20 +273,18 @@ extern "C" int vbmc_neg_elcbo_batch(vbmc_ctx* ctx, const double* thetas_BxN, int
 
   // ---- device memory: thetas | attributes | packs | sums | H | F G H | base attributes | bounds | flags ----
   const size_t n_res = (size_t)B * S * K * (1 + 2 * D);
-  const size_t total = (size_t)B * n_theta + (size_t)B * n_aux + stride * B + n_res + 4 * (size_t)B + n_aux + 2 * (size_t)n_bnd + 4;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, total);
+  Scratch sc;
+  const auto p_th = sc.add((size_t)B * n_theta), p_aux = sc.add((size_t)B * n_aux), p_packs = sc.add(stride * B);
+  const auto p_res = sc.add(n_res), p_H = sc.add((size_t)B), p_out = sc.add(3 * (size_t)B);  // (out: F | G | H)
+  const auto p_base = sc.add((size_t)n_aux), p_bnd = sc.add(2 * (size_t)n_bnd);
+  const auto p_flags = sc.add<int>(8);  // [0] non-finite status of the pack, [1] first bad candidate (room for 8)
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
   rc = ensure_pinned(ctx, 3 * (size_t)B + n_aux + 2 * (size_t)n_bnd + 2);
   if (rc) return rc;
-  double* d_th = ctx->d_scratch;
-  double* d_aux = d_th + (size_t)B * n_theta;
-  double* d_packs = d_aux + (size_t)B * n_aux;
-  double* d_res = d_packs + stride * B;
-  double* d_H = d_res + n_res;
-  double* d_out = d_H + B;  // F | G | H
-  double* d_base = d_out + 3 * (size_t)B;
-  double* d_bnd = d_base + n_aux;
-  int* d_flags = (int*)(d_bnd + 2 * (size_t)n_bnd);  // [0] non-finite status of the pack, [1] first bad candidate
+  double *d_th = sc.ptr(p_th), *d_aux = sc.ptr(p_aux), *d_packs = sc.ptr(p_packs), *d_res = sc.ptr(p_res), *d_H = sc.ptr(p_H);
+  double *d_out = sc.ptr(p_out), *d_base = sc.ptr(p_base), *d_bnd = sc.ptr(p_bnd);
+  int* d_flags = sc.ptr(p_flags);
   hipStream_t sm = ctx->stream;
   // the small host-side inputs through the pinned buffer: the ctx mixture's attributes, the bounds
   double* hp = ctx->h_pinned + 3 * (size_t)B;

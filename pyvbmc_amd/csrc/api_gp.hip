@@ -214,14 +214,16 @@ extern "C" int vbmc_gp_log_joint(vbmc_ctx* ctx, int grad_flags, int avg_flag, in
   const size_t n_res = (size_t)S * K * st;
   const size_t n_Z = compute_var ? (size_t)S * K * N : 0;
   const size_t n_Q = compute_var ? (size_t)S * K * K : 0;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, n_res + 2 * n_Z + n_Q);
+  Scratch sc;
+  const auto p_res = sc.add(n_res), p_Z = sc.add(n_Z), p_V = sc.add(n_Z), p_Q = sc.add(n_Q);
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
   rc = ensure_pinned(ctx, n_res + n_Q);
   if (rc) return rc;
-  double* d_res = ctx->d_scratch;
-  double* d_Z = compute_var ? d_res + n_res : nullptr;
-  double* d_V = compute_var ? d_Z + n_Z : nullptr;
-  double* d_Q = compute_var ? d_V + n_Z : nullptr;
+  double* d_res = sc.ptr(p_res);
+  double* d_Z = compute_var ? sc.ptr(p_Z) : nullptr;
+  double* d_V = compute_var ? sc.ptr(p_V) : nullptr;
+  double* d_Q = compute_var ? sc.ptr(p_Q) : nullptr;
   rc = launch_gp_log_joint(ctx, grad_flags != 0, d_res, d_Z);
   if (rc) return rc;
   if (compute_var) {
@@ -314,22 +316,20 @@ extern "C" int vbmc_gp_predict(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, i
   if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "gp_predict: D=%d > 32 not supported", D);
   // batch so that the S kernel matrices of a batch stay under 1 GiB
   PredictPlan p;
-  int rc = predict_plan(ctx, M, (int64_t)1 << 27, (int64_t)S * N, 65536, 0, 2 * (size_t)S, p);
+  predict_plan(ctx, M, (int64_t)1 << 27, (int64_t)S * N, 65536, p);
+  int rc = predict_reserve(ctx, p, 2 * (size_t)S);
   if (rc) return rc;
   const int64_t mb = p.mb;
+  const double* const moments[1] = {p.fmu};  // fmu | fs2, contiguous
   for (int64_t o = 0; o < M; o += mb) {
     const int64_t m = (M - o) < mb ? (M - o) : mb;
     HIP_TRY(ctx, hipMemcpyAsync(p.xs, xs_MxD + o * D, sizeof(double) * m * D, hipMemcpyHostToDevice, ctx->stream));
     // every hyper-parameter sample in the same three launches (grid.z = sample)
-    if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    if ((rc = timing_begin(ctx, T_PREDICT))) return rc;
     rc = launch_gp_predict_all(ctx, m, p.xs, p.Ks, p.part, add_noise, p.fmu, p.fs2, mb);
     if (rc) return rc;
-    if (ctx->timing) {
-      HIP_TRY(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
-      ctx->ev_valid[3] = true;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, p.fmu, sizeof(double) * 2 * S * mb, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, stream_wait(ctx));
+    if ((rc = timing_end(ctx, T_PREDICT))) return rc;
+    if ((rc = fetch_vectors(ctx, 1, moments, nullptr, 2 * (size_t)S * mb, 0, 0))) return rc;  // (transposed below)
     const double *hm = ctx->h_pinned, *hv = ctx->h_pinned + (size_t)S * mb;  // [S][mb] each
     for (int64_t i = 0; i < m; ++i) {
       if (separate_samples) {

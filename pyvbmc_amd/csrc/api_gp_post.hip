@@ -121,11 +121,13 @@ extern "C" int vbmc_gp_posterior(vbmc_ctx* ctx, int N, int D, int S, int P, int 
   int rc = gp_state_grow(ctx, w, N, D, S, P, true);
   if (rc) return rc;
   const int nb = (N + 63) / 64;
-  const size_t n_flag = (size_t)(S + 1) / 2 + 1;
-  rc = ensure_dev(ctx, &ctx->d_post_ws, &ctx->d_post_ws_cap, n_flag + (size_t)S * nb * 64 * 64);
+  Scratch sc;
+  const auto p_flag = gp_post_flags(sc, S);
+  const auto p_Dinv = sc.add((size_t)S * nb * 64 * 64);
+  rc = reserve_in(ctx, &ctx->d_post_ws, &ctx->d_post_ws_cap, sc);
   if (rc) return rc;
-  int* d_flag = (int*)ctx->d_post_ws;
-  double* d_Dinv = ctx->d_post_ws + n_flag;
+  int* d_flag = sc.ptr(p_flag);
+  double* d_Dinv = sc.ptr(p_Dinv);
   w.h_X.assign(X_NxD, X_NxD + (size_t)N * D);
   w.h_y.assign(y_N, y_N + N);
   w.hyp.assign(hyp_SxP, hyp_SxP + (size_t)S * P);
@@ -161,10 +163,10 @@ extern "C" int vbmc_gp_append(vbmc_ctx* ctx, const double* x_D, double y, double
   const int N = o.N, D = o.D, S = o.S, P = o.P, N1 = N + 1;
   int rc = gp_state_grow(ctx, w, N1, D, S, P, true);
   if (rc) return rc;
-  const size_t n_flag = (size_t)(S + 1) / 2 + 1;
-  rc = ensure_dev(ctx, &ctx->d_post_ws, &ctx->d_post_ws_cap, n_flag + 3 * (size_t)S * N + 4 * (size_t)S + (size_t)S * N1);
+  GpAppendWs ws = gp_post_append_ws(S, N);
+  rc = reserve_in(ctx, &ctx->d_post_ws, &ctx->d_post_ws_cap, ws.sc);
   if (rc) return rc;
-  int* d_flag = (int*)ctx->d_post_ws;
+  int* d_flag = ws.sc.ptr(ws.flag);
   w.h_X = o.h_X;
   w.h_X.insert(w.h_X.end(), x_D, x_D + D);
   w.h_y = o.h_y;
@@ -182,7 +184,7 @@ extern "C" int vbmc_gp_append(vbmc_ctx* ctx, const double* x_D, double y, double
     return rc;
   }
   std::swap(ctx->gp, ctx->gp_next);
-  rc = launch_gp_post_append(ctx, ctx->gp_next, y, ctx->d_post_ws + n_flag, d_flag);
+  rc = launch_gp_post_append(ctx, ctx->gp_next, y, ws);
   rc = finish_build(ctx, d_flag, S, rc, "gp_append");
   if (rc) return rc;
   return fetch(ctx, alpha_out, L_out);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vbmc_hip.h"
+#include "scratch.h"
 
 struct ncclComm;
 
@@ -142,11 +143,15 @@ struct ElboScratch {
   std::vector<double> dG, dH, dF, dFb, mu, sg, lm, wg, ext, dL, wpen, jw;
 };
 
+// The timed intervals of vbmc_last_kernel_ms (the numbers are ABI): entmc, glj, pdf, predict, elbo, predict's variance
+// product (timing level 2 only), the GP posterior's factorisation, the MCMC chains of vbmc_is_mcmc
+enum TimingPair { T_ENTMC = 0, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_COUNT };
+
 struct vbmc_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[16] = {};  // pairs: (0,1) entmc, (2,3) glj, (4,5) pdf, (6,7) predict, (8,9) elbo, (10,11) predict's variance product, (12,13) the GP posterior's factorisation, (14,15) the MCMC chains of vbmc_is_mcmc
-  bool ev_valid[8] = {false, false, false, false, false, false, false, false};
+  hipEvent_t ev[2 * T_COUNT] = {};  // pair p of TimingPair below is (ev[2 p], ev[2 p + 1])
+  bool ev_valid[T_COUNT] = {};
   std::string err;
   hipDeviceProp_t prop;
 
@@ -369,6 +374,16 @@ int set_mixture_host(vbmc_ctx* ctx, int D, int K, const double* mu_KxD, const do
 // buffer helpers (ctx.hip) --------------------------------------------------
 int ensure_dev(vbmc_ctx* ctx, double** p, size_t* cap, size_t n_doubles);
 int ensure_pinned(vbmc_ctx* ctx, size_t n_doubles);
+// the buffer behind a listed layout (scratch.h): grown to sc.total, sc.base set.  reserve: the context's scratch, the one
+// place the entry points outside the step's path ensure it; reserve_in: another grown buffer (gp_post.hip's workspace)
+int reserve_in(vbmc_ctx* ctx, double** p, size_t* cap, Scratch& sc);
+int reserve(vbmc_ctx* ctx, Scratch& sc);
+// n doubles of device memory to the host through the pinned buffer, in chunks
+int download_chunked(vbmc_ctx* ctx, const double* d_src, double* dst, size_t n);
+// A batch's result vectors: d_src[i] (count doubles each, i < k) to h_pinned + i * stride, one wait, then on to
+// dst[i] + o; a null dst[i] is skipped.  dst == nullptr: they stay in h_pinned for the caller to read (pinned memory for
+// k * stride doubles is the caller's: predict_reserve).
+int fetch_vectors(vbmc_ctx* ctx, int k, const double* const* d_src, double* const* dst, size_t count, size_t stride, size_t o);
 // csrc/host_randn.hip: vbmc_mt19937_randn with progress(user, m) = "out[0 .. m) is final", called from
 // the calling thread while the worker threads still write the rest
 int randn_with_progress(uint32_t* key, int* pos, int* has_gauss, double* gauss, double* out, int64_t n, int n_threads,
@@ -524,6 +539,18 @@ inline hipError_t stream_wait(vbmc_ctx* ctx) {
   if (e == hipSuccess) ctx->pack_in_flight = false;
   return e;
 }
+// the event pair around a timed interval on ctx->stream, recorded while vbmc_set_timing is on
+inline int timing_begin(vbmc_ctx* ctx, TimingPair p) {
+  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[2 * p], ctx->stream));
+  return 0;
+}
+inline int timing_end(vbmc_ctx* ctx, TimingPair p) {
+  if (ctx->timing) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev[2 * p + 1], ctx->stream));
+    ctx->ev_valid[p] = true;
+  }
+  return 0;
+}
 int launch_prep(vbmc_ctx* ctx, const PrepArgs& a);                           // on ctx->stream
 int launch_prep_on(vbmc_ctx* ctx, hipStream_t stream, const PrepArgs& a);
 
@@ -575,9 +602,15 @@ struct Selector {
   std::vector<double> cdf;   // K
 };
 void make_selector(const double* w, int K, int64_t N, int balance, Selector& s);
-// N draws of the mixture `d_pack` (selection vectors through d_sel, (K+1) int64 + K doubles)
+// The selection vectors in device scratch, a piece of selector_elems(K) doubles: (K+1) int64 counts | K doubles of cdf
+// (mode.hip draws from the cdf alone and carves selector_cdf_elems(K))
+inline size_t selector_cdf_elems(int K) { return (size_t)K; }
+inline size_t selector_elems(int K) { return (size_t)K + 1 + selector_cdf_elems(K); }
+inline int64_t* selector_cum(double* d_sel) { return (int64_t*)d_sel; }
+inline double* selector_cdf(double* d_sel, int K) { return d_sel + K + 1; }
+// N draws of the mixture `d_pack` (selection vectors through d_sel, a piece of selector_elems(K) doubles)
 int launch_sample(vbmc_ctx* ctx, const double* d_pack, const MixLayout& ml, const double* w_host, int64_t N,
-                  uint64_t seed, int balance, void* d_sel, double* d_x, int32_t* d_comp, double df = INFINITY);
+                  uint64_t seed, int balance, double* d_sel, double* d_x, int32_t* d_comp, double df = INFINITY);
 // per-block partial sums of log q_other - log q_own with kl_div's zero-replacement rules (nblk blocks)
 int launch_kl_terms(vbmc_ctx* ctx, const double* d_y_own, const double* d_y_other, int64_t n, int nblk, double* d_part);
 // gp
@@ -590,9 +623,23 @@ int launch_pad_linv(vbmc_ctx* ctx);
 // gp_post.hip: the posterior of ctx->gp's X, y, hyp, noise built in ctx->gp's buffers (covariance, blocked upper
 // Cholesky, L^-1, alpha); d_flag[s] != 0 afterwards: sample s met a pivot that is not a positive finite number
 int launch_gp_post_build(vbmc_ctx* ctx, double* d_Dinv, int* d_flag);
+// the per-sample flags at the head of a build's or an append's workspace (ctx->d_post_ws): S ints and a spare double
+inline Piece<int> gp_post_flags(Scratch& sc, int S) {
+  const Piece<int> p = sc.add<int>((size_t)S);
+  sc.add(1);
+  return p;
+}
+// the workspace of an append to S samples of N points, listed once: flags | kvec, lvec, uvec [S][N] | dd 3 S | rnew S |
+// tvec [S][N + 1]
+struct GpAppendWs {
+  Scratch sc;
+  Piece<int> flag;
+  Piece<> kvec, lvec, uvec, dd, rnew, tvec;
+};
+GpAppendWs gp_post_append_ws(int S, int N);
 // one point appended: `from` (N points, live) -> ctx->gp (N + 1 points, X / XT / hyp / sl / sn2 already in place);
-// ws: 3 S N + 4 S + S (N + 1) doubles
-int launch_gp_post_append(vbmc_ctx* ctx, const GpState& from, double y_new, double* ws, int* d_flag);
+// ws: gp_post_append_ws(from.S, from.N), reserved
+int launch_gp_post_append(vbmc_ctx* ctx, const GpState& from, double y_new, const GpAppendWs& ws);
 void gp_post_free(vbmc_ctx* ctx);
 // api_gp.hip: the device buffers of a GP state of N points, D dimensions, S samples, P hyper-parameters, kept across GP
 // updates and only grown (capacity n + n / 8 + 64: active sampling makes N creep up by one); with_post: also what a
@@ -600,42 +647,45 @@ void gp_post_free(vbmc_ctx* ctx);
 int gp_state_grow(vbmc_ctx* ctx, GpState& g, int N, int D, int S, int P, bool with_post);
 // leading dimension of the padded operands of predict's variance product, and the size of the
 // K* scratch of a batch of mb points (rows rounded up to whole 64-row tiles)
-inline size_t align32(size_t n) { return (n + 31) & ~(size_t)31; }
 inline int predict_ld(int N) { return (N + 63) / 64 * 64; }
 inline size_t predict_ks_elems(int S, int64_t mb, int N) {
   return (size_t)S * (size_t)((mb + 63) / 64 * 64) * (size_t)predict_ld(N);
 }
 // The batch plan of an entry point that runs predict on M points: mb points per batch -- budget / cost doubles,
-// in whole 64-row tiles, at most cap and at most M -- and the scratch of one batch carved up as
+// in whole 64-row tiles, at most cap and at most M -- and the scratch of one batch listed as
 //   xs (mb x D) | Ks [S] (256-byte aligned: read by 16-byte LDS-direct loads) | part, fpart [S][ntiles][mb] |
-//   fmu [S][mb] | fs2 [S][mb] | extra (extra_per_point x mb, the caller's own),
-// with the device scratch and pinned_per_point x mb doubles of pinned memory ensured.
+//   fmu [S][mb] | fs2 [S][mb].
+// The caller adds its own pieces to p.sc behind these, then predict_reserve ensures the device scratch and
+// pinned_per_point x mb doubles of pinned memory and forms the pointers.
 struct PredictPlan {
   int64_t mb = 0;
   int ntiles = 0;
-  size_t total = 0;
-  double *xs = nullptr, *Ks = nullptr, *part = nullptr, *fmu = nullptr, *fs2 = nullptr, *extra = nullptr;
+  Scratch sc;
+  Piece<> p_xs, p_Ks, p_part, p_fmu, p_fs2;
+  double *xs = nullptr, *Ks = nullptr, *part = nullptr, *fmu = nullptr, *fs2 = nullptr;
 };
-inline int predict_plan(vbmc_ctx* ctx, int64_t M, int64_t budget, int64_t cost, int64_t cap, size_t extra_per_point,
-                        size_t pinned_per_point, PredictPlan& p) {
+inline void predict_plan(const vbmc_ctx* ctx, int64_t M, int64_t budget, int64_t cost, int64_t cap, PredictPlan& p) {
   const int S = ctx->gp.S, N = ctx->gp.N, D = ctx->gp.D;
   p.ntiles = (N + 63) / 64;
   int64_t mb = budget / cost;
   mb = mb > cap ? cap : (mb < 64 ? 64 : (mb / 64) * 64);
   p.mb = mb = M < mb ? M : mb;
-  const size_t n_xs = align32((size_t)mb * D), n_ks = predict_ks_elems(S, mb, N);
-  const size_t n_part = 2 * (size_t)S * p.ntiles * mb, n_mom = (size_t)S * mb;
-  p.total = n_xs + n_ks + n_part + 2 * n_mom + extra_per_point * (size_t)mb;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, p.total);
+  p.p_xs = p.sc.add((size_t)mb * D);
+  p.p_Ks = p.sc.add(predict_ks_elems(S, mb, N), 32);
+  p.p_part = p.sc.add(2 * (size_t)S * p.ntiles * mb);
+  p.p_fmu = p.sc.add((size_t)S * mb);
+  p.p_fs2 = p.sc.add((size_t)S * mb);
+}
+inline int predict_reserve(vbmc_ctx* ctx, PredictPlan& p, size_t pinned_per_point) {
+  int rc = reserve(ctx, p.sc);
   if (rc) return rc;
-  rc = ensure_pinned(ctx, pinned_per_point * (size_t)mb);
+  rc = ensure_pinned(ctx, pinned_per_point * (size_t)p.mb);
   if (rc) return rc;
-  p.xs = ctx->d_scratch;
-  p.Ks = p.xs + n_xs;
-  p.part = p.Ks + n_ks;
-  p.fmu = p.part + n_part;
-  p.fs2 = p.fmu + n_mom;
-  p.extra = p.fs2 + n_mom;
+  p.xs = p.sc.ptr(p.p_xs);
+  p.Ks = p.sc.ptr(p.p_Ks);
+  p.part = p.sc.ptr(p.p_part);
+  p.fmu = p.sc.ptr(p.p_fmu);
+  p.fs2 = p.sc.ptr(p.p_fs2);
   return 0;
 }
 int launch_gp_predict_products(vbmc_ctx* ctx, int64_t M, const double* d_xs, double* d_Ks, double* d_part,

@@ -57,6 +57,37 @@ int ensure_pinned(vbmc_ctx* ctx, size_t n) {
   return 0;
 }
 
+int reserve_in(vbmc_ctx* ctx, double** p, size_t* cap, Scratch& sc) {
+  const int rc = ensure_dev(ctx, p, cap, sc.total);
+  if (rc) return rc;
+  sc.base = *p;
+  return 0;
+}
+int reserve(vbmc_ctx* ctx, Scratch& sc) { return reserve_in(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, sc); }
+
+int download_chunked(vbmc_ctx* ctx, const double* d_src, double* dst, size_t n) {
+  const size_t chunk = (size_t)1 << 20;  // 8 MiB
+  int rc = ensure_pinned(ctx, n < chunk ? n : chunk);
+  if (rc) return rc;
+  for (size_t o = 0; o < n; o += chunk) {
+    const size_t m = (n - o) < chunk ? (n - o) : chunk;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, d_src + o, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, stream_wait(ctx));
+    memcpy(dst + o, ctx->h_pinned, sizeof(double) * m);
+  }
+  return 0;
+}
+
+int fetch_vectors(vbmc_ctx* ctx, int k, const double* const* d_src, double* const* dst, size_t count, size_t stride, size_t o) {
+  for (int i = 0; i < k; ++i)
+    if (!dst || dst[i])
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned + i * stride, d_src[i], sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, stream_wait(ctx));
+  for (int i = 0; dst && i < k; ++i)
+    if (dst[i]) memcpy(dst[i] + o, ctx->h_pinned + i * stride, sizeof(double) * count);
+  return 0;
+}
+
 // live contexts per device in this process (the armed evaluation is for a context that has its device to itself)
 #include <atomic>
 static std::atomic<int> g_live_ctx[64];
@@ -204,7 +235,7 @@ int vbmc_ctx_create(int device_id, vbmc_ctx** out) {
   if (e == hipSuccess) e = hipGetDeviceProperties(&ctx->prop, device_id);
   if (e == hipSuccess) bind_host_thread(ctx);  // (before the pinned allocations below: they follow the thread's node)
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-  for (int i = 0; i < 16 && e == hipSuccess; ++i) e = hipEventCreate(&ctx->ev[i]);
+  for (int i = 0; i < 2 * T_COUNT && e == hipSuccess; ++i) e = hipEventCreate(&ctx->ev[i]);
   if (e == hipSuccess) e = hipHostMalloc((void**)&ctx->h_done, 64, hipHostMallocDefault);
   if (e == hipSuccess) {
     for (int i = 0; i < 8; ++i) ctx->h_done[i] = 0;
@@ -358,10 +389,10 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on) {
 }
 
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out) {
-  if (!ctx || which < 0 || which > 7 || !ms_out) return VBMC_E_ARG;
+  if (!ctx || which < 0 || which >= T_COUNT || !ms_out) return VBMC_E_ARG;
   NEED_DEVICE(ctx);
   if (!ctx->ev_valid[which])
-    return vbmc_fail(ctx, VBMC_E_ARG, which == 5 ? "no timed launch recorded for 5 (gp_predict's product alone is timed at vbmc_set_timing(ctx, 2) only)"
+    return vbmc_fail(ctx, VBMC_E_ARG, which == T_PREDICT_VAR ? "no timed launch recorded for 5 (gp_predict's product alone is timed at vbmc_set_timing(ctx, 2) only)"
                                                  : "no timed launch recorded for %d", which);
   HIP_TRY(ctx, hipEventSynchronize(ctx->ev[2 * which + 1]));
   float ms = 0.f;

@@ -12,6 +12,7 @@
 
 #include "fastmath.h"
 #include "mixture_dev.h"
+#include "scratch.h"
 
 namespace {
 
@@ -138,6 +139,15 @@ int vbmc_probe_wave(int op, const double* v, double* out, int n_blocks) {
   PROBE_TRY(hipDeviceSynchronize());
   PROBE_TRY(hipMemcpy(out, b.d[1], bytes, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// host only: scratch.h's carver over n pieces (count, element bytes, alignment in doubles); offsets[i] and the total, in
+// doubles (tests/test_scratch_layout.py)
+void vbmc_probe_scratch_layout(int n, const size_t* count, const size_t* elem_bytes, const size_t* align, size_t* offsets,
+                               size_t* total) {
+  Scratch sc;
+  for (int i = 0; i < n; ++i) offsets[i] = sc.add_bytes(count[i], elem_bytes[i], align[i]);
+  *total = sc.total;
 }
 
 }  // extern "C"

@@ -673,13 +673,13 @@ int entmc_launch_main(vbmc_ctx* ctx, const EntPlan& p) {
   const EntArgs& a = p.a;
   // timing: the wave-split launch carries the event pair on its own dispatch packet; the generic
   // kernel is bracketed by two records (each a barrier packet, ~6 us between dependent kernels)
-  hipEvent_t e0 = ctx->timing ? ctx->ev[0] : nullptr, e1 = ctx->timing ? ctx->ev[1] : nullptr;
+  hipEvent_t e0 = ctx->timing ? ctx->ev[2 * T_ENTMC] : nullptr, e1 = ctx->timing ? ctx->ev[2 * T_ENTMC + 1] : nullptr;
   ctx->last_plan[0] = (int)p.kernel;
   ctx->last_plan[1] = a.rg;
   ctx->last_plan[2] = a.chunks;
   ctx->last_plan[3] = a.eps_mode == VBMC_EPS_RESIDENT ? 1 : 0;
   const bool bracket = ctx->timing && (p.kernel == EntKernel::Valu || p.kernel == EntKernel::Small);
-  if (bracket) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+  if (bracket) HIP_TRY(ctx, hipEventRecord(ctx->ev[2 * T_ENTMC], ctx->stream));
   switch (p.kernel) {
     case EntKernel::Small: launch_entmc_small(ctx->stream, a, p.DP, p.table); break;
     case EntKernel::Mfma: launch_entmc_mfma(ctx->stream, a, p.DP, p.table, e0, e1); break;
@@ -701,8 +701,8 @@ int entmc_launch_main(vbmc_ctx* ctx, const EntPlan& p) {
     default: return vbmc_fail(ctx, VBMC_E_ARG, "entmc: plan names no entropy kernel (%d)", (int)p.kernel);
   }
   if (ctx->timing) {
-    if (bracket) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    ctx->ev_valid[0] = true;
+    if (bracket) HIP_TRY(ctx, hipEventRecord(ctx->ev[2 * T_ENTMC + 1], ctx->stream));
+    ctx->ev_valid[T_ENTMC] = true;
   }
   HIP_TRY(ctx, hipGetLastError());
   return 0;

@@ -979,14 +979,11 @@ void glj_fill_prep(const vbmc_ctx* ctx, int want_grad, double* res, double* Z, P
 int launch_gp_log_joint(vbmc_ctx* ctx, int want_grad, double* d_res, double* d_Z) {
   PrepArgs a;
   glj_fill_prep(ctx, want_grad, d_res, d_Z, a);
-  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-  int rc = launch_prep(ctx, a);
+  int rc = timing_begin(ctx, T_GLJ);
   if (rc) return rc;
-  if (ctx->timing) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->ev_valid[1] = true;
-  }
-  return 0;
+  rc = launch_prep(ctx, a);
+  if (rc) return rc;
+  return timing_end(ctx, T_GLJ);
 }
 
 // Q[s][j][k] = z_j^T (L^T L)^-1 z_k (L_chol)  or  z_j^T L z_k (otherwise), from Z.
@@ -1085,7 +1082,8 @@ int launch_gp_predict_products(vbmc_ctx* ctx, int64_t M, const double* d_xs, dou
                      (const double*)g.d_alpha, (const double*)g.d_sW, (const double*)g.d_hyp,
                      (const double*)g.d_xc, (const double*)g.d_smeta, g.P, N, D, M, d_Ks, lda, ks_stride,
                      d_part + (size_t)ntiles * M, pstride, fin.tick);
-  if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[10], ctx->stream));
+  int rc = 0;
+  if (ctx->timing >= 2 && (rc = timing_begin(ctx, T_PREDICT_VAR))) return rc;
   if (dma) {
     static bool lds_set[64] = {};
     int dev = 0;
@@ -1114,10 +1112,9 @@ int launch_gp_predict_products(vbmc_ctx* ctx, int64_t M, const double* d_xs, dou
                        (const double*)g.d_smeta, pstride);
   }
   if (ctx->timing >= 2) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[11], ctx->stream));
-    ctx->ev_valid[5] = true;
+    if ((rc = timing_end(ctx, T_PREDICT_VAR))) return rc;
   } else {
-    ctx->ev_valid[5] = false;  // (no pair around this product: an interval left by an earlier level-2 call is not this call's)
+    ctx->ev_valid[T_PREDICT_VAR] = false;  // (no pair around this product: an interval left by an earlier level-2 call is not this call's)
   }
   HIP_TRY(ctx, hipGetLastError());
   return 0;

@@ -347,7 +347,8 @@ int launch_gp_post_build(vbmc_ctx* ctx, double* d_Dinv, int* d_flag) {
   hipLaunchKernelGGL(gp_cov_kernel, dim3(nb, nb, S), dim3(256), 0, ctx->stream, (const double*)g.d_XT, (const double*)g.d_X,
                      (const double*)g.d_y, (const double*)g.d_hyp, g.P, N, g.D, g.mean_kind, (const double*)g.d_sn2,
                      (const double*)g.d_sl, g.d_L, g.d_r);
-  if (ctx->timing) HIP_TRY(ctx, hipEventRecord(ctx->ev[12], ctx->stream));
+  int rc = timing_begin(ctx, T_GP_POST);
+  if (rc) return rc;
   for (int j = 0; j < nb; ++j) {
     hipLaunchKernelGGL(chol_diag_kernel, dim3(S), dim3(64), 0, ctx->stream, g.d_L, N, j, d_flag);
     hipLaunchKernelGGL(chol_dinv_kernel, dim3(S), dim3(64), 0, ctx->stream, (const double*)g.d_L, N, j, d_Dinv, nb);
@@ -357,21 +358,33 @@ int launch_gp_post_build(vbmc_ctx* ctx, double* d_Dinv, int* d_flag) {
       hipLaunchKernelGGL(chol_trail_kernel, dim3(rest, rest, S), dim3(256), 0, ctx->stream, g.d_L, N, j);
     }
   }
-  if (ctx->timing) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[13], ctx->stream));
-    ctx->ev_valid[6] = true;
-  }
+  if ((rc = timing_end(ctx, T_GP_POST))) return rc;
   HIP_TRY(ctx, hipGetLastError());
-  int rc = launch_trinv(ctx, d_Dinv);
+  rc = launch_trinv(ctx, d_Dinv);
   if (rc) return rc;
   return launch_alpha(ctx, d_Dinv);  // (the inverted blocks are not read after launch_trinv: S N <= S nb 64^2)
 }
 
-int launch_gp_post_append(vbmc_ctx* ctx, const GpState& o, double y_new, double* ws, int* d_flag) {
+GpAppendWs gp_post_append_ws(int S, int N) {
+  GpAppendWs w;
+  const size_t sn = (size_t)S * N;
+  w.flag = gp_post_flags(w.sc, S);
+  w.kvec = w.sc.add(sn);
+  w.lvec = w.sc.add(sn);
+  w.uvec = w.sc.add(sn);
+  w.dd = w.sc.add(3 * (size_t)S);
+  w.rnew = w.sc.add((size_t)S);
+  w.tvec = w.sc.add((size_t)S * (N + 1));
+  return w;
+}
+
+int launch_gp_post_append(vbmc_ctx* ctx, const GpState& o, double y_new, const GpAppendWs& ws) {
   GpState& g = ctx->gp;
   const int N = o.N, S = o.S, N1 = N + 1, nb = (N + PB - 1) / PB;
-  double *kvec = ws, *lvec = kvec + (size_t)S * N, *uvec = lvec + (size_t)S * N, *dd = uvec + (size_t)S * N, *rnew = dd + 3 * S;
-  double* tvec = rnew + S;  // S (N + 1)
+  const Scratch& sc = ws.sc;
+  double *kvec = sc.ptr(ws.kvec), *lvec = sc.ptr(ws.lvec), *uvec = sc.ptr(ws.uvec), *dd = sc.ptr(ws.dd), *rnew = sc.ptr(ws.rnew);
+  double* tvec = sc.ptr(ws.tvec);
+  int* d_flag = sc.ptr(ws.flag);
   const double* x = g.d_X + (size_t)N * g.D;
   hipLaunchKernelGGL(gp_append_k_kernel, dim3((N + 255) / 256, S), dim3(256), 0, ctx->stream, (const double*)o.d_XT, N, o.D, x,
                      y_new, (const double*)o.d_hyp, o.P, o.mean_kind, (const double*)o.d_sl, kvec, rnew);

@@ -739,28 +739,26 @@ size_t lds_bytes(int nm, bool spline) {
   return f > b ? f : b;
 }
 
-// device layout of one kde / mtv call, carved from ctx->d_scratch (doubles)
+// device layout of one kde / mtv call: the first pieces of the call's scratch list (offsets in doubles)
 struct KdePlan {
   int ncol = 0, nm = 0;
   int64_t pmax = 0;
   size_t o_keys = 0, o_ga = 0, o_dens = 0, o_xm = 0, o_msp = 0, o_colp = 0, o_stat = 0, o_nf = 0, o_bnd = 0,
-         o_part = 0, total = 0;
-  void plan(int ncol_, int nm_, int64_t nmax, bool want_xmesh, bool want_spline, int D) {
+         o_part = 0;
+  void plan(Scratch& sc, int ncol_, int nm_, int64_t nmax, bool want_xmesh, bool want_spline, int D) {
     ncol = ncol_;
     nm = nm_;
     pmax = next_pow2(nmax > kChunk ? nmax : kChunk);
-    size_t o = 0;
-    o_keys = o; o += (size_t)ncol * pmax;
-    o_ga = o; o += (size_t)ncol * nm;
-    o_dens = o; o += (size_t)ncol * nm;
-    o_xm = o; o += want_xmesh ? (size_t)ncol * nm : 0;
-    o_msp = o; o += want_spline ? (size_t)ncol * nm : 0;
-    o_colp = o; o += (size_t)ncol * CP_N;
-    o_stat = o; o += (size_t)ncol * 2;
-    o_nf = o; o += ((size_t)ncol + 1) / 2;
-    o_bnd = o; o += 2 * (size_t)ncol;
-    o_part = o; o += want_spline ? (size_t)D * 3 * kIntBlocks : 0;
-    total = o;
+    o_keys = sc.add((size_t)ncol * pmax).off;
+    o_ga = sc.add((size_t)ncol * nm).off;
+    o_dens = sc.add((size_t)ncol * nm).off;
+    o_xm = sc.add(want_xmesh ? (size_t)ncol * nm : 0).off;
+    o_msp = sc.add(want_spline ? (size_t)ncol * nm : 0).off;
+    o_colp = sc.add((size_t)ncol * CP_N).off;
+    o_stat = sc.add<int64_t>((size_t)ncol * 2).off;
+    o_nf = sc.add<unsigned>((size_t)ncol).off;
+    o_bnd = sc.add(2 * (size_t)ncol).off;
+    o_part = sc.add(want_spline ? (size_t)D * 3 * kIntBlocks : 0).off;
   }
 };
 
@@ -835,13 +833,14 @@ extern "C" int vbmc_kde_1d(vbmc_ctx* ctx, int ncol, int64_t n, const double* x_c
   if (n > ((int64_t)1 << 30)) return vbmc_fail(ctx, VBMC_E_UNSUP, "kde_1d: %lld samples > 2^30", (long long)n);
   NEED_DEVICE(ctx);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  Scratch sc;
   KdePlan pl;
-  pl.plan(ncol, n_mesh, n, true, false, 0);
+  pl.plan(sc, ncol, n_mesh, n, true, false, 0);
   const size_t nx = (size_t)ncol * n;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, pl.total + nx);
+  const auto p_x = sc.add(nx);
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
-  double* base = ctx->d_scratch;
-  double* d_x = base + pl.total;
+  double *base = sc.base, *d_x = sc.ptr(p_x);
   HIP_TRY(ctx, hipMemcpyAsync(d_x, x_colxn, sizeof(double) * nx, hipMemcpyHostToDevice, ctx->stream));
   if (lb_col) HIP_TRY(ctx, hipMemcpyAsync(base + pl.o_bnd, lb_col, sizeof(double) * ncol, hipMemcpyHostToDevice, ctx->stream));
   if (ub_col)
@@ -900,19 +899,17 @@ extern "C" int vbmc_mtv(vbmc_ctx* ctx, int D, const vbmc_mtv_side* s1, const vbm
   NEED_DEVICE(ctx);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int ncol = 2 * D, nm = kMtvMesh;
+  Scratch sc;
   KdePlan pl;
-  pl.plan(ncol, nm, s1->n > s2->n ? s1->n : s2->n, false, true, D);
+  pl.plan(sc, ncol, nm, s1->n > s2->n ? s1->n : s2->n, false, true, D);
   const int Kmax = ctx->K > K2 ? ctx->K : K2;
-  size_t o = pl.total;
-  const size_t o_x1 = o; o += (size_t)s1->n * D;
-  const size_t o_x2 = o; o += (size_t)s2->n * D;
-  const size_t o_pack = o; o += pack2.size();
-  const size_t o_sel = o; o += (size_t)2 * (Kmax > 0 ? Kmax : 1) + 2;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, o);
+  const Piece<> p_x[2] = {sc.add((size_t)s1->n * D), sc.add((size_t)s2->n * D)};
+  const auto p_pack = sc.add(pack2.size()), p_sel = sc.add(selector_elems(Kmax > 0 ? Kmax : 1));
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
-  double* base = ctx->d_scratch;
+  double* base = sc.base;
   if (need_mix2)
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_pack, pack2.data(), sizeof(double) * pack2.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(sc.ptr(p_pack), pack2.data(), sizeof(double) * pack2.size(), hipMemcpyHostToDevice, ctx->stream));
   std::vector<double> bnd(2 * (size_t)ncol);
   for (int s = 0; s < 2; ++s)
     for (int d = 0; d < D; ++d) {
@@ -923,14 +920,14 @@ extern "C" int vbmc_mtv(vbmc_ctx* ctx, int D, const vbmc_mtv_side* s1, const vbm
   KdeSrc src = {};
   for (int s = 0; s < 2; ++s) {
     const vbmc_mtv_side& q = *sd[s];
-    double* d_x = base + (s ? o_x2 : o_x1);
+    double* d_x = sc.ptr(p_x[s]);
     if (q.source == VBMC_MTV_HOST) {
       HIP_TRY(ctx, hipMemcpyAsync(d_x, q.x_NxD, sizeof(double) * q.n * D, hipMemcpyHostToDevice, ctx->stream));
     } else {
       // sample(N, True, True, rng="philox", seed): balanced draws of the mixture, then its transformer's inverse
       const bool m2 = q.source == VBMC_MTV_MIX2;
-      rc = launch_sample(ctx, m2 ? base + o_pack : ctx->d_mix, m2 ? ml2 : ctx->ml, m2 ? w2_K : ctx->w.data(), q.n,
-                         q.seed, 1, (void*)(base + o_sel), d_x, nullptr, INFINITY);
+      rc = launch_sample(ctx, m2 ? sc.ptr(p_pack) : ctx->d_mix, m2 ? ml2 : ctx->ml, m2 ? w2_K : ctx->w.data(), q.n,
+                         q.seed, 1, sc.ptr(p_sel), d_x, nullptr, INFINITY);
       if (rc) return rc;
       rc = launch_xf_apply(ctx, m2 ? t2 : t1, q.n, 1, d_x, d_x);
       if (rc) return rc;

@@ -176,15 +176,12 @@ int launch_pdf(vbmc_ctx* ctx, const double* d_pack, const MixLayout& ml, const d
              prod_lam;
     }
   }
-  timed = timed && ctx->timing;
-  if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+  int rc = 0;
+  if (timed && (rc = timing_begin(ctx, T_PDF))) return rc;
 #define CALL(DP) launch_dp<DP>(ctx, a)
   VBMC_DISPATCH_DP(D, CALL);
 #undef CALL
-  if (timed) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-    ctx->ev_valid[2] = true;
-  }
+  if (timed && (rc = timing_end(ctx, T_PDF))) return rc;
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }
@@ -210,15 +207,13 @@ int mixture_pdf_impl(vbmc_ctx* ctx, int64_t n, const double* x_nxD, int log_flag
   const int D = ctx->D;
   // batch so that scratch stays bounded (x [u in place], y, [log|J|, inside], dy)
   const int64_t BATCH = 1 << 22;
-  const size_t per = (size_t)D + 1 + (t ? 2 : 0) + (grad_flag ? D : 0);
   const int64_t nb = n < BATCH ? n : BATCH;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, per * (size_t)nb);
+  Scratch sc;
+  const auto p_x = sc.add((size_t)nb * D), p_y = sc.add((size_t)nb);
+  const auto p_lj = sc.add(t ? (size_t)nb : 0), p_in = sc.add(t ? (size_t)nb : 0), p_dy = sc.add(grad_flag ? (size_t)nb * D : 0);
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
-  double* d_x = ctx->d_scratch;
-  double* d_y = d_x + (size_t)nb * D;
-  double* d_lj = d_y + nb;
-  double* d_in = d_lj + nb;
-  double* d_dy = t ? d_in + nb : d_y + nb;
+  double *d_x = sc.ptr(p_x), *d_y = sc.ptr(p_y), *d_lj = sc.ptr(p_lj), *d_in = sc.ptr(p_in), *d_dy = sc.ptr(p_dy);
   for (int64_t o = 0; o < n; o += nb) {
     const int64_t m = (n - o) < nb ? (n - o) : nb;
     HIP_TRY(ctx, hipMemcpyAsync(d_x, x_nxD + o * D, sizeof(double) * m * D, hipMemcpyHostToDevice,

@@ -581,16 +581,15 @@ extern "C" int vbmc_mixture_mode(vbmc_ctx* ctx, int n_opts, int orig_flag, int64
   const int tiles = (int)((n + K + kThreads - 1) / kThreads);
   const size_t n_cand = cand_RxnxD ? (size_t)n_opts * (size_t)n * D : 0;
   const size_t n_part = (size_t)n_opts * tiles;
-  const size_t need = n_cand + (size_t)K + 2 * n_part + (size_t)n_opts * (5 + 2 * D);
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, need);
+  Scratch sc;
+  const auto p_cand = sc.add(n_cand), p_cdf = sc.add(selector_cdf_elems(K)), p_pv = sc.add(n_part);
+  const auto p_pi = sc.add<long long>(n_part);
+  const auto p_rec = sc.add((size_t)n_opts * 5), p_pts = sc.add((size_t)n_opts * D), p_ys = sc.add((size_t)n_opts * D);
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
-  double* d_cand = ctx->d_scratch;
-  double* d_cdf = d_cand + n_cand;
-  double* d_pv = d_cdf + K;
-  long long* d_pi = (long long*)(d_pv + n_part);
-  double* d_rec = d_pv + 2 * n_part;
-  double* d_pts = d_rec + (size_t)n_opts * 5;
-  double* d_ys = d_pts + (size_t)n_opts * D;
+  double *d_cand = sc.ptr(p_cand), *d_cdf = sc.ptr(p_cdf), *d_pv = sc.ptr(p_pv);
+  long long* d_pi = sc.ptr(p_pi);
+  double *d_rec = sc.ptr(p_rec), *d_pts = sc.ptr(p_pts), *d_ys = sc.ptr(p_ys);
   Selector sel;  // np.random.choice(p=w)'s inverse CDF: sample.hip's selector without balance
   make_selector(ctx->w.data(), K, n, 0, sel);
   HIP_TRY(ctx, hipMemcpyAsync(d_cdf, sel.cdf.data(), sizeof(double) * K, hipMemcpyHostToDevice, ctx->stream));

@@ -174,15 +174,15 @@ void make_selector(const double* w, int K, int64_t N, int balance, Selector& s) 
 }
 
 // Draw N samples of `d_pack` into d_x (device), optionally labels into d_comp.
-// d_sel: device scratch of (K+1) int64 + K doubles.
+// d_sel: device scratch of selector_elems(K) doubles.
 int launch_sample(vbmc_ctx* ctx, const double* d_pack, const MixLayout& ml, const double* w_host,
-                  int64_t N, uint64_t seed, int balance, void* d_sel, double* d_x, int32_t* d_comp,
+                  int64_t N, uint64_t seed, int balance, double* d_sel, double* d_x, int32_t* d_comp,
                   double df) {
   const int K = ml.K;
   Selector s;
   make_selector(w_host, K, N, balance, s);
-  int64_t* d_cum = (int64_t*)d_sel;
-  double* d_cdf = (double*)(d_cum + K + 1);
+  int64_t* d_cum = selector_cum(d_sel);
+  double* d_cdf = selector_cdf(d_sel, K);
   HIP_TRY(ctx, hipMemcpyAsync(d_cum, s.cum.data(), sizeof(int64_t) * (K + 1), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_cdf, s.cdf.data(), sizeof(double) * K, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));  // the selector vectors are locals
@@ -231,19 +231,20 @@ static int mixture_sample_impl(vbmc_ctx* ctx, int64_t N, uint64_t seed, int bala
   const int D = ctx->D, K = ctx->K;
   // one launch covers all N indices so that sample n does not depend on the batching;
   // x is produced in full and copied back in one piece (N x D doubles of scratch)
-  const size_t n_x = x_NxD ? (size_t)N * D : 0;
-  const size_t n_c = comp_N ? ((size_t)N + 1) / 2 : 0;  // int32 labels, in doubles
-  const size_t n_sel = (size_t)2 * K + 2;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, n_x + n_c + n_sel);
+  Scratch sc;
+  const auto p_x = sc.add(x_NxD ? (size_t)N * D : 0);
+  const auto p_c = sc.add<int32_t>(comp_N ? (size_t)N : 0);
+  const auto p_sel = sc.add(selector_elems(K));
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
-  double* d_x = x_NxD ? ctx->d_scratch : nullptr;
-  int32_t* d_c = comp_N ? (int32_t*)(ctx->d_scratch + n_x) : nullptr;
-  void* d_sel = (void*)(ctx->d_scratch + n_x + n_c);
+  double* d_x = x_NxD ? sc.ptr(p_x) : nullptr;
+  int32_t* d_c = comp_N ? sc.ptr(p_c) : nullptr;
+  double* d_sel = sc.ptr(p_sel);
   rc = launch_sample(ctx, ctx->d_mix, ctx->ml, ctx->w.data(), N, seed, balance_flag, d_sel, d_x, d_c, df);
   if (rc) return rc;
   if (x_NxD) {
     if (t && (rc = launch_xf_apply(ctx, *t, N, 1, d_x, d_x))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(x_NxD, d_x, sizeof(double) * n_x, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(x_NxD, d_x, sizeof(double) * p_x.count, hipMemcpyDeviceToHost, ctx->stream));
   }
   if (comp_N)
     HIP_TRY(ctx, hipMemcpyAsync(comp_N, d_c, sizeof(int32_t) * N, hipMemcpyDeviceToHost, ctx->stream));
@@ -283,19 +284,17 @@ static int kl_div_mc_impl(vbmc_ctx* ctx, const char* who, int64_t N, uint64_t se
   if (rc) return rc;
   const int nblk = 512;
   const int Kmax = K1 > K2 ? K1 : K2;
-  const size_t n_xf = t1 ? (size_t)N * D + 2 * (size_t)N : 0;  // u, log|J|, inside
-  const size_t need = (size_t)ml2.total + (size_t)N * D + n_xf + 2 * (size_t)N + (size_t)2 * Kmax + 2 + 2 * (size_t)nblk;
-  rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, need);
+  Scratch sc;
+  const auto p_pack2 = sc.add((size_t)ml2.total), p_x = sc.add((size_t)N * D);
+  const auto p_u = sc.add(t1 ? (size_t)N * D : 0);  // the points the densities are taken at: x itself without transformers
+  const auto p_y1 = sc.add((size_t)N), p_y2 = sc.add((size_t)N);
+  const auto p_lj = sc.add(t1 ? (size_t)N : 0), p_in = sc.add(t1 ? (size_t)N : 0);  // log|J|, inside
+  const auto p_sel = sc.add(selector_elems(Kmax)), p_part = sc.add(2 * (size_t)nblk);
+  rc = reserve(ctx, sc);
   if (rc) return rc;
-  double* d_pack2 = ctx->d_scratch;
-  double* d_x = d_pack2 + ml2.total;
-  double* d_u = t1 ? d_x + (size_t)N * D : d_x;  // the points the densities are taken at
-  double* d_y1 = d_u + (size_t)N * D;
-  double* d_y2 = d_y1 + N;
-  double* d_lj = d_y2 + N;
-  double* d_in = d_lj + N;
-  void* d_sel = (void*)(t1 ? d_in + N : d_y2 + N);
-  double* d_part = (double*)d_sel + 2 * Kmax + 2;
+  double *d_pack2 = sc.ptr(p_pack2), *d_x = sc.ptr(p_x), *d_u = t1 ? sc.ptr(p_u) : d_x;
+  double *d_y1 = sc.ptr(p_y1), *d_y2 = sc.ptr(p_y2), *d_lj = sc.ptr(p_lj), *d_in = sc.ptr(p_in);
+  double *d_sel = sc.ptr(p_sel), *d_part = sc.ptr(p_part);
   HIP_TRY(ctx, hipMemcpyAsync(d_pack2, pack2.data(), sizeof(double) * ml2.total, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, stream_wait(ctx));
   std::vector<double> part(2 * (size_t)nblk);

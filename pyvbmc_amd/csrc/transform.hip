@@ -338,10 +338,11 @@ extern "C" int vbmc_transform(vbmc_ctx* ctx, int64_t n, int direction, const dou
   const int64_t BATCH = (int64_t)1 << 21;
   const int64_t nb = n < BATCH ? n : BATCH;
   const size_t n_out = direction == 2 ? 1 : (size_t)D;
-  int rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, (size_t)nb * (D + n_out));
+  Scratch sc;
+  const auto p_in = sc.add((size_t)nb * D), p_out = sc.add((size_t)nb * n_out);
+  int rc = reserve(ctx, sc);
   if (rc) return rc;
-  double* d_in = ctx->d_scratch;
-  double* d_out = d_in + (size_t)nb * D;
+  double *d_in = sc.ptr(p_in), *d_out = sc.ptr(p_out);
   for (int64_t o = 0; o < n; o += nb) {
     const int64_t m = (n - o) < nb ? (n - o) : nb;
     HIP_TRY(ctx, hipMemcpyAsync(d_in, in + o * D, sizeof(double) * m * D, hipMemcpyHostToDevice, ctx->stream));
@@ -364,14 +365,12 @@ extern "C" int vbmc_mixture_moments_orig(vbmc_ctx* ctx, int64_t N, uint64_t seed
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int D = ctx->D, K = ctx->K, P = D * (D + 1) / 2;
   const int nblk = 512;
-  const size_t need = (size_t)N * D + (size_t)2 * K + 2 + (size_t)nblk * (D > P ? D : P) + D + P;
-  rc = ensure_dev(ctx, &ctx->d_scratch, &ctx->d_scratch_cap, need);
+  Scratch sc;
+  const auto p_x = sc.add((size_t)N * D), p_sel = sc.add(selector_elems(K));
+  const auto p_part = sc.add((size_t)nblk * (D > P ? D : P)), p_mean = sc.add((size_t)D), p_cov = sc.add((size_t)P);
+  rc = reserve(ctx, sc);
   if (rc) return rc;
-  double* d_x = ctx->d_scratch;
-  void* d_sel = (void*)(d_x + (size_t)N * D);
-  double* d_part = (double*)d_sel + 2 * K + 2;
-  double* d_mean = d_part + (size_t)nblk * (D > P ? D : P);
-  double* d_cov = d_mean + D;
+  double *d_x = sc.ptr(p_x), *d_sel = sc.ptr(p_sel), *d_part = sc.ptr(p_part), *d_mean = sc.ptr(p_mean), *d_cov = sc.ptr(p_cov);
   // the balanced samples of sample(N, orig_flag=True, balance_flag=True) (:791-796), never copied out
   rc = launch_sample(ctx, ctx->d_mix, ctx->ml, ctx->w.data(), N, seed, 1, d_sel, d_x, nullptr, INFINITY);
   if (rc) return rc;

@@ -100,7 +100,7 @@ def mcmc_shape(i, reps):
         ms, kms = [], []
         for _ in range(reps):
             ms.append(call(n_mcmc, sampler="device", seed=3)[0])
-            kms.append(ctx.last_kernel_ms(7))
+            kms.append(ctx.last_kernel_ms(_lib.T_IS_MCMC))
         st = ctx.__dict__["_is_mcmc_stats"]
         row = {"row": f"{tag}_device_threads{nt}", "call_ms": round(statistics.median(ms), 3),
                "step2_device_ms": round(statistics.median(ms) - base, 3), "kernel_ms": round(statistics.median(kms), 3),

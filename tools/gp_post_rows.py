@@ -89,7 +89,7 @@ def run_shape(D, N, S, reps, warm):
     k = []
     for _ in range(warm + reps):
         build(N, True, False)
-        k.append(ctx.last_kernel_ms(6))
+        k.append(ctx.last_kernel_ms(_lib.T_GP_POST))
     ctx.set_timing(0)
     row["chol_kernels_ms"] = round(statistics.median(k[warm:]), 4)
     row["c_lt_a"] = row["c_device_update_nofetch_ms"] < row["a_host_update_upload_ms"]

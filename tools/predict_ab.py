@@ -27,11 +27,11 @@ for S in (1, 4):
         ctx.set_timing(1)
         for _ in range(15):
             gp.predict(xs, separate_samples=True)
-            pm.append(ctx.last_kernel_ms(3))
+            pm.append(ctx.last_kernel_ms(_lib.T_PREDICT))
         ctx.set_timing(2)
         for _ in range(15):
             gp.predict(xs, separate_samples=True)
-            vm.append(ctx.last_kernel_ms(5))
+            vm.append(ctx.last_kernel_ms(_lib.T_PREDICT_VAR))
         ctx.set_timing(False)
         print(f"cfg {cfg} S={S} M={M}: all launches {1e3 * np.median(pm):.2f} us (min {1e3 * min(pm):.2f}), "
               f"K* -> product events {1e3 * np.median(vm):.2f} us; sums {fmu.sum():.15e} {fs2.sum():.15e}", flush=True)
