@@ -197,6 +197,10 @@ int vbmc_set_release_callback(vbmc_ctx* ctx, void (*fn)(void*), void* user);
  *                  (csrc/entropy_args.h WsSpan); 0 = equal chunks per component
  *   "ws_front"     [VBMC_WS_FRONT]: that share (0 = built-in per instantiation); "ws_pad" [VBMC_WS_PAD]:
  *                  batches a component's end is priced at when the parts are cut (-1 = built-in)
+ *   "ws_roles"     [VBMC_WS_ROLES]: 1 = which components a wave of the wave-split kernel takes is its role,
+ *                  (wave + 2) mod 4 in the second workgroup of a CU and the wave index elsewhere, and a wave's
+ *                  loops end behind the ceil((K - role) / 4) components it owns (default); 0 = role = wave and
+ *                  every wave runs over all 4 KTMAX table rows.  Bit-identical results either way.
  * The results of an evaluation do not depend on any of these -- except that "ws_span" / "ws_front" /
  * "ws_pad" change how the Monte-Carlo rows are grouped into partial sums, i.e. the last bits of the
  * entropy (<= 1e-15 relative); for given values every evaluation is bit-reproducible.
@@ -207,8 +211,8 @@ int vbmc_set_option(vbmc_ctx* ctx, const char* key, int value);
  * vbmc_neg_elcbo, the optimiser loop): out[0] = kernel (0 generic, 1 wave-split on equal chunks, 2 small-
  * sample, 3 matrix-pipe form, 4 the fused optimiser loop: no entropy launch of its own, 5 wave-split in span
  * mode), out[1] = 64-row batches per workgroup (the wave-split kernel's batch loop count; span mode: the
- * longest part), out[2] = partial rows (workgroups) per component, out[3] = 1 if the draws were read from
- * HBM, 0 if generated in-line.  Lets the parity tests assert which code path they exercised. */
+ * longest part), out[2] = partial rows (workgroups) per component, out[3] = bit 0: the draws were read from
+ * HBM (clear: generated in-line), bit 1: the wave-split kernel ran with "ws_roles".  Lets the parity tests assert which code path they exercised. */
 int vbmc_last_entmc_plan(const vbmc_ctx* ctx, int out[4]);
 
 /* Host utility (no device, no ctx): the span-mode partition of the wave-split entropy kernel for cus CUs of

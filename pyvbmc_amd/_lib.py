@@ -352,11 +352,12 @@ class Context:
         """Launch geometry of the most recent Monte-Carlo entropy: which kernel ran, how many
         64-row batches each workgroup looped over (span mode: the longest part), partial rows per
         component, draw source; ``span``: the wave-split kernel ran in span mode (front / filler parts
-        sized to end together, csrc/entropy_args.h) rather than on equal chunks."""
+        sized to end together, csrc/entropy_args.h) rather than on equal chunks; ``roles``: it ran with option
+        ``ws_roles`` (rotated roles, loops that end at the components a wave owns)."""
         out = (C.c_int * 4)()
         self.check(self._lib.vbmc_last_entmc_plan(self._h, out))
         return {"kernel": ("valu", "ws", "small", "mfma", "adam_fused", "ws", "ws")[out[0]] if out[0] >= 0 else None, "rg": out[1],
-                "chunks": out[2], "resident_draws": bool(out[3]), "span": out[0] in (5, 6), "adam_tail": out[0] == 6}
+                "chunks": out[2], "resident_draws": bool(out[3] & 1), "roles": bool(out[3] & 2), "span": out[0] in (5, 6), "adam_tail": out[0] == 6}
 
     def philox_normals(self, K, n_half, D, seed, row_begin=0, row_count=None):
         """[K][row_count][D] draws of the device generator (vbmc_philox_normals)."""

@@ -267,6 +267,7 @@ struct vbmc_ctx {
   int opt_ws_span = 1;      // entropy kernel: span mode (entropy_args.h WsSpan: front / filler parts sized to end together); 0 = equal chunks
   int opt_ws_front = 0;     // span mode: the front workgroup's share of a CU's batches, per mille (0 = the built-in value)
   int opt_ws_pad = -1;      // span mode: padding slots behind every component (-1 = the built-in value)
+  int opt_ws_roles = 1;     // wave-split kernel: rotated roles in a CU's filler workgroup, loops end at the components owned (EntArgs::roles); 0 = role = wave, all rows
   int opt_mix_bar = 1;      // host-driven step: pack written by the CPU into device memory (no upload launch), GP sums in the finish launch
   double* h_pack_dev = nullptr;     // device-side address of h_pack ...
   double* h_pack_dev_of = nullptr;  // ... valid for this h_pack

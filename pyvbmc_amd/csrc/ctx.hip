@@ -116,6 +116,8 @@ static void options_from_env(vbmc_ctx* c) {
   if (e) c->opt_ws_front = atoi(e);
   e = getenv("VBMC_WS_PAD");
   if (e) c->opt_ws_pad = atoi(e);
+  e = getenv("VBMC_WS_ROLES");
+  c->opt_ws_roles = !(e && e[0] == '0');
   e = getenv("VBMC_MIX_BAR");
   c->opt_mix_bar = !(e && e[0] == '0');
   e = getenv("VBMC_PREDICT_DMA");
@@ -345,6 +347,7 @@ int vbmc_set_option(vbmc_ctx* ctx, const char* key, int value) {
   else if (!strcmp(key, "predict_fused")) ctx->opt_predict_fused = value < 0 ? 0 : value > 2 ? 2 : value;
   else if (!strcmp(key, "mix_bar")) ctx->opt_mix_bar = value != 0;
   else if (!strcmp(key, "ws_span")) ctx->opt_ws_span = value != 0;
+  else if (!strcmp(key, "ws_roles")) ctx->opt_ws_roles = value != 0;
   else if (!strcmp(key, "ws_pad")) ctx->opt_ws_pad = value > 8 ? 8 : value;
   else if (!strcmp(key, "ws_front")) ctx->opt_ws_front = value < 0 ? 0 : value > 990 ? 990 : value;
   else if (!strcmp(key, "elbo_arm")) ctx->opt_elbo_arm = value < 0 ? 0 : value > 2 ? 2 : value;  // 1: only while this context is alone on its device; 2: always

@@ -446,6 +446,7 @@ int entmc_plan(vbmc_ctx* ctx, int64_t ns_per_comp, int eps_mode, uint64_t seed, 
       }
     }
   }
+  a.roles = ws && ctx->opt_ws_roles ? 1 : 0;
   a.pair_cus = 0;
   if (ws) {
     // one round of the 2-waves/SIMD build: workgroups b and b + CUs share a CU (entropy_ws.hip)
@@ -677,7 +678,7 @@ int entmc_launch_main(vbmc_ctx* ctx, const EntPlan& p) {
   ctx->last_plan[0] = (int)p.kernel;
   ctx->last_plan[1] = a.rg;
   ctx->last_plan[2] = a.chunks;
-  ctx->last_plan[3] = a.eps_mode == VBMC_EPS_RESIDENT ? 1 : 0;
+  ctx->last_plan[3] = (a.eps_mode == VBMC_EPS_RESIDENT ? 1 : 0) | ((p.kernel == EntKernel::Ws || p.kernel == EntKernel::WsSpan) && a.roles ? 2 : 0);
   const bool bracket = ctx->timing && (p.kernel == EntKernel::Valu || p.kernel == EntKernel::Small);
   if (bracket) HIP_TRY(ctx, hipEventRecord(ctx->ev[2 * T_ENTMC], ctx->stream));
   switch (p.kernel) {

@@ -84,6 +84,10 @@ struct EntArgs {
   int pair_cus = 0;
   WsSpan sp;          // wave-split kernel: span mode (above); then chunks = sp.R and rg = the longest part
   int gp_wgs = 0;     // span mode: workgroups of the GP row (blocks behind the entropy parts)
+  // wave-split kernel: 1 = the waves of a CU's filler workgroup take the components of the role two on (so that
+  // every SIMD hosts one heavy and one light role) and every wave leaves its loops behind the components it owns;
+  // 0 = role = wave and every wave runs over all KTMAX rows (option "ws_roles").  The results do not depend on it.
+  int roles = 0;
   // armed evaluation (common.h ArmedEval): every workgroup returns at once when *cancel == ~0
   const uint64_t* cancel = nullptr;
   // matrix-pipe kernel in the host-driven step (round 6): the GP sums of the prep launch IN FRONT of this one lie in device
@@ -101,16 +105,35 @@ struct EntArgs {
 // register-array size (components per wave) the wave-split launcher picks, and the waves per SIMD
 // its build runs at (= resident workgroups per CU: a workgroup is one wave on each SIMD).
 // The (j,k) table always carries 4 * ws_ktmax_for(K) rows per component j (ws_table_rows): the rows
-// beyond K are components of density exactly 0, so the kernel's loops run over whole register arrays
-// with no per-component guards.  (Rounds 1-2 padded to 4 ceil(K/4) only and kept a guarded variant for
-// ceil(K/4) < KTMAX; that variant ran 2-3.5x slower per evaluated pair than the guard-free one --
-// K = 48 against K = 50 at D = 10: 3 699 against 1 592 ps per pair, tools/ws_k_probe.py -- far more
-// than the padding costs.)
+// beyond K are components of density exactly 0, so a wave may run over its whole register array.
+// (Rounds 1-2 padded to 4 ceil(K/4) only and kept a guarded variant -- `if (kk < KT)` around every
+// component's block, the row prefetch conditional too -- for ceil(K/4) < KTMAX; that variant ran
+// 2-3.5x slower per evaluated pair than the guard-free one -- K = 48 against K = 50 at D = 10: 3 699
+// against 1 592 ps per pair, tools/ws_k_probe.py: the scalar row buffers became phis and spilled.
+// With EntArgs::roles the unrolled loops instead LEAVE at the first component a wave does not own
+// (ws_kt_role, one scalar compare and branch in front of a block that is otherwise the guard-free
+// one; the row prefetch stays unconditional, the table rows exist): profiles/ws_roles.md.)
 constexpr int ws_ktmax_for(int K) {
   const int KT = (K + 3) / 4;
   return KT <= 4 ? 4 : KT <= 8 ? 8 : KT <= 10 ? 10 : KT <= 13 ? 13 : KT <= 16 ? 16 : KT <= 20 ? 20 : KT <= 25 ? 25 : 32;
 }
 constexpr int ws_table_rows(int K) { return 4 * ws_ktmax_for(K); }
+// components role r of a workgroup owns (k = r, r + 4, ...): ceil((K - r) / 4)
+constexpr int ws_kt_role(int K, int r) { return K > r ? (K - r + 3) / 4 : 0; }
+// the fewest components a role owns among the K that ws_ktmax_for sends to register-array size ktmax (K above four times
+// the next smaller size; at least 1: with K <= 3 a role that owns no component runs over one padding row)
+constexpr int ws_ktmin_for(int ktmax) {
+  return ktmax <= 4 ? 1 : ktmax <= 8 ? 4 : ktmax <= 10 ? 8 : ktmax <= 13 ? 10 : ktmax <= 16 ? 13 : ktmax <= 20 ? 16 : ktmax <= 25 ? 20 : 25;
+}
+constexpr bool ws_kt_roles_cover(int kmax) {
+  for (int K = 1; K <= kmax; ++K) {
+    if (K >= 4 && ws_kt_role(K, 3) < ws_ktmin_for(ws_ktmax_for(K))) return false;
+    if (ws_kt_role(K, 0) + ws_kt_role(K, 1) + ws_kt_role(K, 2) + ws_kt_role(K, 3) != K) return false;
+    if (ws_kt_role(K, 0) > ws_ktmax_for(K) || ws_kt_role(K, 3) > ws_kt_role(K, 2) || ws_kt_role(K, 2) > ws_kt_role(K, 1)) return false;
+  }
+  return true;
+}
+static_assert(ws_kt_roles_cover(128), "the four roles own every component once, each at least ws_ktmin_for; roles 2 and 3 are the lightest");
 constexpr int ws_min_waves(int dp, int ktmax, bool grad) {
 #ifdef VBMC_WS_FORCE_WAVES
   return VBMC_WS_FORCE_WAVES;

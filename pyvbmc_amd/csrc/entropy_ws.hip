@@ -14,7 +14,8 @@
 //     registers; to make that fit, the K components are split over the 4 waves of a
 //     workgroup ("ws" = wave-split):
 //                 lane = antithetic-pair row (64 rows per batch),
-//                 wave w owns components k = w, w+4, w+8, ...  (KT = ceil(K/4)).
+//                 the wave of role r owns components k = r, r+4, r+8, ...  (KT = ceil(K/4);
+//                 the role is the wave's SIMD, rotated by two in a CU's second workgroup: below).
 //     Everything indexed by k is therefore wave-uniform: the per-(j,k) constants
 //     (Delta_jk row, log2 density at the component mean, exponent scale, weights) come from a
 //     small precomputed table through SCALAR loads and feed the FMAs as SGPR operands
@@ -29,6 +30,8 @@
 // Output: the same per-workgroup partial rows as entropy.hip, reduced by its kernels
 // (entmc_finish_kernel, mu_from_w = 1).
 #include <hip/hip_ext.h>
+
+#include <type_traits>
 
 #include "adam_dev.h"
 #include "common.h"
@@ -92,8 +95,8 @@ constexpr int WAVES = WG / 64;
 __device__ __forceinline__ double wave_sum(double v) { return fm::wave_sum_dpp(v); }
 
 // The (j,k) table rows [Delta_jk (DP) | a | c | lrc | w | wis2 | pad] are written by prep.hip, always
-// 4 KTMAX of them per component j (padding components have zero density, entropy_args.h): the loops
-// over a wave's components carry no guards.
+// 4 KTMAX of them per component j (padding components have zero density, entropy_args.h): the blocks
+// of the loops over a wave's components carry no guards; the loops end behind the components the wave owns.
 // Per-lane state is ~(4 DP + 3 KTMAX) doubles with gradients.  Up to ~95 it fits the 256
 // registers of 2 waves/SIMD; beyond that one wave per SIMD with the 512-register budget
 // (AGPRs as spill space) beats spilling to scratch memory.
@@ -128,6 +131,28 @@ constexpr int ws_epi_doubles(int dp, int ktmax, bool grad) {
   return nq == 0 ? 0 : WAVES * (1 + 2 * dp + ktmax) * ((64 >> nq) + 1);
 }
 
+// f(kk) for kk = 0 .. KTMAX - 1 in turn, leaving in front of kk == kt (wave-uniform, KTMIN <= kt): a fully unrolled loop
+// with an early exit.  A register-array size serves the K above the next smaller one's 4 KTMIN only, so no role owns
+// fewer than KTMIN components (ws_ktmin_for) and the first KTMIN blocks stay one straight run without tests.
+// Written as a recursion: the unroller does not fully unroll a loop of which it knows only a trip-count bound > 8.
+template <int KK, int KTMIN, int KTMAX, class F>
+__device__ __forceinline__ void ws_for_owned(int kt, F&& f) {
+  if constexpr (KK < KTMAX) {
+    if constexpr (KK >= KTMIN)
+      if (KK == kt) return;
+    f(std::integral_constant<int, KK>());
+    ws_for_owned<KK + 1, KTMIN, KTMAX>(kt, f);
+  }
+}
+// At the end of a block, on the table row it requested in front of its arithmetic.  Only the next block reads that
+// row, and between the two stands the exit test: with no use in the block itself the compiler moves the request behind
+// the test, right in front of its wait, and every component pays a scalar-load latency.  (The row has landed by now.)
+template <int N>
+__device__ __forceinline__ void ws_keep(const double (&r)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) asm volatile("" : : "s"(r[i]));
+}
+
 #if defined(WS_TIMES) && VBMC_DP == 10
 __device__ unsigned long long g_ws_times[1024 * 4];  // per workgroup: start, batch loop start, batch loop end, end
 #define WS_STAMP(i) do { if (threadIdx.x == 0) g_ws_times[(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (i)] = wall_clock64(); } while (0)
@@ -150,6 +175,7 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
   // lie in memory ([2][64 rows][DP]), filled one batch ahead by LDS-direct loads (ws_fill below)
   __shared__ __attribute__((aligned(16))) double sE[PHILOX ? GB : 2][DP][64];
   __shared__ double sRed[WAVES][2 * DP + 1];
+  __shared__ int sSimd[WAVES];                    // the SIMD each wave runs on (roles)
   extern __shared__ double dyn[];                 // [epilogue transpose buffer | sW[K4]]
   constexpr int EPI = ws_epi_doubles(DP, KTMAX, GRAD);
   double* sW = dyn + EPI;
@@ -214,9 +240,11 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
   int64_t g_lo, g_hi;
   int nb, part = 0, chunk_slot = 0, j_chunk = 0;
   int nbv;  // slots per component in the list that is cut: its batches, then (span mode) the padding slots
+  bool filler = false;  // the second workgroup of its CU (dispatched in the second round)
   if (span) {
     nb = a.sp.nb;
     nbv = a.sp.nbv();
+    filler = (int)blockIdx.x >= a.sp.cus;
     part = a.sp.part_of_block((int)blockIdx.x);
     g_lo = a.sp.lo(part);
     g_hi = a.sp.lo(part + 1);
@@ -230,6 +258,7 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
     if (a.pair_cus > 0) {
       const int total = a.ml.K * a.chunks, b = j * a.chunks + chunk;
       const int paired = total - a.pair_cus;  // workgroups of the second round = pairs (b, b + pair_cus)
+      filler = b >= a.pair_cus;
       if (paired > 0 && b < 2 * a.pair_cus) {
         const int m = b < a.pair_cus ? b : b - a.pair_cus;
         const int item = m < paired ? 2 * m + (b >= a.pair_cus ? 1 : 0) : paired + m;
@@ -247,6 +276,28 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
   }
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // Which components a wave takes is its ROLE: k = role, role + 4, ...  For K = 4 KT - 2 (the headline's 50) roles 0 and
+  // 1 own one component more than roles 2 and 3.  A workgroup's four waves sit on the four SIMDs of its CU, one each, but
+  // in an order that differs from workgroup to workgroup (tools/probes/placement.hip, profiles/ws_roles.md), so the role
+  // is taken from the SIMD the wave runs on: role = SIMD in the first workgroup of a CU, SIMD + 2 in the filler -- every
+  // SIMD then hosts one heavy and one light role.  (The four ids are checked through LDS: role = wave if they are not
+  // distinct.)  The logarithms go to roles 2 and 3, never heavier than the other two.  Everything summed across waves
+  // (sQ, sRed, sW, the epilogue's rows) is indexed by role: the results depend neither on the placement nor on the
+  // rotation.  The draw staging (ws_fill, the Philox slots) is dealt by the plain wave index.
+  int role = wave;
+  if (a.roles) {
+    const int simd = (int)__builtin_amdgcn_s_getreg(4 | (4 << 6) | (1 << 11));  // HW_ID bits 5:4
+    if (lane == 0) sSimd[wave] = simd;
+    __syncthreads();
+    const int seen = (1 << sSimd[0]) | (1 << sSimd[1]) | (1 << sSimd[2]) | (1 << sSimd[3]);
+    role = __builtin_amdgcn_readfirstlane(seen == 0xF ? (simd + (filler ? 2 : 0)) & 3 : wave);
+  }
+  // the components this role owns: both loops over kk leave at kk == kt_r (a.roles == 0: they run over all KTMAX rows).
+  // Never fewer than KTMIN for the K this instantiation serves; with one of K <= 3 a role that owns none runs over one
+  // padding row.
+  constexpr int KTMIN = ws_ktmin_for(KTMAX);
+  const int kt_own = ws_kt_role(a.ml.K, role);
+  const int kt_r = __builtin_amdgcn_readfirstlane(a.roles ? (kt_own > KTMIN ? kt_own : KTMIN) : KTMAX);
   WS_STAMP(0);
   constexpr bool eps_exact = !PHILOX && STAGE != 0;
 
@@ -407,7 +458,7 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
     // zero offset ties the loads to this iteration so they stay streaming scalar loads.
     int zoff;
     asm volatile("s_mov_b32 %0, 0" : "=s"(zoff));
-    const double* Tw = Tj + (size_t)wave * TS + zoff;
+    const double* Tw = Tj + (size_t)role * TS + zoff;
 
     // ---- pass 1 over this wave's components: densities (cached) and partial q ----
     // The table row of component kk+1 is requested (scalar loads -> SGPRs) as soon as row kk
@@ -416,14 +467,21 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
     double qp = 0.0, qm = 0.0;
     double rp_[KTMAX], rm_[KTMAX];
     constexpr int NR1 = DP + 3;  // Delta, c0, a, w
-    double cur[NR1], nxt[NR1];
+    double cur[NR1];
     {
       const double* tr = Tw;
 #pragma unroll
       for (int i = 0; i < NR1; ++i) cur[i] = tr[i];
     }
-#pragma unroll
-    for (int kk = 0; kk < KTMAX; ++kk) {
+    // the wave owns kt_r components: leave in front of the first one it does not (a scalar compare and branch; the
+    // block behind it is the unguarded one, its request for row kk + 1 included -- the table has the row).
+    // The count goes through an opaque copy per pass: compared as it is, the KTMAX tests are loop invariants that
+    // the compiler forms in front of the batch loop and keeps as lane masks in spilled SGPR pairs.
+    int kt1;
+    asm volatile("s_mov_b32 %0, %1" : "=s"(kt1) : "s"(kt_r));
+    ws_for_owned<0, KTMIN, KTMAX>(kt1, [&](auto kc) __attribute__((always_inline)) {
+      constexpr int kk = decltype(kc)::value;
+      double nxt[NR1];
       {
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): row kk is in SGPRs
         __builtin_amdgcn_sched_barrier(0);
@@ -446,20 +504,21 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
         qm = fma(cur[DP + 2], rm, qm);
 #pragma unroll
         for (int i = 0; i < NR1; ++i) cur[i] = nxt[i];
+        if (kk + 1 < KTMAX && kk + 1 >= KTMIN) ws_keep(cur);
       }
-    }
+    });
     // ---- q = sum over the 4 waves ----
     const int buf = it & 1;
-    sQ[buf][wave][0][lane] = qp;
-    sQ[buf][wave][1][lane] = qm;
+    sQ[buf][role][0][lane] = qp;
+    sQ[buf][role][1][lane] = qm;
     if constexpr (eps_exact) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the next batch's rows
     __syncthreads();
     qp = (sQ[buf][0][0][lane] + sQ[buf][1][0][lane]) + (sQ[buf][2][0][lane] + sQ[buf][3][0][lane]);
     qm = (sQ[buf][0][1][lane] + sQ[buf][1][1][lane]) + (sQ[buf][2][1][lane] + sQ[buf][3][1][lane]);
 
-    // log q: wave 0 takes the + samples, wave 1 the - samples
-    if (wave < 2) {
-      const double qv = valid ? (wave == 0 ? qp : qm) : 1.0;
+    // log q: role 2 takes the + samples, role 3 the - samples
+    if (role >= 2) {
+      const double qv = valid ? (role == 2 ? qp : qm) : 1.0;
       lmant *= __builtin_amdgcn_frexp_mant(qv);  // [1/2, 1) each: eight of them stay far from underflow; q = 0 -> 0 -> -inf
       lexp += __builtin_amdgcn_frexp_exp(qv);
       if ((it & (LOGB - 1)) == LOGB - 1 || it + 1 == n_it) {
@@ -486,15 +545,19 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
 #pragma unroll
       for (int d = 0; d < DP; ++d) Td[d] = 0.0;
       constexpr int NR2 = DP + 4;  // Delta, (c0, a, w skipped), wis2
-      double c2[NR2], n2[NR2];
+      double c2[NR2];
       {
         const double* tr = Tw;
 #pragma unroll
         for (int d = 0; d < DP; ++d) c2[d] = tr[d];
         c2[DP + 3] = tr[DP + 3];
       }
-#pragma unroll
-      for (int kk = 0; kk < KTMAX; ++kk) {
+      // (ends as pass 1 does; Wacc of the components not owned stays 0, which is what their rows give)
+      int kt2;
+      asm volatile("s_mov_b32 %0, %1" : "=s"(kt2) : "s"(kt_r));
+      ws_for_owned<0, KTMIN, KTMAX>(kt2, [&](auto kc) __attribute__((always_inline)) {
+        constexpr int kk = decltype(kc)::value;
+        double n2[NR2];
         {
           __builtin_amdgcn_s_waitcnt(0xC07F);
           __builtin_amdgcn_sched_barrier(0);
@@ -517,8 +580,13 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
 #pragma unroll
           for (int d = 0; d < DP; ++d) c2[d] = n2[d];
           c2[DP + 3] = n2[DP + 3];
+          if (kk + 1 < KTMAX && kk + 1 >= KTMIN) {
+#pragma unroll
+            for (int d = 0; d < DP; ++d) asm volatile("" : : "s"(c2[d]));
+            asm volatile("" : : "s"(c2[DP + 3]));
+          }
         }
-      }
+      });
       const double cs = sig_j * sgs, cd = sig_j * sgd;
 #pragma unroll
       for (int d = 0; d < DP; ++d) {
@@ -542,7 +610,7 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
       return v;
     };
     {
-      double* mine = dyn + (size_t)wave * NI * RS + (lane / GL);  // mine[item * RS]
+      double* mine = dyn + (size_t)role * NI * RS + (lane / GL);  // mine[item * RS]
       const bool wr = (lane & (GL - 1)) == 0;
       double v = group(slog_acc);
       if (wr) mine[0] = v;
@@ -586,7 +654,7 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
   } else {
     {
       const double v = wave_sum(slog_acc);
-      if (lane == 0) sRed[wave][0] = v;
+      if (lane == 0) sRed[role][0] = v;
     }
     if (GRAD) {
 #pragma unroll
@@ -594,15 +662,15 @@ __global__ __launch_bounds__(WG, ws_min_waves(DP, KTMAX, GRAD)) void entmc_ws_ke
         const double vmu = wave_sum(mu_acc[d]);
         const double vlam = wave_sum(lam_acc[d]);
         if (lane == 0) {
-          sRed[wave][1 + d] = vmu;
-          sRed[wave][1 + DP + d] = vlam;
+          sRed[role][1 + d] = vmu;
+          sRed[role][1 + DP + d] = vlam;
         }
       }
 #pragma unroll
       for (int kk = 0; kk < KTMAX; ++kk)
         {
           const double v = wave_sum(Wacc[kk]);
-          if (lane == 0) sW[4 * kk + wave] = v;
+          if (lane == 0) sW[4 * kk + role] = v;
         }
     }
     __syncthreads();
