@@ -127,7 +127,8 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on);
  *            the product kernel, not the production configuration; a predict at level 0 / 1 invalidates the record
  *            (VBMC_E_ARG "no timed launch recorded", never a stale interval).
  *        6 = vbmc_gp_posterior's blocked Cholesky factorisation alone (all its block steps),
- *        7 = vbmc_is_mcmc's launch (all S chains). */
+ *        7 = vbmc_is_mcmc's launch (all S chains),
+ *        8 = vbmc_gp_lml's last chunk: its factorisation and its value / gradient kernels. */
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out);
 
 /* Host-side wall-clock breakdown (microseconds) of the most recent vbmc_neg_elcbo:
@@ -421,6 +422,23 @@ int vbmc_gp_append(vbmc_ctx* ctx, const double* x_D, double y, double* alpha_SxN
 
 /* Copy the resident posterior out: alpha (S x N) and L (S x N x N), both nullable. */
 int vbmc_gp_fetch(vbmc_ctx* ctx, double* alpha_SxN, double* L_SxNxN);
+
+/* Log marginal likelihood of the training data and its gradient for B hyper-parameter candidates: the objective of GP
+ * hyper-parameter fitting (gpyreg's; not part of the reference tree -- the textbook formula).  Per candidate, with C =
+ * K + diag(sn2) = sl A, U^T U = A, r = y - m(X), alpha = C^-1 r and sl = sn2_div as in vbmc_gp_posterior:
+ *   lml = -1/2 r.alpha - sum_i log U_ii - N/2 log(2 pi sl),
+ *   dlml/dtheta = -1/2 tr((C^-1 - alpha alpha^T) dC/dtheta) for [log ell (D), log sf, log sn], alpha . dm/dtheta for the
+ * mean's parameters, in the layout of hyp.  dsn2_B: d sn2 / d log sn per candidate, the caller's (2 exp(2 hyp_noise)
+ * under constant additive noise, 0 without it); priors are the caller's too.  Candidates are factorised in chunks whose
+ * factor state stays under 1 GiB (vbmc_set_option "gp_lml_chunk" forces a chunk size); the GP the context holds is not
+ * touched.  want_grad = 0: the value alone (dlml_BxP may then be null).  A candidate that is not positive definite or
+ * whose results are not finite gets status_B = 1, lml = -inf and a NaN gradient row; the call still returns VBMC_OK and
+ * the other candidates are what they would be without it.  VBMC_E_UNSUP when a candidate has sn2_div < 1e-6, D > 32 or
+ * one candidate's state exceeds the cap; VBMC_E_ARG on bad shapes.  FP64, fixed summation order: bit-reproducible, and
+ * a candidate's results do not depend on the chunking. */
+int vbmc_gp_lml(vbmc_ctx* ctx, int N, int D, int B, int P, int mean_kind, const double* X_NxD, const double* y_N,
+                const double* sn2_BxN, const double* sn2_div_B, const double* dsn2_B, const double* hyp_BxP, int want_grad,
+                double* lml_B, double* dlml_BxP, int32_t* status_B);
 
 /* ---- a8: vbmc/variational_optimization.py:1238-1606 _gp_log_joint ------- */
 

@@ -22,7 +22,7 @@ E_NOTPD = -8  # vbmc_gp_posterior / vbmc_gp_append: not positive definite
 W_GP_CHANGED = 1  # vbmc_neg_elcbo: the watched GP arrays changed under it (vbmc_set_gp_watch)
 W_NOT_FUSED = 2   # vbmc_adam_run_auto: the one-launch loop does not apply (or gave up): run batches with vbmc_adam_run
 # the timed intervals of Context.last_kernel_ms (csrc/common.h TimingPair; the numbers are ABI)
-T_ENTMC, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC = range(8)
+T_ENTMC, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML = range(9)
 
 
 class VbmcHipError(RuntimeError):
@@ -164,6 +164,11 @@ SIGNATURES = {
     ),
     "vbmc_gp_append": (C.c_int, [_vp, _dp, C.c_double, _dp, _dp]),
     "vbmc_gp_fetch": (C.c_int, [_vp, _dp, _dp]),
+    "vbmc_gp_lml": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp,
+         C.POINTER(C.c_int32)],
+    ),
     "vbmc_gp_log_joint": (
         C.c_int,
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp],

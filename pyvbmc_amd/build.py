@@ -25,6 +25,8 @@ SOURCES = [
     "api_gp.hip",
     "gp_post.hip",
     "api_gp_post.hip",
+    "gp_lml.hip",
+    "api_gp_lml.hip",
     "api_elbo.hip",
     "api_batch.hip",
     "adam.hip",

@@ -144,8 +144,9 @@ struct ElboScratch {
 };
 
 // The timed intervals of vbmc_last_kernel_ms (the numbers are ABI): entmc, glj, pdf, predict, elbo, predict's variance
-// product (timing level 2 only), the GP posterior's factorisation, the MCMC chains of vbmc_is_mcmc
-enum TimingPair { T_ENTMC = 0, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_COUNT };
+// product (timing level 2 only), the GP posterior's factorisation, the MCMC chains of vbmc_is_mcmc, one chunk of
+// vbmc_gp_lml (factorisation and gradient kernels)
+enum TimingPair { T_ENTMC = 0, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML, T_COUNT };
 
 struct vbmc_ctx {
   int device = 0;
@@ -255,6 +256,7 @@ struct vbmc_ctx {
   int opt_arm_late_test = 0;  // test hook: n > 0 = the n-th use of an armed evaluation from now takes the late-go recovery path
   int opt_acq_poll = 1;       // small acquisition batches: points written by the CPU, results polled (api_acq.hip)
   int opt_is_mcmc_threads = 512;  // workgroup size of vbmc_is_mcmc's chains: 256, 512 or 768 (acq_is_mcmc.hip)
+  int opt_gp_lml_chunk = 0;       // vbmc_gp_lml: n > 0 = candidates per chunk (test hook); 0 = the largest under the byte cap
   void (*release_cb)(void*) = nullptr;  // vbmc_set_release_callback
   void* release_cb_user = nullptr;
   int opt_adam_fused = 1;     // the optimiser loop as one launch per batch where its shape applies (adam_fused.hip)
@@ -642,6 +644,28 @@ GpAppendWs gp_post_append_ws(int S, int N);
 // ws: gp_post_append_ws(from.S, from.N), reserved
 int launch_gp_post_append(vbmc_ctx* ctx, const GpState& from, double y_new, const GpAppendWs& ws);
 void gp_post_free(vbmc_ctx* ctx);
+// vbmc_gp_lml's chunk plan, stated once: the candidates factorised side by side.  A candidate's factor state is L, L^-1
+// (N^2 each), the padded copy of L^-1 (ld^2), the inverted diagonal blocks (nb 64^2) and the gradient's tile partials
+// (nb (nb + 1) / 2 tile pairs of D + 2 sums); the chunk is the largest whose state stays under cap_bytes, at most B, or
+// `forced` (> 0) where that is smaller.  0: not even one candidate fits.
+constexpr size_t GP_LML_CAP_BYTES = (size_t)1 << 30;
+inline size_t gp_lml_part_elems(int N, int D) {
+  const size_t nb = ((size_t)N + 63) / 64;
+  return nb * (nb + 1) / 2 * ((size_t)D + 2);
+}
+inline int gp_lml_plan(int N, int D, int B, size_t cap_bytes, int forced) {
+  const size_t nn = (size_t)N * N, ld = (size_t)(((size_t)N + 63) / 64 * 64), nb = ld / 64;
+  const size_t per = sizeof(double) * (2 * nn + ld * ld + nb * 64 * 64 + gp_lml_part_elems(N, D));
+  size_t chunk = cap_bytes / per;
+  if (chunk > (size_t)B) chunk = (size_t)B;
+  if (forced > 0 && (size_t)forced < chunk) chunk = (size_t)forced;
+  return (int)chunk;
+}
+// gp_lml.hip: value and gradient of the log marginal likelihood of ctx->gp's S candidates from the factor state
+// launch_gp_post_build left there.  d_sums [S][2], d_part [S][gp_lml_part_elems], d_mg [S][mean parameters]: workspace;
+// d_lml [S], d_dlml [S][P] (want_grad): results, device memory
+int launch_gp_lml(vbmc_ctx* ctx, int want_grad, const double* d_dsn2, double* d_sums, double* d_part, double* d_mg,
+                  double* d_lml, double* d_dlml);
 // api_gp.hip: the device buffers of a GP state of N points, D dimensions, S samples, P hyper-parameters, kept across GP
 // updates and only grown (capacity n + n / 8 + 64: active sampling makes N creep up by one); with_post: also what a
 // device-built posterior keeps (y, residuals, noise variances, sl)

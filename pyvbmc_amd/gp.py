@@ -15,6 +15,9 @@ names so the hot-path functions accept either it or a real ``gpyreg.GP``:
 * ``update(..., device=True)``, ``append`` and ``device_posterior`` build the same records on the device instead
   (vbmc_gp_posterior / vbmc_gp_append: batched FP64 Cholesky, one-point append) and leave them installed there, so
   the ``upload_gp`` that follows ships nothing.  Opt-in: the default path and its bits are unchanged.
+* ``log_marginal_likelihood`` / ``GP.log_likelihood``: the objective of hyper-parameter fitting and its gradient for a
+  batch of candidates on the device (vbmc_gp_lml), with a NumPy / SciPy host route of the same formulas.  The fitting
+  loop itself (optimiser, slice sampler, priors) stays with the caller.
 """
 import ctypes as C
 import sys
@@ -361,6 +364,117 @@ def fetch_posteriors(gp, ctx=None):
     return posts
 
 
+def _mean_and_grad(kind, hm, X):
+    """m(X) (N) and dm/dtheta (mean parameters, N) of the three mean kinds."""
+    N, D = X.shape
+    if kind == _lib.MEAN_ZERO:
+        return np.zeros(N), np.zeros((0, N))
+    if kind == _lib.MEAN_CONST:
+        return np.full(N, hm[0]), np.ones((1, N))
+    om = np.exp(hm[1 + D : 1 + 2 * D])
+    u = X - hm[1 : 1 + D]
+    m = hm[0] - 0.5 * np.sum((u / om) ** 2, axis=1)
+    return m, np.vstack([np.ones((1, N)), (u / om**2).T, ((u / om) ** 2).T])
+
+
+def _host_lml(X, y, kind, h, sn2, sn2_div, dsn2, grad):
+    """One candidate on the host with vbmc_gp_lml's formulas: ``(lml, dlml or None)``; -inf and a NaN gradient when the
+    covariance does not factorise or a result is not finite.  ``sn2_div < 1e-6`` (the posterior's non-Cholesky branch):
+    the factor of C = K + diag(sn2) itself, sl = 1."""
+    N, D = X.shape
+    P = h.size
+    bad = (-np.inf, np.full(P, np.nan) if grad else None)
+    with np.errstate(all="ignore"):
+        ell = np.exp(h[:D])
+        Xs = X / ell
+        d2 = np.zeros((N, N))
+        for d in range(D):
+            d2 += (Xs[:, d][:, None] - Xs[:, d][None, :]) ** 2
+        K = np.exp(2 * h[D]) * np.exp(-0.5 * d2)
+        sl = sn2_div if sn2_div >= 1e-6 else 1.0
+        A = K / sl + np.diag(sn2 / sl)
+        m, dm = _mean_and_grad(kind, h[D + 2 :], X)
+        r = y - m
+        if not (np.all(np.isfinite(A)) and np.all(np.isfinite(r))):
+            return bad
+        try:
+            U = sla.cholesky(A, lower=False)
+        except (np.linalg.LinAlgError, ValueError):
+            return bad
+        alpha = sla.cho_solve((U, False), r) / sl
+        lml = -0.5 * (r @ alpha) - np.sum(np.log(np.diag(U))) - 0.5 * N * np.log(2 * np.pi * sl)
+        if not np.isfinite(lml):
+            return bad
+        if not grad:
+            return lml, None
+        Ui = sla.solve_triangular(U, np.eye(N), lower=False)
+        W = (Ui @ Ui.T) / sl - np.outer(alpha, alpha)
+        WK = W * K
+        g = np.empty(P)
+        for d in range(D):
+            g[d] = -0.5 * np.sum(WK * (Xs[:, d][:, None] - Xs[:, d][None, :]) ** 2)
+        g[D] = -np.sum(WK)
+        g[D + 1] = -0.5 * dsn2 * np.trace(W)
+        g[D + 2 :] = dm @ alpha
+        if not np.all(np.isfinite(g)):
+            return bad
+    return lml, g
+
+
+def log_marginal_likelihood(gp, hyp, *, grad=False, device=True, ctx=None):
+    """Log marginal likelihood of ``gp``'s training data under each row of ``hyp`` (B, P): ``lml`` (B,), or
+    ``(lml, dlml (B, P))`` with ``grad=True`` -- the objective of hyper-parameter fitting, without priors.
+
+    ``gp`` is read as ``device_posterior`` reads it (``X``, ``y``, ``s2``, ``mean``, ``noise``; the same noise rule).  The
+    derivative with respect to the noise parameter is that of constant additive noise (d sn2 / d log sn =
+    2 exp(2 hyp_noise)) where the GP has it -- a noise object's ``constant_add``; a stand-in without a noise object
+    always has -- and 0 otherwise.
+    ``device=True``: batched on the device (vbmc_gp_lml: the factorisation of ``vbmc_gp_posterior`` in chunks, the
+    gradient's trace on the FP64 matrix cores); the posterior the context holds is untouched.  Rows with
+    ``sn2_div < 1e-6`` and shapes the device does not take (D > 32) are computed on the host, row by row, as
+    ``device=False`` computes every row (NumPy / SciPy, the same formulas).  A row that is not positive definite gives
+    ``-inf`` and a NaN gradient row on both routes; it never raises."""
+    X = _lib.f64(np.atleast_2d(gp.X))
+    y = _lib.f64(np.ravel(gp.y))
+    N, D = X.shape
+    hyp = _lib.f64(np.atleast_2d(hyp))
+    B, P = hyp.shape
+    kind = mean_kind_of(gp)
+    if P != D + 2 + (0, 1, 1 + 2 * D)[kind]:
+        raise ValueError(f"log_marginal_likelihood: hyp has {P} columns, the GP takes {D + 2 + (0, 1, 1 + 2 * D)[kind]}")
+    with np.errstate(all="ignore"):
+        sn2 = _lib.f64(np.stack([_noise_var(gp, h[D + 1 : D + 2]) for h in hyp]))
+        sn2_div = _lib.f64(np.min(sn2, axis=1))
+        noise = getattr(gp, "noise", None)
+        const_add = True if noise is None or not hasattr(noise, "compute") else bool(getattr(noise, "constant_add", False))
+        dsn2 = _lib.f64(2.0 * np.exp(2 * hyp[:, D + 1]) if const_add else np.zeros(B))
+    lml = np.empty(B)
+    dlml = np.empty((B, P)) if grad else None
+    host_rows = np.ones(B, dtype=bool)
+    if device:
+        ctx = (getattr(gp, "ctx", None) or _lib.default_context()) if ctx is None else ctx
+        dev = np.flatnonzero(sn2_div >= 1e-6)
+        if dev.size:
+            h_d, sn2_d, div_d, ds_d = (_lib.f64(a[dev]) for a in (hyp, sn2, sn2_div, dsn2))
+            lml_d = np.empty(dev.size)
+            dl_d = np.empty((dev.size, P)) if grad else None
+            status = np.zeros(dev.size, dtype=np.int32)
+            rc = ctx._lib.vbmc_gp_lml(ctx._h, N, D, dev.size, P, kind, _lib.ptr(X), _lib.ptr(y), _lib.ptr(sn2_d),
+                                      _lib.ptr(div_d), _lib.ptr(ds_d), _lib.ptr(h_d), int(bool(grad)), _lib.ptr(lml_d),
+                                      _lib.ptr(dl_d), status.ctypes.data_as(C.POINTER(C.c_int32)))
+            if rc != _lib.E_UNSUP:
+                ctx.check(rc)
+                lml[dev] = lml_d
+                if grad:
+                    dlml[dev] = dl_d
+                host_rows[dev] = False
+    for b in np.flatnonzero(host_rows):
+        lml[b], g = _host_lml(X, y, kind, hyp[b], sn2[b], sn2_div[b], dsn2[b], grad)
+        if grad:
+            dlml[b] = g
+    return (lml, dlml) if grad else lml
+
+
 class GP:
     def __init__(self, D, covariance, mean, noise):
         if not isinstance(covariance, SquaredExponential):
@@ -469,6 +583,12 @@ class GP:
                 _adopt(self, ctx, dev=True)
                 return
         self.update(X1, y1, None, hyp, device=device, fetch=fetch)
+
+    def log_likelihood(self, hyp=None, grad=False, *, device=True):
+        """``log_marginal_likelihood`` of this GP: ``hyp`` (B, P), default the present records' samples."""
+        if hyp is None:
+            hyp = np.stack([np.ravel(p.hyp) for p in self.posteriors])
+        return log_marginal_likelihood(self, hyp, grad=grad, device=device, ctx=self.ctx if device else None)
 
     def get_hyperparameters(self, as_array=True):
         return np.stack([p.hyp for p in self.posteriors])
