@@ -128,7 +128,9 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on);
  *            (VBMC_E_ARG "no timed launch recorded", never a stale interval).
  *        6 = vbmc_gp_posterior's blocked Cholesky factorisation alone (all its block steps),
  *        7 = vbmc_is_mcmc's launch (all S chains),
- *        8 = vbmc_gp_lml's last chunk: its factorisation and its value / gradient kernels. */
+ *        8 = vbmc_gp_lml's last chunk: its factorisation and its value / gradient kernels,
+ *        9 = vbmc_search_fill's uploads and launches, 10 = vbmc_search_eval's acquisition, noise lookup and mask,
+ *        11 = its sort and gather. */
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out);
 
 /* Host-side wall-clock breakdown (microseconds) of the most recent vbmc_neg_elcbo:
@@ -663,6 +665,57 @@ int vbmc_is_mcmc(vbmc_ctx* ctx, int ln_y_fmu, double u_q, const double* x0_SxD, 
  * only the argmin is wanted.  D <= 32. */
 int vbmc_sq_dist(vbmc_ctx* ctx, int64_t n, int64_t m, int D, const double* a_nxD,
                  const double* b_mxD, double* c_nxm, int64_t* argmin_n);
+
+/* ---- the acquisition search of active_sample ------------- *
+ *
+ * vbmc/active_sample.py:310-349, 647-837: a set of M search points (transformed space) is drawn, scored with the
+ * acquisition function and ranked.  The set stays in the context between the calls below: what goes in are the
+ * bounds and a few D x D factors, what comes back is the ranked set.
+ *
+ * vbmc_search_fill fills the set from n_src sources, in order (M = the sum of their rows; D <= 32, M <= 2^20,
+ * VBMC_E_UNSUP above, before anything is drawn):
+ *   VBMC_SRC_COPY       data = rows x D host points, already in transformed space (the search cache, :716-722)
+ *   VBMC_SRC_TRANSFORM  data = rows x D host points of the original space, put through the slot-0 transformer
+ *                       (the cache rows x_orig, :706); without a transformer (use_xf = 0) they are copied
+ *   VBMC_SRC_MIXTURE    rows balanced draws of the ctx mixture with `df`, as vbmc_mixture_sample_t draws them with
+ *                       key `seed` (unshuffled; :728-730, :829)
+ *   VBMC_SRC_AFFINE     data = [mean D | A D x D]: row r = z_r A + mean, z_r the standard normals of Philox stream 7
+ *                       (csrc/sample.hip) at counter (r, pair) under key `seed` (:736-738, :782-784; the caller passes
+ *                       as A the factor np.random.multivariate_normal forms of the covariance, sqrt(s)[:, None] * v of
+ *                       its SVD -- pyvbmc_amd/active_search.py mvn_factor, which sets singular values below
+ *                       s.max() * D * eps to zero first)
+ *   VBMC_SRC_BOX        data = [lb D | ub D]: row r = z_r o (ub - lb) + lb, the same normals (:806-809)
+ * Every row is then clamped to [lb_search_D, ub_search_D] (:836; both NULL: no clamp) and, when integer_bits is not
+ * 0 (bit d = dimension d is an integer variable), rounded as AbstractAcqFcn._real2int does (abstract_acq_fcn.py:
+ * 149-193): inverse transform, rint (half to even), forward transform, the integer columns replaced.  use_xf: 1 = the
+ * slot-0 transformer applies (it must be set for D), 0 = the identity.  X_out_MxD (nullable) receives the set.
+ * vbmc_search_put is the fill of one VBMC_SRC_COPY source without a clamp: host-drawn points become the set.
+ *
+ * vbmc_search_eval scores and ranks the set.  kind: VBMC_ACQ_STD .. VBMC_ACQ_NOISY as vbmc_acq_eval, or VBMC_ACQ_IS,
+ * the importance-sampled acquisition of vbmc_acq_is_eval on the resident importance state (u = norm.ppf(quantile); the
+ * variance regularisation and the clamp of abstract_acq_fcn.py:110-131 applied here too).  VBMC_ACQ_NOISY and
+ * VBMC_ACQ_IS take the observation noise of every point from the nearest training input
+ * (_estimate_observation_noise, :224-256): n_noise rows X_rescaled_NxD, sn2_new_N and length_scale_D, the set divided
+ * by the length scale on the device (the lookup runs over the whole set in one pass: 2 M ceil(n_noise / 64) <= 2^28,
+ * VBMC_E_UNSUP above).  Then +inf where the inverse-transformed point (use_xf as above) lies outside
+ * [lb_eps_orig_D, ub_eps_orig_D] (:133-139), and the stable ascending order of (value, row), NaN last -- what
+ * np.argsort(kind="stable") gives.  Outputs, each nullable: acq_M in set order, order_M, the set in that order. */
+enum { VBMC_SRC_COPY = 0, VBMC_SRC_TRANSFORM = 1, VBMC_SRC_MIXTURE = 2, VBMC_SRC_AFFINE = 3, VBMC_SRC_BOX = 4 };
+enum { VBMC_ACQ_IS = 4 };
+typedef struct vbmc_search_source {
+  int kind;
+  int64_t rows;
+  const double* data;
+  double df;     /* VBMC_SRC_MIXTURE: degrees of freedom (+inf or 0: Gaussian) */
+  uint64_t seed; /* key of the source's draws */
+} vbmc_search_source;
+int vbmc_search_fill(vbmc_ctx* ctx, int D, int n_src, const vbmc_search_source* src, const double* lb_search_D,
+                     const double* ub_search_D, uint32_t integer_bits, int use_xf, double* X_out_MxD);
+int vbmc_search_put(vbmc_ctx* ctx, int64_t M, int D, const double* X_MxD, uint32_t integer_bits, int use_xf);
+int vbmc_search_eval(vbmc_ctx* ctx, int kind, double y_max, double tol_gp_var, double u, int64_t n_noise,
+                     const double* X_rescaled_NxD, const double* sn2_new_N, const double* length_scale_D, int use_xf,
+                     const double* lb_eps_orig_D, const double* ub_eps_orig_D, double* acq_M, int64_t* order_M,
+                     double* X_sorted_MxD);
 
 /* ---- sampling and its Monte-Carlo consumers -------------- */
 

@@ -23,6 +23,7 @@ W_GP_CHANGED = 1  # vbmc_neg_elcbo: the watched GP arrays changed under it (vbmc
 W_NOT_FUSED = 2   # vbmc_adam_run_auto: the one-launch loop does not apply (or gave up): run batches with vbmc_adam_run
 # the timed intervals of Context.last_kernel_ms (csrc/common.h TimingPair; the numbers are ABI)
 T_ENTMC, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML = range(9)
+T_SEARCH_FILL, T_SEARCH_EVAL, T_SEARCH_SORT = 9, 10, 11
 
 
 class VbmcHipError(RuntimeError):
@@ -96,6 +97,22 @@ class MtvSide(C.Structure):
         ("seed", C.c_uint64),
         ("lb_D", _dp),
         ("ub_D", _dp),
+    ]
+
+
+SRC_COPY, SRC_TRANSFORM, SRC_MIXTURE, SRC_AFFINE, SRC_BOX = range(5)  # vbmc_search_source.kind
+ACQ_IS = 4  # vbmc_search_eval: the importance-sampled acquisition (kinds 0-3 as vbmc_acq_eval)
+
+
+class SearchSource(C.Structure):
+    """vbmc_search_source: one source of the search set's rows (vbmc_search_fill)."""
+
+    _fields_ = [
+        ("kind", C.c_int),
+        ("rows", C.c_int64),
+        ("data", _dp),
+        ("df", C.c_double),
+        ("seed", C.c_uint64),
     ]
 
 
@@ -203,6 +220,10 @@ SIGNATURES = {
     "vbmc_is_mcmc": (C.c_int, [_vp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_uint64, _dp, _dp,
                                _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "vbmc_sq_dist": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "vbmc_search_fill": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(SearchSource), _dp, _dp, C.c_uint32, C.c_int, _dp]),
+    "vbmc_search_put": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_uint32, C.c_int]),
+    "vbmc_search_eval": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, _dp, _dp, _dp, C.c_int, _dp,
+                                   _dp, _dp, C.POINTER(C.c_int64), _dp]),
     "vbmc_mixture_sample": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, C.POINTER(C.c_int32)]),
     "vbmc_mixture_sample_t": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, C.c_double, _dp, C.POINTER(C.c_int32)]),
     "vbmc_kl_div_mc": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, _dp, _dp, _dp, _dp]),

@@ -35,6 +35,8 @@ SOURCES = [
     "api_acq_is.hip",
     "acq_is_prep.hip",
     "acq_is_mcmc.hip",
+    "search.hip",
+    "api_search.hip",
     "sample.hip",
     "transform.hip",
     "kde.hip",

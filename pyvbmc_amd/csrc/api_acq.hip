@@ -157,6 +157,19 @@ __global__ __launch_bounds__(256) void acq_tail_small_kernel(AcqTail a) {
 
 }  // namespace
 
+int launch_acq_closed(vbmc_ctx* ctx, const PredictPlan& p, int64_t m, const double* d_xs, const double* d_sn2, int kind,
+                      double y_max, double tol_gp_var, double* d_dens, double* d_res) {
+  int rc = launch_gp_predict_all(ctx, m, d_xs, p.Ks, p.part, 0, p.fmu, p.fs2, p.mb);
+  if (rc) return rc;
+  rc = launch_mixture_pdf(ctx, m, d_xs, kind == VBMC_ACQ_LOG, 0, INFINITY, d_dens, nullptr);
+  if (rc) return rc;
+  hipLaunchKernelGGL(acq_combine_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream,
+                     (const double*)p.fmu, (const double*)p.fs2, (const double*)d_dens, d_sn2, ctx->gp.S, m, p.mb, kind,
+                     y_max, tol_gp_var, d_res, d_res + p.mb, d_res + 2 * p.mb);
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
 extern "C" int vbmc_acq_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, int kind, double y_max,
                              double tol_gp_var, const double* sn2_M, double* acq_M, double* f_bar_M,
                              double* var_tot_M) {
@@ -182,7 +195,7 @@ extern "C" int vbmc_acq_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, int
   const auto p_dens = p.sc.add((size_t)mb), p_sn2 = p.sc.add((size_t)mb), p_acq = p.sc.add(3 * (size_t)mb);
   int rc = predict_reserve(ctx, p, 3);
   if (rc) return rc;
-  double *d_xs = p.xs, *d_Ks = p.Ks, *d_part = p.part, *d_fmu = p.fmu, *d_fs2 = p.fs2;
+  double *d_xs = p.xs, *d_Ks = p.Ks, *d_part = p.part;
   double *d_dens = p.sc.ptr(p_dens), *d_sn2 = p.sc.ptr(p_sn2), *d_acq = p.sc.ptr(p_acq);
   const double* const res_src[3] = {d_acq, d_acq + mb, d_acq + 2 * mb};
   double* const res_dst[3] = {acq_M, f_bar_M, var_tot_M};
@@ -263,15 +276,7 @@ extern "C" int vbmc_acq_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, int
                                 ctx->stream));
     if (kind == VBMC_ACQ_NOISY)
       HIP_TRY(ctx, hipMemcpyAsync(d_sn2, sn2_M + o, sizeof(double) * m, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_gp_predict_all(ctx, m, d_xs, d_Ks, d_part, 0, d_fmu, d_fs2, mb);
-    if (rc) return rc;
-    rc = launch_mixture_pdf(ctx, m, d_xs, kind == VBMC_ACQ_LOG, 0, INFINITY, d_dens, nullptr);
-    if (rc) return rc;
-    hipLaunchKernelGGL(acq_combine_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const double*)d_fmu, (const double*)d_fs2, (const double*)d_dens,
-                       (const double*)d_sn2, S, m, mb, kind, y_max, tol_gp_var, d_acq, d_acq + mb,
-                       d_acq + 2 * mb);
-    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = launch_acq_closed(ctx, p, m, d_xs, d_sn2, kind, y_max, tol_gp_var, d_dens, d_acq))) return rc;
     if ((rc = fetch_vectors(ctx, 3, res_src, res_dst, (size_t)m, (size_t)mb, (size_t)o))) return rc;
   }
   return VBMC_OK;

@@ -257,19 +257,54 @@ extern "C" int vbmc_acq_is_build(vbmc_ctx* ctx, int64_t Na, const double* Xa, in
   return VBMC_OK;
 }
 
+int acq_is_need(vbmc_ctx* ctx, const char* who, int64_t* Na) {
+  const IsState* st = (const IsState*)ctx->acq_is;
+  const GpState& g = ctx->gp;
+  if (!st || !st->d || st->S != g.S || st->N != g.N || st->D != g.D)
+    return vbmc_fail(ctx, VBMC_E_ARG, "%s: importance state not set for this GP (vbmc_acq_is_set)", who);
+  *Na = st->Na;
+  return 0;
+}
+
+int launch_acq_is(vbmc_ctx* ctx, const PredictPlan& p, int64_t m, const double* d_xs, const double* d_sn2, double u,
+                  double* d_Kx, double* d_T, double* d_as, double* d_res) {
+  const IsState* st = (const IsState*)ctx->acq_is;
+  const GpState& g = ctx->gp;
+  const int N = g.N, D = g.D, S = g.S;
+  const int64_t Na = st->Na, mb = p.mb;
+  int rc = launch_gp_predict_all(ctx, m, d_xs, p.Ks, p.part, 0, p.fmu, p.fs2, mb);  // f_s2 at Xs, every sample
+  if (rc) return rc;
+  for (int s = 0; s < S; ++s) {
+    const double* hyp = g.d_hyp + (size_t)s * g.P;
+    hipLaunchKernelGGL(se_cross_kernel, dim3((unsigned)((m * N + 255) / 256)), dim3(256), 0, ctx->stream, d_xs, m,
+                       (const double*)g.d_X, N, D, hyp, d_Kx);
+    rc = launch_gp_panel_product(ctx, d_Kx, st->d + st->o_C + (size_t)s * N * Na, d_T, m, N, (int)Na);
+    if (rc) return rc;
+    const double* Xa = st->d + (st->per_sample ? (size_t)s * Na * D : 0);
+    hipLaunchKernelGGL(is_reduce_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream, d_xs, m, D, Xa, Na, hyp,
+                       (const double*)d_T, (const double*)(p.fs2 + (size_t)s * mb), d_sn2,
+                       (const double*)(st->d + st->o_f + (size_t)s * Na),
+                       st->has_lnw ? (const double*)(st->d + st->o_w + (size_t)s * Na) : (const double*)nullptr,
+                       g.L_chol[s] ? 1 : 0, u, d_as + (size_t)s * mb);
+  }
+  hipLaunchKernelGGL(is_combine_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)d_as, S,
+                     m, mb, d_res, (const double*)p.fmu, (const double*)p.fs2, d_res + mb);
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
 extern "C" int vbmc_acq_is_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, const double* sn2_M,
                                 double u, double* acq_M, double* var_tot_M) {
   if (!ctx || (M > 0 && (!xs_MxD || !sn2_M || !acq_M))) return VBMC_E_ARG;
   NEED_DEVICE(ctx);
   if (!ctx->gp.set) return vbmc_fail(ctx, VBMC_E_ARG, "acq_is_eval: GP not set");
-  IsState* st = (IsState*)ctx->acq_is;
-  const GpState& g = ctx->gp;
-  if (!st || !st->d || st->S != g.S || st->N != g.N || st->D != g.D)
-    return vbmc_fail(ctx, VBMC_E_ARG, "acq_is_eval: importance state not set for this GP (vbmc_acq_is_set)");
+  int64_t Na = 0;
+  int rc = acq_is_need(ctx, "acq_is_eval", &Na);
+  if (rc) return rc;
   if (M == 0) return VBMC_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const GpState& g = ctx->gp;
   const int N = g.N, D = g.D, S = g.S;
-  const int64_t Na = st->Na;
   if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "acq_is_eval: D=%d > 32 not supported", D);
   // its own pieces: sn2 | Kx (mb x N) | T (mb x Na) | acq_s [S] | acq, var_tot (one piece, mb apart)
   PredictPlan p;
@@ -277,9 +312,8 @@ extern "C" int vbmc_acq_is_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, 
   const int64_t mb = p.mb;
   const auto p_sn2 = p.sc.add((size_t)mb), p_Kx = p.sc.add((size_t)mb * N), p_T = p.sc.add((size_t)mb * Na);
   const auto p_as = p.sc.add((size_t)S * mb), p_acq = p.sc.add(2 * (size_t)mb);
-  int rc = predict_reserve(ctx, p, 2);
-  if (rc) return rc;
-  double *d_xs = p.xs, *d_Ks = p.Ks, *d_part = p.part, *d_fmu = p.fmu, *d_fs2 = p.fs2;
+  if ((rc = predict_reserve(ctx, p, 2))) return rc;
+  double* d_xs = p.xs;
   double *d_sn2 = p.sc.ptr(p_sn2), *d_Kx = p.sc.ptr(p_Kx), *d_T = p.sc.ptr(p_T), *d_as = p.sc.ptr(p_as), *d_acq = p.sc.ptr(p_acq);
   const double* const res_src[2] = {d_acq, d_acq + mb};
   double* const res_dst[2] = {acq_M, var_tot_M};
@@ -287,26 +321,7 @@ extern "C" int vbmc_acq_is_eval(vbmc_ctx* ctx, int64_t M, const double* xs_MxD, 
     const int64_t m = (M - o) < mb ? (M - o) : mb;
     HIP_TRY(ctx, hipMemcpyAsync(d_xs, xs_MxD + o * D, sizeof(double) * m * D, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_sn2, sn2_M + o, sizeof(double) * m, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_gp_predict_all(ctx, m, d_xs, d_Ks, d_part, 0, d_fmu, d_fs2, mb);  // f_s2 at Xs, every sample
-    if (rc) return rc;
-    for (int s = 0; s < S; ++s) {
-      const double* hyp = g.d_hyp + (size_t)s * g.P;
-      hipLaunchKernelGGL(se_cross_kernel, dim3((unsigned)((m * N + 255) / 256)), dim3(256), 0, ctx->stream,
-                         (const double*)d_xs, m, (const double*)g.d_X, N, D, hyp, d_Kx);
-      rc = launch_gp_panel_product(ctx, d_Kx, st->d + st->o_C + (size_t)s * N * Na, d_T, m, N, (int)Na);
-      if (rc) return rc;
-      const double* Xa = st->d + (st->per_sample ? (size_t)s * Na * D : 0);
-      hipLaunchKernelGGL(is_reduce_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream,
-                         (const double*)d_xs, m, D, Xa, Na, hyp, (const double*)d_T,
-                         (const double*)(d_fs2 + (size_t)s * mb), (const double*)d_sn2,
-                         (const double*)(st->d + st->o_f + (size_t)s * Na),
-                         st->has_lnw ? (const double*)(st->d + st->o_w + (size_t)s * Na) : (const double*)nullptr,
-                         g.L_chol[s] ? 1 : 0, u, d_as + (size_t)s * mb);
-    }
-    hipLaunchKernelGGL(is_combine_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const double*)d_as, S, m, mb, d_acq, (const double*)d_fmu, (const double*)d_fs2,
-                       d_acq + mb);
-    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = launch_acq_is(ctx, p, m, d_xs, d_sn2, u, d_Kx, d_T, d_as, d_acq))) return rc;
     if ((rc = fetch_vectors(ctx, 2, res_src, res_dst, (size_t)m, (size_t)mb, (size_t)o))) return rc;
   }
   return VBMC_OK;

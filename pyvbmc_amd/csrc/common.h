@@ -145,8 +145,10 @@ struct ElboScratch {
 
 // The timed intervals of vbmc_last_kernel_ms (the numbers are ABI): entmc, glj, pdf, predict, elbo, predict's variance
 // product (timing level 2 only), the GP posterior's factorisation, the MCMC chains of vbmc_is_mcmc, one chunk of
-// vbmc_gp_lml (factorisation and gradient kernels)
-enum TimingPair { T_ENTMC = 0, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML, T_COUNT };
+// vbmc_gp_lml (factorisation and gradient kernels), the three phases of the acquisition search (vbmc_search_fill's
+// launches; vbmc_search_eval's acquisition and mask; its sort and gather)
+enum TimingPair { T_ENTMC = 0, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML, T_SEARCH_FILL,
+                  T_SEARCH_EVAL, T_SEARCH_SORT, T_COUNT };
 
 struct vbmc_ctx {
   int device = 0;
@@ -303,6 +305,7 @@ struct vbmc_ctx {
   int randn_last_reused = 0;  // the last device pass found its window in the pass before (device_randn.hip)
   int opt_randn_dev = 1;      // vbmc_set_eps_numpy: the reference's stream generated on the device (0: on the host cores + PCIe)
   void* xf = nullptr;         // parameter-transformer descriptors, two slots (transform.hip)
+  void* search = nullptr;     // the resident search set of the acquisition search (api_search.hip)
 };
 // the device's CU count, which sizes one round of workgroups (256 where the runtime reports none)
 inline int ctx_cus(const vbmc_ctx* ctx) { return ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256; }
@@ -311,6 +314,7 @@ void adam_free(vbmc_ctx* ctx);
 void acq_is_free(vbmc_ctx* ctx);
 void randn_dev_free(vbmc_ctx* ctx);
 void xf_free(vbmc_ctx* ctx);  // transform.hip
+void search_free(vbmc_ctx* ctx);  // api_search.hip
 // device_randn.hip: the next n values of NumPy's legacy randn stream into d_out (device memory), state advanced as
 // vbmc_mt19937_randn does; VBMC_W_NOT_FUSED = not this path's size (the caller uses the host generator)
 int randn_device(vbmc_ctx* ctx, uint32_t* key, int* pos, int* has_gauss, double* gauss, double* d_out, int64_t n);
@@ -721,6 +725,48 @@ int launch_gp_panel_product(vbmc_ctx* ctx, const double* d_A, const double* d_B,
                             bool upper_b = false);
 int launch_gp_predict_all(vbmc_ctx* ctx, int64_t M, const double* d_xs, double* d_Ks, double* d_part,
                           int add_noise, double* d_fmu, double* d_fs2, int64_t ld);
+// One batch of m device points (d_xs, reserved plan p) through the acquisition, no copy in or out: what vbmc_acq_eval
+// and vbmc_acq_is_eval run per batch, and vbmc_search_eval on the resident search set.
+// api_acq.hip, the closed forms: d_dens (mb) workspace, d_sn2 (m; VBMC_ACQ_NOISY only), d_res = acq | f_bar | var_tot, mb apart
+int launch_acq_closed(vbmc_ctx* ctx, const PredictPlan& p, int64_t m, const double* d_xs, const double* d_sn2, int kind,
+                      double y_max, double tol_gp_var, double* d_dens, double* d_res);
+// api_acq_is.hip, the importance-sampled kinds: the resident importance state checked against the context's GP (`who`
+// prefixes the message), its number of importance points, and the batch -- d_Kx (mb x N), d_T (mb x Na), d_as [S][mb]
+// workspace, d_res = acq | var_tot, mb apart
+int acq_is_need(vbmc_ctx* ctx, const char* who, int64_t* Na);
+int launch_acq_is(vbmc_ctx* ctx, const PredictPlan& p, int64_t m, const double* d_xs, const double* d_sn2, double u,
+                  double* d_Kx, double* d_T, double* d_as, double* d_res);
+// search.hip: the kernels of the acquisition search (api_search.hip), all on ctx->stream
+struct XfView;
+struct SearchSrcDev {  // one source of the fill table as the generator kernel reads it
+  int kind, pad;
+  long long begin, count;  // rows [begin, begin + count) of the set
+  unsigned long long seed;
+  long long par;           // offset of its parameters in the table's block of doubles
+};
+// rows of the affine-Gaussian and box-normal sources drawn, every row clamped to [d_lb, d_ub] (null: no clamp) and its
+// integer columns (bit d of int_bits) rounded in original space (t null: the identity transformer)
+int launch_search_fill(vbmc_ctx* ctx, double* d_X, int64_t M, int D, const SearchSrcDev* d_src, int n_src, const double* d_par,
+                       const double* d_lb, const double* d_ub, uint32_t int_bits, const XfView* t);
+// acq[m] = +inf where the point (inverse-transformed, t null: as it is) lies outside [d_lb, d_ub]
+int launch_search_mask(vbmc_ctx* ctx, const double* d_X, int64_t M, int D, const XfView* t, const double* d_lb,
+                       const double* d_ub, double* d_acq);
+// the noise lookup's operands: d_xsc = X / ell per column; the column sums of a set in d_part (search_sum_blocks x D
+// doubles) and the centre of AbstractAcqFcn._sq_dist from the two sets' sums
+constexpr int search_sum_blocks = 64;
+int launch_search_scale(vbmc_ctx* ctx, const double* d_X, int64_t M, int D, const double* d_ell, double* d_xsc);
+int launch_search_colsum(vbmc_ctx* ctx, const double* d_x, int64_t n, int D, double* d_part);
+int launch_search_centre(vbmc_ctx* ctx, const double* d_part_a, int64_t n, const double* d_part_b, int64_t m, int D,
+                         double* d_cen);
+int launch_search_take(vbmc_ctx* ctx, const double* d_table, int64_t n_table, const int64_t* d_pos, int64_t M, double* d_out);
+// the importance kinds' tail (abstract_acq_fcn.py:110-131): variance regularisation of a log-valued acquisition, clamp
+int launch_search_is_finish(vbmc_ctx* ctx, int64_t M, double tol_gp_var, const double* d_var_tot, double* d_acq);
+// stable ascending order of acq[0 .. M) (NaN last): d_keys / d_idx hold search_sort_len(M) pairs; d_order[M] (int64) and
+// d_Xs (M x D, the rows of d_X in that order) are written
+int64_t search_sort_len(int64_t M);
+int launch_search_sort(vbmc_ctx* ctx, const double* d_acq, int64_t M, uint64_t* d_keys, uint32_t* d_idx);
+int launch_search_gather(vbmc_ctx* ctx, const double* d_X, const uint32_t* d_idx, int64_t M, int D, int64_t* d_order,
+                         double* d_Xs);
 // acq_is_mcmc.hip: the S slice-sampling chains of active_importance_sampling's step 2, one workgroup each, on ctx->stream
 // (all pointers device memory; d_invalid [S] zeroed by the caller), and the dynamic LDS a workgroup of `threads` needs
 size_t is_mcmc_lds_bytes(int N, int threads);

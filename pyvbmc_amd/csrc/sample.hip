@@ -15,6 +15,8 @@
 //                                      training point, b = 1 + p the uniforms of dimensions 2 p, 2 p + 1
 //     c = (i_lo, i_hi, s,    6)        draw i of MCMC chain s of active_importance_sampling's step 2 (acq_is_mcmc.hip): words
 //                                      0, 1 as one 53-bit uniform, i in the order the chain consumes its draws
+//     c = (r_lo, r_hi, pair, 7)        normals of dimensions 2 pair, 2 pair + 1 of row r of an affine-Gaussian or box-normal
+//                                      source of the acquisition search (search.hip), under the source's own key
 // oracle/sample_ref.py restates both.  Component choice: inverse CDF of the weights
 // (np.random.choice(p=w), :316-319); with balance_flag the first sum_k floor(w_k N) samples
 // are split exactly according to the weights and the remaining ones are drawn from the

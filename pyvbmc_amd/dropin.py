@@ -32,7 +32,10 @@ module.  Nothing here imports the reference: ``vo`` is passed in (or imported on
 kernels do not cover; ``unpatch_active_sampling(mod)`` puts the reference's function back.  The reference calls it
 without the mirror's keyword-only extras, so under the drop-in they are chosen by the environment: ``VBMC_HIP_RNG=philox``
 (the proposals drawn on the device) and ``VBMC_HIP_AIS_SAMPLER=device`` (the MCMC chains of step 2 as one launch, on the
-mirror's own slice sampler and stream).
+mirror's own slice sampler and stream).  ``patch_active_sampling(mod, search=True)`` also rebinds ``_get_search_points``
+(active_sample.py:647-837) to ``pyvbmc_amd.active_search.get_search_points`` -- with ``VBMC_HIP_RNG=philox`` the search
+points are then drawn on the device -- again with the reference's function behind it; the reference's ``active_sample``
+keeps its own evaluate / argsort lines (:334-349): only callers of ``pyvbmc_amd.search`` get the fused stage.
 """
 import numpy as np
 
@@ -41,12 +44,13 @@ from . import entropy as _entropy
 from . import minimize_adam as _adam
 from . import variational_optimization as _avo
 from .active_importance_sampling import active_importance_sampling as _ais_mirror
+from .active_search import get_search_points as _gsp_mirror
 
 _SAVED = "_pyvbmc_amd_saved"
 _LEAVES = ("entmc_vbmc", "entlb_vbmc", "_gp_log_joint", "_neg_elcbo")
 
 
-_MIRROR_ONLY_KW = ("rng", "seed", "eps_half", "ctx", "rows", "return_raw", "sampler", "products")  # keyword-only extras of the mirrors
+_MIRROR_ONLY_KW = ("rng", "seed", "eps_half", "ctx", "rows", "return_raw", "sampler", "products", "device")  # keyword-only extras of the mirrors
 
 
 def _with_reference_fallback(fast, ref):
@@ -231,12 +235,14 @@ def unpatch(vo):
 
 
 _SAVED_AIS = "_pyvbmc_amd_saved_ais"
+_SAVED_GSP = "_pyvbmc_amd_saved_gsp"
 
 
-def patch_active_sampling(mod=None):
+def patch_active_sampling(mod=None, search=False):
     """Rebind ``active_importance_sampling`` on ``mod`` (default: ``pyvbmc.vbmc.active_sample``, which binds the name by
     value, active_sample.py:15) to the device mirror, with the reference's function behind it for
-    ``_lib.UnsupportedShape``.  Idempotent; returns ``mod``."""
+    ``_lib.UnsupportedShape``; with ``search`` also ``_get_search_points`` (:647-837), in the same way.  Idempotent;
+    returns ``mod``."""
     if mod is None:
         import importlib
 
@@ -247,17 +253,22 @@ def patch_active_sampling(mod=None):
     setattr(mod, _SAVED_AIS, ref)
     fast = _ais_mirror
     mod.active_importance_sampling = _with_reference_fallback(fast, ref) if callable(ref) else fast
+    if search:
+        ref = getattr(mod, "_get_search_points", None)
+        setattr(mod, _SAVED_GSP, ref)
+        mod._get_search_points = _with_reference_fallback(_gsp_mirror, ref) if callable(ref) else _gsp_mirror
     return mod
 
 
 def unpatch_active_sampling(mod):
     """Put back what ``patch_active_sampling`` replaced."""
-    if not hasattr(mod, _SAVED_AIS):
-        return mod
-    ref = getattr(mod, _SAVED_AIS)
-    if ref is None:
-        delattr(mod, "active_importance_sampling")
-    else:
-        mod.active_importance_sampling = ref
-    delattr(mod, _SAVED_AIS)
+    for saved, name in ((_SAVED_AIS, "active_importance_sampling"), (_SAVED_GSP, "_get_search_points")):
+        if not hasattr(mod, saved):
+            continue
+        ref = getattr(mod, saved)
+        if ref is None:
+            delattr(mod, name)
+        else:
+            setattr(mod, name, ref)
+        delattr(mod, saved)
     return mod
