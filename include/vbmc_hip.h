@@ -130,7 +130,8 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on);
  *        7 = vbmc_is_mcmc's launch (all S chains),
  *        8 = vbmc_gp_lml's last chunk: its factorisation and its value / gradient kernels,
  *        9 = vbmc_search_fill's uploads and launches, 10 = vbmc_search_eval's acquisition, noise lookup and mask,
- *        11 = its sort and gather. */
+ *        11 = its sort and gather,
+ *        12 = vbmc_gp_hyp_sample: all the rounds of the last call (a call that launched nothing leaves no record). */
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out);
 
 /* Host-side wall-clock breakdown (microseconds) of the most recent vbmc_neg_elcbo:
@@ -441,6 +442,37 @@ int vbmc_gp_fetch(vbmc_ctx* ctx, double* alpha_SxN, double* L_SxNxN);
 int vbmc_gp_lml(vbmc_ctx* ctx, int N, int D, int B, int P, int mean_kind, const double* X_NxD, const double* y_N,
                 const double* sn2_BxN, const double* sn2_div_B, const double* dsn2_B, const double* hyp_BxP, int want_grad,
                 double* lml_B, double* dlml_BxP, int32_t* status_B);
+
+/* GP hyper-parameter sampling: C slice-sampling chains over f(h) = lml(h) + log p(h), advanced in lockstep so that every
+ * evaluation round is one batch of C candidates for vbmc_gp_lml's kernels (csrc/gp_hyp.hip; gpyreg's sampler, priors and
+ * stream are not part of the reference tree -- these are this library's own, stated in NumPy by tests/slice_host.py and
+ * pyvbmc_amd/gp.py).
+ *   lml: what vbmc_gp_lml returns for the row h under sn2_n = exp(2 h[D+1]) + s2_n (s2_N nullable: no user-provided
+ *   noise) and sn2_div = min_n sn2_n, from the same kernels; the exponential is taken on the device.  A candidate that
+ *   does not factorise or whose value is not finite has f = -inf: it lies outside every slice and is never an error.
+ *   log p(h) = sum_p t_p (p ascending); t_p = 0 where prior_sigma_P[p] is NaN, else with z = (h_p - mu_p) / sigma_p
+ *   t_p = -1/2 log(2 pi) - log sigma - 1/2 z^2 where prior_df_P[p] is +inf, and the Student-t density's
+ *   lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(pi nu) - log sigma - (nu+1)/2 log(1 + z^2/nu) otherwise.
+ * Sampler: Neal's coordinate-wise slice sampler as tests/slice_host.py states it (level, then interval; stepping out at
+ * most 32 evaluations a side, at most 64 shrink proposals; x0 clipped into [lb, ub]; burn_in + n thin sweeps, a sample
+ * kept every thin-th sweep after burn_in).  Draw i of chain c is the 53-bit uniform of Philox block (i_lo, i_hi, c, 6)
+ * under `seed`.  A round is one advance launch (workgroup = chain: the chain's state machine consumes the value of the
+ * round before and writes its next candidate into the factorisation's inputs), then the factorisation and the value
+ * kernels on the staged state; the GP the context holds is not touched.  Chains beyond one chunk (vbmc_gp_lml's plan,
+ * vbmc_set_option "gp_lml_chunk") are processed chunk by chunk inside a round; the host reads back one count of
+ * unfinished chains every vbmc_set_option "gp_hyp_rounds" rounds (default 4; a test hook).  X, y, s2 go up once.
+ * Outputs: hyp_CxnxP the kept samples, logpost_Cxn their f, logprior_Cxn their log p, stats_Cx4 = [evaluations, draws,
+ * step-out caps hit, shrink caps hit] per chain; invalid_C[c] = 1 when f(x0[c]) is not finite -- that chain's outputs
+ * are zeros and the others are what they would be without it.  A chain's outputs depend on (data, x0[c], widths, bounds,
+ * priors, n, thin, burn_in, seed, c) alone: not on C, the chunking or the rounds per read.
+ * VBMC_E_UNSUP, before any launch: D > 32, one candidate's factor state exceeds the cap, or
+ * exp(2 lb[D+1]) + min s2 < 1e-6 (the non-Cholesky branch stays on the host).  VBMC_E_ARG: bad shapes, bounds that are
+ * not finite or lb > ub, widths <= 0, a prior with sigma <= 0 or df <= 0, n < 1, thin < 1, burn_in < 0. */
+int vbmc_gp_hyp_sample(vbmc_ctx* ctx, int N, int D, int P, int mean_kind, const double* X_NxD, const double* y_N,
+                       const double* s2_N, int C, const double* x0_CxP, const double* widths_P, const double* lb_P,
+                       const double* ub_P, const double* prior_mu_P, const double* prior_sigma_P, const double* prior_df_P,
+                       int n, int thin, int burn_in, uint64_t seed, double* hyp_CxnxP, double* logpost_Cxn,
+                       double* logprior_Cxn, int64_t* stats_Cx4, int32_t* invalid_C);
 
 /* ---- a8: vbmc/variational_optimization.py:1238-1606 _gp_log_joint ------- */
 

@@ -24,6 +24,7 @@ W_NOT_FUSED = 2   # vbmc_adam_run_auto: the one-launch loop does not apply (or g
 # the timed intervals of Context.last_kernel_ms (csrc/common.h TimingPair; the numbers are ABI)
 T_ENTMC, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML = range(9)
 T_SEARCH_FILL, T_SEARCH_EVAL, T_SEARCH_SORT = 9, 10, 11
+T_GP_HYP = 12
 
 
 class VbmcHipError(RuntimeError):
@@ -185,6 +186,11 @@ SIGNATURES = {
         C.c_int,
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp,
          C.POINTER(C.c_int32)],
+    ),
+    "vbmc_gp_hyp_sample": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
+         C.c_int, C.c_uint64, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
     ),
     "vbmc_gp_log_joint": (
         C.c_int,

@@ -27,6 +27,8 @@ SOURCES = [
     "api_gp_post.hip",
     "gp_lml.hip",
     "api_gp_lml.hip",
+    "gp_hyp.hip",
+    "api_gp_hyp.hip",
     "api_elbo.hip",
     "api_batch.hip",
     "adam.hip",

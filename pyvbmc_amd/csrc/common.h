@@ -146,9 +146,9 @@ struct ElboScratch {
 // The timed intervals of vbmc_last_kernel_ms (the numbers are ABI): entmc, glj, pdf, predict, elbo, predict's variance
 // product (timing level 2 only), the GP posterior's factorisation, the MCMC chains of vbmc_is_mcmc, one chunk of
 // vbmc_gp_lml (factorisation and gradient kernels), the three phases of the acquisition search (vbmc_search_fill's
-// launches; vbmc_search_eval's acquisition and mask; its sort and gather)
+// launches; vbmc_search_eval's acquisition and mask; its sort and gather), all the rounds of one vbmc_gp_hyp_sample
 enum TimingPair { T_ENTMC = 0, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML, T_SEARCH_FILL,
-                  T_SEARCH_EVAL, T_SEARCH_SORT, T_COUNT };
+                  T_SEARCH_EVAL, T_SEARCH_SORT, T_GP_HYP, T_COUNT };
 
 struct vbmc_ctx {
   int device = 0;
@@ -259,6 +259,7 @@ struct vbmc_ctx {
   int opt_acq_poll = 1;       // small acquisition batches: points written by the CPU, results polled (api_acq.hip)
   int opt_is_mcmc_threads = 512;  // workgroup size of vbmc_is_mcmc's chains: 256, 512 or 768 (acq_is_mcmc.hip)
   int opt_gp_lml_chunk = 0;       // vbmc_gp_lml: n > 0 = candidates per chunk (test hook); 0 = the largest under the byte cap
+  int opt_gp_hyp_rounds = 4;      // vbmc_gp_hyp_sample: rounds queued between two reads of the unfinished-chain count (test hook)
   void (*release_cb)(void*) = nullptr;  // vbmc_set_release_callback
   void* release_cb_user = nullptr;
   int opt_adam_fused = 1;     // the optimiser loop as one launch per batch where its shape applies (adam_fused.hip)
@@ -670,6 +671,30 @@ inline int gp_lml_plan(int N, int D, int B, size_t cap_bytes, int forced) {
 // d_lml [S], d_dlml [S][P] (want_grad): results, device memory
 int launch_gp_lml(vbmc_ctx* ctx, int want_grad, const double* d_dsn2, double* d_sums, double* d_part, double* d_mg,
                   double* d_lml, double* d_dlml);
+// gp_hyp.hip: the lockstep slice chains of vbmc_gp_hyp_sample over lml + log prior.  One advance launch moves the chains
+// [b0, b0 + S) of a chunk on by one evaluation: chain c consumes lml[c] / flag[c] of the round before and writes its next
+// candidate into slot c - b0 of the buffers launch_gp_post_build reads.  All pointers device memory.
+struct GpHypArgs {
+  int N = 0, D = 0, P = 0, C = 0, n = 0, thin = 0, burn_in = 0;
+  uint64_t seed = 0;
+  double s2_min = 0.0;          // min_n s2_n (0 without user noise)
+  const double* s2 = nullptr;   // [N] user-provided noise variances, or null
+  const double *x0 = nullptr, *widths = nullptr, *lb = nullptr, *ub = nullptr;  // [C][P], [P] each
+  // the prior per parameter: location, scale (NaN: none), degrees of freedom (+inf: Gaussian), the constant part of t_p
+  const double *pmu = nullptr, *psig = nullptr, *pdf = nullptr, *pconst = nullptr;
+  const double* lml = nullptr;  // [C] the value the round before produced
+  int* flag = nullptr;          // [C] its factorisation flags: read, then cleared for the next build
+  double *x = nullptr, *xp = nullptr;  // [C][P] the chain's point; the point under evaluation
+  double* state = nullptr;      // [C][gp_hyp_state_elems()]
+  double *hyp_out = nullptr, *logpost = nullptr, *logprior = nullptr;  // [C][n][P], [C][n], [C][n]
+  long long* stats = nullptr;   // [C][4]
+  int* invalid = nullptr;       // [C]
+  double *g_hyp = nullptr, *g_sl = nullptr, *g_smeta = nullptr, *g_sn2 = nullptr;  // the staged GP's [S][P], [S], [S][3], [S][N]
+};
+size_t gp_hyp_state_elems();  // doubles of one chain's state (zeroed by the caller: a zeroed state is a chain at its start)
+int launch_gp_hyp_advance(vbmc_ctx* ctx, const GpHypArgs& a, int b0, int S);
+// *d_count = chains of [0, C) that have not finished
+int launch_gp_hyp_count(vbmc_ctx* ctx, const double* d_state, int C, int* d_count);
 // api_gp.hip: the device buffers of a GP state of N points, D dimensions, S samples, P hyper-parameters, kept across GP
 // updates and only grown (capacity n + n / 8 + 64: active sampling makes N creep up by one); with_post: also what a
 // device-built posterior keeps (y, residuals, noise variances, sl)

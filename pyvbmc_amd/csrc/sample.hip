@@ -14,7 +14,8 @@
 //     c = (n_lo, n_hi, b,    5)        box-uniform proposal n of active_importance_sampling (acq_is_prep.hip): b = 0 the
 //                                      training point, b = 1 + p the uniforms of dimensions 2 p, 2 p + 1
 //     c = (i_lo, i_hi, s,    6)        draw i of MCMC chain s of active_importance_sampling's step 2 (acq_is_mcmc.hip): words
-//                                      0, 1 as one 53-bit uniform, i in the order the chain consumes its draws
+//                                      0, 1 as one 53-bit uniform, i in the order the chain consumes its draws; likewise
+//                                      draw i of chain s of GP hyper-parameter sampling (gp_hyp.hip), under that call's seed
 //     c = (r_lo, r_hi, pair, 7)        normals of dimensions 2 pair, 2 pair + 1 of row r of an affine-Gaussian or box-normal
 //                                      source of the acquisition search (search.hip), under the source's own key
 // oracle/sample_ref.py restates both.  Component choice: inverse CDF of the weights

@@ -9,16 +9,20 @@ names so the hot-path functions accept either it or a real ``gpyreg.GP``:
 
 * ``update(X_new, y_new, s2_new, hyp)`` builds the posterior records on the host.
   That is the O(N^3) Cholesky done ONCE per GP fit -- an input of the path
-  (SURVEY 8a row a11), not part of it; hyper-parameter fitting itself (slice
-  sampling) is out of scope.
+  (SURVEY 8a row a11), not part of it.
 * ``predict`` runs on the MI355X (vbmc_gp_predict).
 * ``update(..., device=True)``, ``append`` and ``device_posterior`` build the same records on the device instead
   (vbmc_gp_posterior / vbmc_gp_append: batched FP64 Cholesky, one-point append) and leave them installed there, so
   the ``upload_gp`` that follows ships nothing.  Opt-in: the default path and its bits are unchanged.
 * ``log_marginal_likelihood`` / ``GP.log_likelihood``: the objective of hyper-parameter fitting and its gradient for a
-  batch of candidates on the device (vbmc_gp_lml), with a NumPy / SciPy host route of the same formulas.  The fitting
-  loop itself (optimiser, slice sampler, priors) stays with the caller.
+  batch of candidates on the device (vbmc_gp_lml), with a NumPy / SciPy host route of the same formulas.
+* ``hyper_log_prior``, ``sample_hyperparameters`` and ``GP.fit`` / ``set_bounds`` / ``set_priors``: hyper-parameter
+  fitting.  The sampler runs C slice chains over lml + log prior in lockstep on the device (vbmc_gp_hyp_sample), one
+  batch of C candidates per evaluation round, with a NumPy host route on the same draws.  The sampler, the priors and
+  ``fit``'s stages are this package's own: gpyreg's are not in the reference tree, and neither its stream nor its
+  default bounds are reproduced.
 """
+import math
 import ctypes as C
 import sys
 from types import SimpleNamespace
@@ -475,6 +479,223 @@ def log_marginal_likelihood(gp, hyp, *, grad=False, device=True, ctx=None):
     return (lml, dlml) if grad else lml
 
 
+# ------------------------------------------------------------------------------------------ hyper-parameter sampling
+def _prior_arrays(priors, P):
+    """``(mu, sigma, df)`` of P entries from a prior dict (None: no prior anywhere, sigma NaN)."""
+    if priors is None:
+        return tuple(np.full(P, np.nan) for _ in range(3))
+    mu, sigma, df = (np.array(np.broadcast_to(np.asarray(priors[k], dtype=np.float64), (P,))) for k in ("mu", "sigma", "df"))
+    on = ~np.isnan(sigma)
+    if np.any(on & ~((sigma > 0) & np.isfinite(sigma) & np.isfinite(mu) & (df > 0))):
+        raise ValueError("hyper prior: a parameter with a prior needs finite mu, sigma > 0 and df > 0 (or +inf)")
+    return mu, sigma, df
+
+
+def hyper_log_prior(hyp, priors, grad=False):
+    """Log prior of hyper-parameter vectors ``hyp`` (P,) or (B, P): ``sum_p t_p``, added with p ascending.
+
+    ``priors``: dict of arrays ``mu``, ``sigma``, ``df`` (P entries each).  ``t_p = 0`` where ``sigma_p`` is NaN (no
+    prior); else with z = (h_p - mu_p) / sigma_p it is the Gaussian's ``-1/2 log(2 pi) - log sigma - 1/2 z^2`` where
+    ``df_p`` is +inf and the Student-t's ``lgamma((nu+1)/2) - lgamma(nu/2) - 1/2 log(pi nu) - log sigma - (nu+1)/2
+    log1p(z^2/nu)`` otherwise -- what vbmc_gp_hyp_sample evaluates on the device.  ``grad=True``: ``(value, d/dhyp)``."""
+    h = np.asarray(hyp, dtype=np.float64)
+    one = h.ndim == 1
+    h = np.atleast_2d(h)
+    B, P = h.shape
+    mu, sigma, df = _prior_arrays(priors, P)
+    lp, g = np.zeros(B), np.zeros((B, P))
+    for p in range(P):
+        if np.isnan(sigma[p]):
+            continue
+        z = (h[:, p] - mu[p]) / sigma[p]
+        if np.isinf(df[p]):
+            c = -0.5 * math.log(2 * math.pi) - math.log(sigma[p])
+            t = c - 0.5 * (z * z)
+            g[:, p] = -z / sigma[p]
+        else:
+            nu = float(df[p])
+            c = math.lgamma(0.5 * (nu + 1)) - math.lgamma(0.5 * nu) - 0.5 * math.log(math.pi * nu) - math.log(sigma[p])
+            t = c - 0.5 * (nu + 1) * np.log1p(z * z / nu)
+            g[:, p] = -(nu + 1) * z / (sigma[p] * (nu + z * z))
+        lp = lp + t
+    if one:
+        return (float(lp[0]), g[0]) if grad else float(lp[0])
+    return (lp, g) if grad else lp
+
+
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_SLICE_OUT_CAP, _SLICE_SHRINK_CAP, _SLICE_STREAM = 32, 64, 6
+
+
+def _philox_bits53(i, chain, seed):
+    """The upper 53 bits of words 0, 1 of Philox4x32-10 block (i_lo, i_hi, chain, 6) under key ``seed`` (csrc/philox.h):
+    draw i of chain ``chain`` of the slice samplers (stream 6 of csrc/sample.hip's list)."""
+    m = 0xFFFFFFFF
+    c0, c1, c2, c3 = i & m, (i >> 32) & m, chain & m, _SLICE_STREAM
+    k0, k1 = seed & m, (seed >> 32) & m
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & m, (p0 >> 32) ^ c3 ^ k1, p0 & m
+        k0, k1 = (k0 + _PHILOX_W0) & m, (k1 + _PHILOX_W1) & m
+    return ((c0 << 32) | c1) >> 11
+
+
+def _slice_chain(log_p, x0, widths, lb, ub, n, thin, burn_in, seed, chain):
+    """One chain of the package's coordinate-wise slice sampler (Neal 2003) on the host, the statement
+    vbmc_gp_hyp_sample and vbmc_is_mcmc run on the device: level ``f(x) + log u`` (u in (0, 1]), an interval of width
+    ``widths_d`` placed around x_d and clipped to the bounds, stepping out (at most 32 evaluations a side) while f at an
+    end that is inside the bounds lies above the level, shrinkage (at most 64 proposals; x_d stays when the cap is
+    reached), x0 clipped into the bounds, ``burn_in + n thin`` sweeps over the coordinates in order, a sample kept after
+    every thin-th sweep past burn_in.  Returns ``(samples (n, P), f (n,), stats)`` with stats = [evaluations, draws,
+    step-out caps, shrink caps]; ``ValueError("Invalid value.")`` when f(x0) is not finite."""
+    x = np.maximum(np.minimum(np.array(x0, dtype=np.float64).ravel(), ub), lb)
+    P = x.size
+    cnt = {"evals": 0, "draws": 0, "out": 0, "shrink": 0}
+
+    def bits():
+        cnt["draws"] += 1
+        return _philox_bits53(cnt["draws"] - 1, chain, seed)
+
+    def f(pt):
+        cnt["evals"] += 1
+        return float(log_p(pt))
+
+    def at(d, v):
+        pt = x.copy()
+        pt[d] = v
+        return f(pt)
+
+    fx = f(x)
+    if not np.isfinite(fx):
+        raise ValueError("Invalid value.")
+    samples, f_vals = np.empty((n, P)), np.empty(n)
+    kept = 0
+    for t in range(burn_in + n * thin):
+        for d in range(P):
+            xd, w, lo, hi = x[d], widths[d], lb[d], ub[d]
+            ly = fx + np.log((bits() + 1) * 2.0**-53)
+            L = xd - w * (bits() * 2.0**-53)
+            R = L + w
+            L, R = max(L, lo), min(R, hi)
+            j = 0
+            while L > lo:
+                if j == _SLICE_OUT_CAP:
+                    cnt["out"] += 1
+                    break
+                if at(d, L) <= ly:
+                    break
+                L, j = max(L - w, lo), j + 1
+            j = 0
+            while R < hi:
+                if j == _SLICE_OUT_CAP:
+                    cnt["out"] += 1
+                    break
+                if at(d, R) <= ly:
+                    break
+                R, j = min(R + w, hi), j + 1
+            for j in range(_SLICE_SHRINK_CAP):
+                xp = L + (bits() * 2.0**-53) * (R - L)
+                fp = at(d, xp)
+                if fp > ly:
+                    x[d], fx = xp, fp
+                    break
+                if xp < xd:
+                    L = xp
+                else:
+                    R = xp
+            else:
+                cnt["shrink"] += 1
+        if t >= burn_in and (t - burn_in + 1) % thin == 0:
+            samples[kept], f_vals[kept] = x, fx
+            kept += 1
+    return samples, f_vals, np.array([cnt["evals"], cnt["draws"], cnt["out"], cnt["shrink"]], dtype=np.int64)
+
+
+def _const_noise_form(gp):
+    """Whether the GP's noise is constant additive noise exp(2 hyp_noise) plus, optionally, the user-provided ``s2`` -- the
+    forms vbmc_gp_hyp_sample evaluates itself -- and the ``s2`` (N,) that applies (None: none)."""
+    noise = getattr(gp, "noise", None)
+    s2 = getattr(gp, "s2", None)
+    s2 = None if s2 is None or not np.size(s2) else _lib.f64(np.ravel(s2))
+    if noise is None or not hasattr(noise, "compute"):
+        return True, s2  # (a stand-in without a noise object: the rule of ``_noise_var``)
+    if not getattr(noise, "constant_add", False):
+        return False, None
+    return True, s2 if getattr(noise, "user_provided_add", False) else None
+
+
+def sample_hyperparameters(gp, x0, *, lb, ub, widths, priors=None, n=1, thin=1, burn_in=0, seed=None, device=True, ctx=None):
+    """Slice-sample the hyper-parameters of ``gp`` from ``lml + log prior``: C chains, one per row of ``x0`` (C, P).
+
+    ``gp`` is read as ``log_marginal_likelihood`` reads it.  ``lb``, ``ub`` (finite), ``widths`` (> 0): P entries each;
+    ``priors``: as ``hyper_log_prior`` takes them (None: flat inside the bounds).  Chain c keeps ``n`` samples, one after
+    every ``thin``-th of the sweeps that follow ``burn_in``; its draws are counter-based (Philox block (i, c, stream 6)
+    under ``seed``; None: a fresh seed), so its samples depend on its own start alone, not on C.
+    ``device=True``: the chains advance in lockstep on the device (vbmc_gp_hyp_sample), every evaluation round one batch
+    of C candidates through vbmc_gp_lml's kernels; the posterior the context holds is untouched.  Shapes the device
+    refuses (D > 32, a noise bound that allows sn2_div < 1e-6, noise that is not constant-additive) and ``device=False``
+    run the same chains in NumPy over the host lml, with the same draws.
+    Returns ``dict(samples (C, n, P), log_post (C, n), log_priors (C, n), stats (C, 4))``, stats = [evaluations, draws,
+    step-out caps hit, shrink caps hit].  ``ValueError("Invalid value.")`` when a chain's start has no finite density."""
+    X = _lib.f64(np.atleast_2d(gp.X))
+    y = _lib.f64(np.ravel(gp.y))
+    N, D = X.shape
+    kind = mean_kind_of(gp)
+    P = D + 2 + (0, 1, 1 + 2 * D)[kind]
+    x0 = _lib.f64(np.atleast_2d(x0))
+    if x0.ndim != 2 or x0.shape[1] != P or x0.shape[0] < 1:
+        raise ValueError(f"sample_hyperparameters: x0 must be (C, {P})")
+    Cn = x0.shape[0]
+    lb, ub, widths = (_lib.f64(np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), (P,)))) for a in (lb, ub, widths))
+    if not (np.all(np.isfinite(lb)) and np.all(np.isfinite(ub)) and np.all(lb <= ub)):
+        raise ValueError("sample_hyperparameters: finite bounds with lb <= ub are required")
+    if not (np.all(widths > 0) and np.all(np.isfinite(widths))):
+        raise ValueError("sample_hyperparameters: widths must be positive")
+    n, thin, burn_in = int(n), int(thin), int(burn_in)
+    if n < 1 or thin < 1 or burn_in < 0:
+        raise ValueError("sample_hyperparameters: n >= 1, thin >= 1, burn_in >= 0")
+    mu, sigma, df = (_lib.f64(a) for a in _prior_arrays(priors, P))
+    pri = {"mu": mu, "sigma": sigma, "df": df}
+    seed = int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0]) if seed is None else int(seed)
+    seed &= 0xFFFFFFFFFFFFFFFF
+    const_form, s2 = _const_noise_form(gp)
+    if device and const_form:
+        ctx = (getattr(gp, "ctx", None) or _lib.default_context()) if ctx is None else ctx
+        samples, lpost, lprior = np.zeros((Cn, n, P)), np.zeros((Cn, n)), np.zeros((Cn, n))
+        stats, invalid = np.zeros((Cn, 4), dtype=np.int64), np.zeros(Cn, dtype=np.int32)
+        rc = ctx._lib.vbmc_gp_hyp_sample(
+            ctx._h, N, D, P, kind, _lib.ptr(X), _lib.ptr(y), _lib.ptr(s2), Cn, _lib.ptr(x0), _lib.ptr(widths), _lib.ptr(lb),
+            _lib.ptr(ub), _lib.ptr(mu), _lib.ptr(sigma), _lib.ptr(df), n, thin, burn_in, C.c_uint64(seed), _lib.ptr(samples),
+            _lib.ptr(lpost), _lib.ptr(lprior), stats.ctypes.data_as(C.POINTER(C.c_int64)),
+            invalid.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc != _lib.E_UNSUP:
+            ctx.check(rc)
+            if np.any(invalid):
+                raise ValueError("Invalid value.")
+            return dict(samples=samples, log_post=lpost, log_priors=lprior, stats=stats)
+
+    def log_p(h):
+        with np.errstate(all="ignore"):
+            sn2 = _noise_var(gp, h[D + 1 : D + 2])
+            lml = _host_lml(X, y, kind, h, sn2, np.min(sn2), 0.0, False)[0]
+        return lml + hyper_log_prior(h, pri)
+
+    out = [_slice_chain(log_p, x0[c], widths, lb, ub, n, thin, burn_in, seed, c) for c in range(Cn)]
+    samples = np.stack([o[0] for o in out])
+    return dict(samples=samples, log_post=np.stack([o[1] for o in out]),
+                log_priors=np.stack([hyper_log_prior(o[0], pri) for o in out]), stats=np.stack([o[2] for o in out]))
+
+
+# hyper-parameter blocks by gpyreg's names, in the layout of hyp: (name, first index, length) for a GP of dimension D
+def _hyp_blocks(D, mean_n):
+    blocks = [("covariance_log_lengthscale", 0, D), ("covariance_log_outputscale", D, 1), ("noise_log_scale", D + 1, 1)]
+    if mean_n >= 1:
+        blocks.append(("mean_const", D + 2, 1))
+    if mean_n == 1 + 2 * D:
+        blocks += [("mean_location", D + 3, D), ("mean_log_scale", 2 * D + 3, D)]
+    return blocks
+
+
 class GP:
     def __init__(self, D, covariance, mean, noise):
         if not isinstance(covariance, SquaredExponential):
@@ -489,6 +710,10 @@ class GP:
         self.posteriors = None
         self.temporary_data = {}
         self._ctx = None
+        P = D + 2 + mean.hyperparameter_count(D)
+        self._bounds = {"lb": np.full(P, -np.inf), "ub": np.full(P, np.inf)}
+        # the priors of hyper-parameter fitting, one entry per parameter: sigma NaN = no prior, df +inf = Gaussian
+        self.hyper_priors = {"mu": np.full(P, np.nan), "sigma": np.full(P, np.nan), "df": np.full(P, np.nan)}
 
     @property
     def ctx(self):
@@ -592,6 +817,169 @@ class GP:
 
     def get_hyperparameters(self, as_array=True):
         return np.stack([p.hyp for p in self.posteriors])
+
+    # ------------------------------------------------------------------------------------ hyper-parameter fitting
+    def _blocks(self):
+        return _hyp_blocks(self.D, self.mean.hyperparameter_count(self.D))
+
+    def _block_of(self, name):
+        for nm, first, length in self._blocks():
+            if nm == name:
+                return slice(first, first + length)
+        raise ValueError(f"this GP has no hyper-parameter block '{name}'")
+
+    @staticmethod
+    def _fill(dst, sl, values):
+        """dst[sl] = values (a scalar or the block's length), NaN entries leaving a slot as it was"""
+        v = np.array(np.broadcast_to(np.asarray(values, dtype=np.float64), dst[sl].shape))
+        keep = np.isnan(v)
+        v[keep] = dst[sl][keep]
+        dst[sl] = v
+
+    def set_bounds(self, bounds):
+        """Bounds of the hyper-parameters: the array form ``{"lb": (P,), "ub": (P,)}`` or gpyreg's name-keyed form
+        ``{"noise_log_scale": (lb, ub), ...}`` (the blocks of ``get_bounds``; scalars or the block's length).  NaN entries
+        leave a slot as it was."""
+        if set(bounds) <= {"lb", "ub"}:
+            for k, v in bounds.items():
+                self._fill(self._bounds[k], slice(None), v)
+            return
+        for name, pair in bounds.items():
+            if pair is None:
+                continue
+            sl = self._block_of(name)
+            self._fill(self._bounds["lb"], sl, pair[0])
+            self._fill(self._bounds["ub"], sl, pair[1])
+
+    def get_bounds(self, as_array=False):
+        """``{name: (lb, ub)}`` per block (``covariance_log_lengthscale`` (D), ``covariance_log_outputscale``,
+        ``noise_log_scale``, ``mean_const``, ``mean_location`` (D), ``mean_log_scale`` (D), as far as the mean has them), or
+        copies of the arrays ``{"lb", "ub"}`` with ``as_array``."""
+        if as_array:
+            return {k: v.copy() for k, v in self._bounds.items()}
+        return {nm: (self._bounds["lb"][f : f + n].copy(), self._bounds["ub"][f : f + n].copy()) for nm, f, n in self._blocks()}
+
+    def set_priors(self, priors):
+        """Priors of the hyper-parameters: the array form ``{"mu", "sigma", "df"}`` (P entries each; sigma NaN = no prior, df
+        +inf = Gaussian) or gpyreg's name-keyed form ``{"noise_log_scale": ("student_t", (mu, sigma, df)), ...}`` with
+        ``("gaussian", (mu, sigma))`` and None (no prior) as the other kinds.  NaN entries leave a slot as it was."""
+        hp = self.hyper_priors
+        if set(priors) <= {"mu", "sigma", "df"}:
+            for k, v in priors.items():
+                self._fill(hp[k], slice(None), v)
+            return
+        for name, spec in priors.items():
+            sl = self._block_of(name)
+            if spec is None:
+                for k in ("mu", "sigma", "df"):
+                    hp[k][sl] = np.nan
+                continue
+            kind, par = spec
+            if kind == "student_t":
+                mu, sigma, df = par
+            elif kind == "gaussian":
+                (mu, sigma), df = par, np.inf
+            else:
+                raise NotImplementedError(f"hyper prior '{kind}': only 'gaussian' and 'student_t' are supported")
+            self._fill(hp["mu"], sl, mu)
+            self._fill(hp["sigma"], sl, sigma)
+            self._fill(hp["df"], sl, df)
+
+    def get_priors(self, as_array=False):
+        """``{name: spec}`` per block in ``set_priors``' name-keyed form (None: no prior on the whole block), or copies of
+        the arrays with ``as_array``."""
+        hp = self.hyper_priors
+        if as_array:
+            return {k: v.copy() for k, v in hp.items()}
+        out = {}
+        for nm, f, n in self._blocks():
+            mu, sigma, df = (hp[k][f : f + n].copy() for k in ("mu", "sigma", "df"))
+            if np.all(np.isnan(sigma)):
+                out[nm] = None
+            elif np.all(np.isinf(df[~np.isnan(sigma)])):
+                out[nm] = ("gaussian", (mu, sigma))
+            else:
+                out[nm] = ("student_t", (mu, sigma, df))
+        return out
+
+    def fit(self, X=None, y=None, s2=None, hyp0=None, options=None, *, device=True, seed=None):
+        """Fit the hyper-parameters to the training data (``X``, ``y``, ``s2`` REPLACE the GP's when given) inside the
+        bounds of ``set_bounds`` (finite ones are required) under the priors of ``set_priors``:
+
+        1. candidates: the rows of ``hyp0`` (default: the present records' samples, else the middle of the box) clipped
+           into the bounds, plus ``init_N`` uniform draws in the box from ``np.random.default_rng(seed)``; all of them are
+           scored in ONE ``log_marginal_likelihood`` batch, plus the prior;
+        2. SciPy L-BFGS-B inside the bounds from the best ``opts_N`` of them on -(lml + log prior) with its gradient
+           (tolerance ``tol_opt``); the best point seen is the optimum;
+        3. ``n_samples`` > 0: that many slice chains from the optimum, one kept sample each after ``burn`` sweeps and
+           ``thin`` more (``sample_hyperparameters``; ``widths`` as given, else (ub - lb) / 8);
+        4. ``update(hyp=samples, device=device)``: with the device route the posterior stays installed.
+
+        ``options``: a dict with ``init_N`` (0), ``opts_N`` (1), ``n_samples`` (0), ``thin`` (1), ``burn`` (0), ``widths``
+        (None), ``tol_opt`` (1e-5) -- the keys the reference's ``_get_gp_training_options`` fills.  Returns ``(hyp (S, P),
+        optimize_result, sample_result)``: ``optimize_result`` a dict ``hyp``, ``log_post``, ``candidates``,
+        ``candidate_log_post``, ``n_iterations``; ``sample_result`` (None without sampling) a dict ``samples`` (S, P),
+        ``log_priors`` (S,), ``log_post`` (S,), ``stats`` (S, 4).  gpyreg's own design of starting points, its default
+        bounds and its random stream are not reproduced."""
+        import scipy.optimize as sopt
+
+        opts = {"init_N": 0, "opts_N": 1, "n_samples": 0, "thin": 1, "burn": 0, "widths": None, "tol_opt": 1e-5}
+        opts.update({k: v for k, v in (options or {}).items() if k in opts and v is not None})
+        if X is not None:
+            self.X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+            self.y = np.asarray(y, dtype=np.float64).reshape(-1, 1)
+            self.s2 = None if s2 is None else np.asarray(s2, dtype=np.float64).reshape(-1, 1)
+        lb, ub = self._bounds["lb"].copy(), self._bounds["ub"].copy()
+        if not (np.all(np.isfinite(lb)) and np.all(np.isfinite(ub)) and np.all(lb <= ub)):
+            raise ValueError("GP.fit: finite bounds with lb <= ub are required (set_bounds)")
+        P = lb.size
+        pri = self.hyper_priors
+        ctx = self.ctx if device else None
+        if hyp0 is None:
+            hyp0 = np.stack([np.ravel(p.hyp) for p in self.posteriors]) if self.posteriors is not None else 0.5 * (lb + ub)
+        hyp0 = np.atleast_2d(np.asarray(hyp0, dtype=np.float64))
+        if hyp0.shape[1] != P:
+            raise ValueError(f"GP.fit: hyp0 has {hyp0.shape[1]} columns, the GP takes {P}")
+        rng = np.random.default_rng(seed)
+        cand = np.clip(hyp0, lb, ub)
+        if int(opts["init_N"]) > 0:
+            cand = np.vstack([cand, lb + (ub - lb) * rng.random((int(opts["init_N"]), P))])
+        score = log_marginal_likelihood(self, cand, device=device, ctx=ctx) + hyper_log_prior(cand, pri)
+        score = np.where(np.isnan(score), -np.inf, score)
+        if not np.any(np.isfinite(score)):
+            raise ValueError("GP.fit: no candidate has a finite log posterior")
+
+        def neg(h):
+            lml, dl = log_marginal_likelihood(self, h[None, :], grad=True, device=device, ctx=ctx)
+            lp, dp = hyper_log_prior(h, pri, grad=True)
+            if not (np.isfinite(lml[0]) and np.all(np.isfinite(dl[0]))):
+                return 1e100, np.zeros(P)
+            return -(lml[0] + lp), -(dl[0] + dp)
+
+        order = np.argsort(-score, kind="stable")
+        best_h, best_f, n_it = cand[order[0]].copy(), float(score[order[0]]), 0
+        for i in order[: max(int(opts["opts_N"]), 0)]:
+            if not np.isfinite(score[i]):
+                continue
+            res = sopt.minimize(neg, cand[i], jac=True, method="L-BFGS-B", bounds=list(zip(lb, ub)), tol=float(opts["tol_opt"]))
+            n_it += int(res.nit)
+            h = np.clip(res.x, lb, ub)
+            f = float(log_marginal_likelihood(self, h[None, :], device=device, ctx=ctx)[0] + hyper_log_prior(h, pri))
+            if np.isfinite(f) and f > best_f:
+                best_h, best_f = h, f
+        opt_res = dict(hyp=best_h, log_post=best_f, candidates=cand, candidate_log_post=score, n_iterations=n_it)
+        S = int(opts["n_samples"])
+        if S <= 0:
+            hyp, smp_res = best_h[None, :], None
+        else:
+            widths = (ub - lb) / 8 if opts["widths"] is None else np.asarray(opts["widths"], dtype=np.float64)
+            sub = None if seed is None else int(rng.integers(0, 2**63))
+            r = sample_hyperparameters(self, np.tile(best_h, (S, 1)), lb=lb, ub=ub, widths=widths, priors=pri, n=1,
+                                       thin=int(opts["thin"]), burn_in=int(opts["burn"]), seed=sub, device=device, ctx=ctx)
+            hyp = r["samples"][:, 0, :]
+            smp_res = dict(samples=hyp, log_priors=r["log_priors"][:, 0], log_post=r["log_post"][:, 0], stats=r["stats"])
+        self.update(hyp=hyp, device=device)
+        return hyp, opt_res, smp_res
 
     def predict(self, x_star, y_star=None, s2_star=0, add_noise=False, separate_samples=False, *,
                 ctx=None):

@@ -197,6 +197,25 @@ def main(out):
         ctx.check(L.vbmc_mtv(h, D, C.byref(sides[0]), C.byref(sides[1]), K2, *[p(a) for a in m2[:4]], p(mtv),
                              info.ctypes.data_as(C.POINTER(C.c_int64))))
         res[f"mtv/dev{dev}/mtv"], res[f"mtv/dev{dev}/info"] = mtv, info
+    # ---- vbmc_gp_hyp_sample: N = 65, D = 3, constant mean, 3 chains of 2 kept samples (a generator of its own: the rows
+    # above keep their inputs)
+    r2 = np.random.default_rng(2024)
+    N, D, Cn, nk = 65, 3, 3, 2
+    X = f64(r2.standard_normal((N, D)) * 2.0)
+    y = f64(-0.5 * np.sum(X**2, axis=1) / D + 0.3 * r2.standard_normal(N))
+    h0 = np.concatenate([np.log(1.4 * np.ones(D)), [np.log(1.2)], [np.log(0.3)], [0.1]])
+    P = h0.size
+    x0 = f64(h0 + 0.1 * r2.standard_normal((Cn, P)))
+    lb, ub, wd = f64(h0 - 1.5), f64(h0 + 1.5), f64(np.full(P, 0.6))
+    pmu, psg, pdf = f64(np.full(P, np.log(1.5))), f64(np.full(P, np.nan)), f64(np.full(P, 3.0))
+    psg[:D], psg[D + 1], pdf[D + 1] = 1.0, 0.5, np.inf
+    smp, lpo, lpr = np.empty((Cn, nk, P)), np.empty((Cn, nk)), np.empty((Cn, nk))
+    st, inv = np.zeros((Cn, 4), dtype=np.int64), np.zeros(Cn, dtype=np.int32)
+    ctx.check(L.vbmc_gp_hyp_sample(h, N, D, P, _lib.MEAN_CONST, p(X), p(y), None, Cn, p(x0), p(wd), p(lb), p(ub), p(pmu),
+                                   p(psg), p(pdf), nk, 2, 1, C.c_uint64(77), p(smp), p(lpo), p(lpr),
+                                   st.ctypes.data_as(C.POINTER(C.c_int64)), inv.ctypes.data_as(C.POINTER(C.c_int32))))
+    for k, v in zip(("samples", "log_post", "log_priors", "stats", "invalid"), (smp, lpo, lpr, st, inv)):
+        res[f"gp_hyp_sample/{k}"] = v
     ctx.close()
     nans = sorted(k for k, v in res.items() if np.asarray(v).dtype.kind == "f" and np.isnan(v).any())
     assert not nans, f"NaN in {nans}: np.array_equal could not compare them"
