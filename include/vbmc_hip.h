@@ -131,7 +131,8 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on);
  *        8 = vbmc_gp_lml's last chunk: its factorisation and its value / gradient kernels,
  *        9 = vbmc_search_fill's uploads and launches, 10 = vbmc_search_eval's acquisition, noise lookup and mask,
  *        11 = its sort and gather,
- *        12 = vbmc_gp_hyp_sample: all the rounds of the last call (a call that launched nothing leaves no record). */
+ *        12 = vbmc_gp_hyp_sample: all the rounds of the last call (a call that launched nothing leaves no record),
+ *        13 = vbmc_search_cmaes: all the rounds of the last call, likewise. */
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out);
 
 /* Host-side wall-clock breakdown (microseconds) of the most recent vbmc_neg_elcbo:
@@ -748,6 +749,46 @@ int vbmc_search_eval(vbmc_ctx* ctx, int kind, double y_max, double tol_gp_var, d
                      const double* X_rescaled_NxD, const double* sn2_new_N, const double* length_scale_D, int use_xf,
                      const double* lb_eps_orig_D, const double* ub_eps_orig_D, double* acq_M, int64_t* order_M,
                      double* X_sorted_MxD);
+
+/* ---- the local optimisation of the acquisition search: CMA-ES ------------- *
+ *
+ * vbmc/active_sample.py:355-423 with search_optimizer = "cmaes" (the reference's default): from the best ranked search
+ * point the acquisition function is minimised in the box [lb_D, ub_D] (:366-375) by `cma.fmin` with tolfun (:377-380),
+ * maxfevals = search_max_fun_evals and the initial step max(sqrt(diag Sigma)) (:383-389), thousands of single-point
+ * acquisition calls from a Python optimiser.  vbmc_search_cmaes runs R such optimisations in lockstep on the device
+ * (R = 1 is the reference's; with R > 1 a caller starts from the R best ranked points): every generation of all runs is
+ * one batch of R lambda rows through the scoring launches of vbmc_search_eval.  The optimiser is this library's own
+ * (csrc/cmaes.hip states it; there is no stream to be bit-compatible with: `cma` is a third-party package): a
+ * (mu/mu_w, lambda)-CMA-ES with an explicit covariance whose Cholesky factor is recomputed every generation, candidates
+ * clipped to the box, normals from Philox stream 8 under the key seed + (r + 1) 0x9E3779B97F4A7C15 of run r.  The
+ * reference wraps its call in cma.NoiseHandler; the acquisition functions are deterministic, so there is no noise
+ * handling here.  Every candidate is evaluated with its integer columns rounded as vbmc_search_fill rounds them
+ * (abstract_acq_fcn.py:77-79, 149-193) and masked by the hard bounds (:133-139, +inf), while the unrounded point drives
+ * the optimiser; the rounded point is what becomes the best.  The start itself is evaluated first (f0_R, one row).
+ *
+ * The scoring arguments (kind .. ub_eps_orig_D) are vbmc_search_eval's.  opts: lambda (0 = 4 + floor(3 ln D)),
+ * max_fevals (the start counts), tol_fun, tol_x (<= 0: 1e-11 sigma0), seed.  Outputs, each nullable: the best evaluated
+ * point and its value, the start's value, and the final mean, step size and covariance of every run; stats_Rx4 =
+ * {generations, evaluations, stop reason, generation of the best (0: the start)}, stop reason 1 tolfun, 2 tolx,
+ * 3 maxfevals, 4 condition (of the Cholesky factor), 5 invalid (a generation without a finite value).
+ * Refused before anything is launched: VBMC_E_UNSUP for D > 32, D = 1 (the reference switches to Nelder-Mead there),
+ * lambda > 64, R lambda above the search set's row cap (2^20); VBMC_E_ARG for R < 1, lambda < 4, sigma0 <= 0, a box that
+ * is not finite or has lb > ub, a start outside the box, max_fevals < 1 + lambda, GP or mixture not set, a missing noise
+ * table for the kinds that need it.  The host queues vbmc_set_option "cmaes_rounds" rounds (default 8) between two reads
+ * of the count of runs not yet stopped.  The resident search set, the installed GP and the mixture are left as they are. */
+typedef struct vbmc_cmaes_opts {
+  int lambda;
+  int64_t max_fevals;
+  double tol_fun;
+  double tol_x;
+  uint64_t seed;
+} vbmc_cmaes_opts;
+int vbmc_search_cmaes(vbmc_ctx* ctx, int kind, double y_max, double tol_gp_var, double u, int64_t n_noise,
+                      const double* X_rescaled_NxD, const double* sn2_new_N, const double* length_scale_D, int use_xf,
+                      const double* lb_eps_orig_D, const double* ub_eps_orig_D, int R, const double* x0_RxD,
+                      const double* sigma0_R, const double* lb_D, const double* ub_D, uint32_t integer_bits,
+                      const vbmc_cmaes_opts* opts, double* x_best_RxD, double* f_best_R, double* f0_R, double* mean_RxD,
+                      double* sigma_R, double* C_RxDxD, int64_t* stats_Rx4);
 
 /* ---- sampling and its Monte-Carlo consumers -------------- */
 

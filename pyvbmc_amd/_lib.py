@@ -25,6 +25,7 @@ W_NOT_FUSED = 2   # vbmc_adam_run_auto: the one-launch loop does not apply (or g
 T_ENTMC, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML = range(9)
 T_SEARCH_FILL, T_SEARCH_EVAL, T_SEARCH_SORT = 9, 10, 11
 T_GP_HYP = 12
+T_SEARCH_CMAES = 13
 
 
 class VbmcHipError(RuntimeError):
@@ -113,6 +114,18 @@ class SearchSource(C.Structure):
         ("rows", C.c_int64),
         ("data", _dp),
         ("df", C.c_double),
+        ("seed", C.c_uint64),
+    ]
+
+
+class CmaesOpts(C.Structure):
+    """vbmc_cmaes_opts: the optimiser's settings (vbmc_search_cmaes)."""
+
+    _fields_ = [
+        ("lam", C.c_int),
+        ("max_fevals", C.c_int64),
+        ("tol_fun", C.c_double),
+        ("tol_x", C.c_double),
         ("seed", C.c_uint64),
     ]
 
@@ -230,6 +243,9 @@ SIGNATURES = {
     "vbmc_search_put": (C.c_int, [_vp, C.c_int64, C.c_int, _dp, C.c_uint32, C.c_int]),
     "vbmc_search_eval": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, _dp, _dp, _dp, C.c_int, _dp,
                                    _dp, _dp, C.POINTER(C.c_int64), _dp]),
+    "vbmc_search_cmaes": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, _dp, _dp, _dp, C.c_int, _dp,
+                                    _dp, C.c_int, _dp, _dp, _dp, _dp, C.c_uint32, C.POINTER(CmaesOpts), _dp, _dp, _dp, _dp,
+                                    _dp, _dp, C.POINTER(C.c_int64)]),
     "vbmc_mixture_sample": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, C.POINTER(C.c_int32)]),
     "vbmc_mixture_sample_t": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, C.c_double, _dp, C.POINTER(C.c_int32)]),
     "vbmc_kl_div_mc": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, _dp, _dp, _dp, _dp]),

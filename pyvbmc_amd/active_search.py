@@ -421,5 +421,162 @@ def search(acq_fcn, gp, vp, function_logger, optim_state, options, *, number_of_
                            X_search=np.delete(X_search, idx, 0), idx_cache=np.delete(idx_cache, idx, 0))
 
 
-__all__ = ["get_search_points", "search", "philox_plan", "put_points", "evaluate_resident", "sub_seed", "mvn_factor",
-           "SOURCES"]
+def cmaes_resident(ctx, D, kind, y_max, tol_var, u, noise, use_xf, lb_eps_orig, ub_eps_orig, x0, sigma0, lb, ub, *,
+                   int_bits=0, lam=None, max_fevals, tol_fun, tol_x=None, seed=0):
+    """``vbmc_search_cmaes``: R CMA-ES runs (the rows of ``x0``) in lockstep on the GP, mixture and importance state the
+    context holds; the scoring arguments are ``evaluate_resident``'s.  Returns ``x_best`` (R, D), ``f_best``, ``f0``,
+    ``mean``, ``sigma``, ``C`` (R, D, D) and ``stats`` (R, 4: generations, evaluations, stop reason, generation of the
+    best), the fields ``pyvbmc_amd.cmaes.fmin`` returns per run."""
+    x0 = _lib.f64(np.atleast_2d(x0))
+    R = x0.shape[0]
+    sigma0 = _lib.f64(np.broadcast_to(np.asarray(sigma0, dtype=np.float64), (R,)))
+    lb, ub = _lib.f64(np.ravel(lb)), _lib.f64(np.ravel(ub))
+    lb_eps, ub_eps = _lib.f64(np.ravel(lb_eps_orig)), _lib.f64(np.ravel(ub_eps_orig))
+    opts = _lib.CmaesOpts(0 if lam is None else int(lam), int(max_fevals), float(tol_fun),
+                          0.0 if tol_x is None else float(tol_x), int(seed) % 2**64)
+    out = SimpleNamespace(x_best=np.empty((R, D)), f_best=np.empty(R), f0=np.empty(R), mean=np.empty((R, D)), sigma=np.empty(R),
+                          C=np.empty((R, D, D)), stats=np.empty((R, 4), dtype=np.int64))
+    ctx.check(ctx._lib.vbmc_search_cmaes(ctx._h, kind, y_max, tol_var, u, 0 if noise[0] is None else noise[0].shape[0],
+                                         _lib.ptr(noise[0]), _lib.ptr(noise[1]), _lib.ptr(noise[2]), use_xf, _lib.ptr(lb_eps),
+                                         _lib.ptr(ub_eps), R, _lib.ptr(x0), _lib.ptr(sigma0), _lib.ptr(lb), _lib.ptr(ub), int_bits,
+                                         C.byref(opts), _lib.ptr(out.x_best), _lib.ptr(out.f_best), _lib.ptr(out.f0),
+                                         _lib.ptr(out.mean), _lib.ptr(out.sigma), _lib.ptr(out.C),
+                                         out.stats.ctypes.data_as(C.POINTER(C.c_int64))))
+    return out
+
+
+def _scoring_args(acq_eval, gp, vp, function_logger, optim_state, ctx, D):
+    """What ``search`` hands to ``evaluate_resident`` for an acquisition object, with the GP, the mixture and the
+    importance state uploaded: ``(kind, y_max, tol_var, u, noise, use_xf)``."""
+    upload_vp(vp, ctx)
+    upload_gp(gp, ctx)
+    is_kind = isinstance(acq_eval, _QuantileAcq)
+    if is_kind:
+        acq_eval._upload_state(gp, optim_state["active_importance_sampling"], ctx)
+    kind = _lib.ACQ_IS if is_kind else acq_eval._kind
+    noise = (None, None, None)
+    if is_kind or kind == ACQ_NOISY:
+        noise = (_lib.f64(gp.temporary_data.get("X_rescaled")), _lib.f64(np.ravel(gp.temporary_data.get("sn2_new"))),
+                 _lib.f64(np.ravel(optim_state.get("gp_length_scale"))))
+    tol_var = float(optim_state.get("tol_gp_var")) if optim_state.get("variance_regularized_acq_fcn") else 0.0
+    y_max = float(function_logger.y_max) if kind in (ACQ_STD, ACQ_LOG, ACQ_NOISY) else 0.0
+    return kind, y_max, tol_var, float(getattr(acq_eval, "u", 0.0)), noise, _xf_flag(vp.parameter_transformer, ctx, D)
+
+
+def refine(res, acq_fcn, gp, vp, function_logger, optim_state, options, *, n_starts=1, seed=None, device=True, ctx=None):
+    """The local optimisation that follows the ranked search in ``active_sample`` (:355-423): from the best search
+    point of ``res`` (what ``search`` returned) the acquisition function is minimised in the search box, and the result
+    replaces the point only if it improves on the search's value.
+
+    * ``options["search_optimizer"] == "none"``: ``res.X_acq`` comes back unchanged.
+    * The box (:366-375): the search bounds extended to contain the start; with non-finite search bounds,
+      ``gp.X.min(0) - 0.1 range`` .. ``gp.X.max(0) + 0.1 range``, extended likewise.  (The reference writes
+      ``np.minimum(gp.X, x0)`` there, an N x D array; the per-dimension extreme is what is meant.)
+    * ``tol_fun`` (:377-380): 1e-2 for a log-valued acquisition, else ``max(1e-12, |f_val_old| 1e-3)``.
+    * The initial step (:383-389): ``max(sqrt(diag Sigma))``, Sigma the posterior's covariance in transformed space
+      (``search_cmaes_vp_init``) or that of the HPD set of ``options["hpd_frac"]``.
+    * ``max_fevals = options["search_max_fun_evals"]``.
+    * D >= 2: CMA-ES -- ``vbmc_search_cmaes`` on the device (every generation one batch through the scoring launches
+      of ``search``), or with ``device=False`` ``pyvbmc_amd.cmaes.fmin`` around this package's batched acquisition call:
+      the same algorithm and draws.  The optimiser is this package's own (csrc/cmaes.hip), not ``cma``: no
+      ``cma.NoiseHandler`` (the acquisition functions are deterministic), no boundary transformation, no restarts.
+      ``n_starts > 1``: the start and the next best ranked rows of ``res`` with a finite value run side by side (the
+      reference has one), and the best of the runs is taken.
+    * D == 1: SciPy's Nelder-Mead around the acquisition call, as the reference; host code.
+    * Accepted only if ``f_best < f_val_old``; then ``X_acq`` is the rounded point (``_real2int``) and
+      ``idx_cache_acq`` NaN (:417-423).
+
+    Returns ``X_acq`` (1, D), ``idx_cache_acq``, ``f_val``, ``f_val_old``, ``accepted`` and, for CMA-ES, ``stats`` (one
+    row per run: generations, evaluations, stop reason, generation of the best), ``runs`` (the optimiser's fields per
+    run), ``best_run`` and the optimiser's arguments ``lb``, ``ub``, ``sigma0``, ``tol_fun``."""
+    from . import cmaes as _cmaes
+
+    X_acq = np.array(res.X_acq, dtype=np.float64).reshape(1, -1)
+    D = X_acq.shape[1]
+    idx = int(res.order[0]) if options["search_cache_frac"] > 0 else int(np.argmin(res.acq_fast))
+    f_val_old = float(res.acq_fast[idx])  # :363
+    same = SimpleNamespace(X_acq=X_acq, idx_cache_acq=res.idx_cache_acq, f_val=f_val_old, f_val_old=f_val_old, accepted=False,
+                           stats=None, runs=None, best_run=None)
+    if options["search_optimizer"] == "none":  # :356
+        return same
+    acq_eval = string_to_acq(acq_fcn) if isinstance(acq_fcn, str) else acq_fcn
+    if not isinstance(acq_eval, AbstractAcqFcn) or acq_eval._kind is None:
+        raise TypeError("refine: acq_fcn must be one of pyvbmc_amd.acquisition's classes (or its constructor string)")
+    _check_D(D)
+    x0 = X_acq[0].copy()  # :364
+    lb_s, ub_s = np.ravel(optim_state["lb_search"]), np.ravel(optim_state["ub_search"])
+    gp_X = np.asarray(gp.X, dtype=np.float64)
+    if np.isfinite(lb_s).all() and np.isfinite(ub_s).all():  # :366-375
+        lb, ub = np.minimum(x0, lb_s), np.maximum(x0, ub_s)
+    else:
+        xrange = gp_X.max(0) - gp_X.min(0)
+        lb, ub = np.minimum(gp_X.min(0), x0) - 0.1 * xrange, np.maximum(gp_X.max(0), x0) + 0.1 * xrange
+    tol_fun = 1e-2 if acq_eval.acq_info.get("log_flag") else max(1e-12, abs(f_val_old * 1e-3))  # :377-380
+    pt = function_logger.parameter_transformer
+    integer_vars = optim_state.get("integer_vars")
+
+    def acq_batch(X):
+        return np.ravel(acq_eval(np.array(X, dtype=np.float64), gp, vp, function_logger, optim_state))
+
+    def rounded(X):
+        return AbstractAcqFcn._real2int(np.array(X, dtype=np.float64), pt, integer_vars)
+
+    if D == 1:  # :357-361, :407-413
+        from scipy.optimize import minimize
+
+        r = minimize(lambda x: float(acq_batch(np.reshape(x, (1, 1)))[0]), x0, method="Nelder-Mead", tol=tol_fun)
+        x_opt, f_opt, stats, runs, best_run = np.reshape(r.x, (1, 1)), float(r.fun), None, None, None
+        x_opt = rounded(x_opt)
+    else:
+        optimizer = options["search_optimizer"]
+        if optimizer != "cmaes":
+            raise NotImplementedError("Not implemented yet")  # :414-415
+        if options["search_cmaes_vp_init"]:  # :383-389
+            _, Sigma = vp.moments(orig_flag=False, cov_flag=True)
+        else:
+            order_y = np.argsort(np.asarray(gp.y), axis=None)[::-1]
+            X_hpd = gp_X[order_y[0:round(options["hpd_frac"] * gp_X.shape[0])]]
+            Sigma = np.cov(X_hpd, rowvar=False, bias=True)
+        sigma0 = float(np.max(np.sqrt(np.diag(np.atleast_2d(Sigma)))))
+        max_fevals = int(options["search_max_fun_evals"])
+        seed = _seed_or_draw(seed)
+        starts = [x0]
+        if n_starts > 1:  # the next best rows of the ranked set, in rank order
+            X_search = np.asarray(res.X_search, dtype=np.float64)
+            for j in res.order:
+                j = int(j)
+                if len(starts) >= n_starts or not np.isfinite(res.acq_fast[j]):
+                    break
+                if j != idx:
+                    starts.append(np.minimum(np.maximum(X_search[j if j < idx else j - 1], lb), ub))
+        starts = np.array(starts)
+        if device:
+            ctx = ctx_of(vp, ctx)
+            if ctx.device < 0:
+                raise _lib.NoDeviceError(_lib.E_NODEV, "refine(device=True) needs a gfx950 device (pyvbmc_amd has no CPU fallback)")
+            kind, y_max, tol_var, u, noise, use_xf = _scoring_args(acq_eval, gp, vp, function_logger, optim_state, ctx, D)
+            int_bits = _int_bits(integer_vars, D)
+            if int_bits:
+                _xf_flag(pt, ctx, D)
+            out = cmaes_resident(ctx, D, kind, y_max, tol_var, u, noise, use_xf, optim_state.get("lb_eps_orig"),
+                                 optim_state.get("ub_eps_orig"), starts, sigma0, lb, ub, int_bits=int_bits,
+                                 max_fevals=max_fevals, tol_fun=tol_fun, seed=seed)
+            runs = [SimpleNamespace(x_best=out.x_best[r], f_best=float(out.f_best[r]), f0=float(out.f0[r]), mean=out.mean[r],
+                                    sigma=float(out.sigma[r]), C=out.C[r], stats=out.stats[r]) for r in range(len(starts))]
+        else:
+            runs = [_cmaes.fmin(acq_batch, s, sigma0, lb, ub, max_fevals=max_fevals, tol_fun=tol_fun, seed=seed, run=r,
+                                evaluated=rounded) for r, s in enumerate(starts)]
+        stats = np.array([r.stats for r in runs], dtype=np.int64)
+        f_all = np.array([r.f_best for r in runs])
+        best_run = int(np.nanargmin(f_all)) if np.isfinite(f_all).any() else 0
+        x_opt, f_opt = np.reshape(runs[best_run].x_best, (1, D)), float(runs[best_run].f_best)
+    info = dict(stats=stats, runs=runs, best_run=best_run, lb=lb, ub=ub, tol_fun=tol_fun, sigma0=sigma0 if D > 1 else None)
+    if f_opt < f_val_old:  # :417-423
+        return SimpleNamespace(X_acq=np.array(x_opt, dtype=np.float64), idx_cache_acq=np.nan, f_val=f_opt, f_val_old=f_val_old,
+                               accepted=True, **info)
+    same.__dict__.update(info)
+    return same
+
+
+__all__ = ["get_search_points", "search", "refine", "cmaes_resident", "philox_plan", "put_points", "evaluate_resident", "sub_seed",
+           "mvn_factor", "SOURCES"]

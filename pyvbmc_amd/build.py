@@ -39,6 +39,8 @@ SOURCES = [
     "acq_is_mcmc.hip",
     "search.hip",
     "api_search.hip",
+    "cmaes.hip",
+    "api_cmaes.hip",
     "sample.hip",
     "transform.hip",
     "kde.hip",

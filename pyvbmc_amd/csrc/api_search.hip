@@ -35,10 +35,12 @@ constexpr int64_t kMaxLookup = (int64_t)1 << 28;
 
 // The copies a call queues read host memory of that call (the table, the parameters, the bounds, the caller's rows): a
 // call that fails after queueing some of them waits for the stream before that memory goes away.
+}  // namespace
 int search_fail_wait(vbmc_ctx* ctx, int rc) {
   if (ctx && ctx->device >= 0 && ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   return rc;
 }
+namespace {
 
 int search_fill_queue(vbmc_ctx* ctx, const char* who, int D, int n_src, const vbmc_search_source* src, const double* lb_D,
                      const double* ub_D, uint32_t int_bits, int use_xf, double* X_out) {
@@ -176,82 +178,104 @@ extern "C" int vbmc_search_put(vbmc_ctx* ctx, int64_t M, int D, const double* X_
   return search_fill_impl(ctx, "search_put", D, 1, &s, nullptr, nullptr, integer_bits, use_xf, nullptr);
 }
 
-static int search_eval_queue(vbmc_ctx* ctx, int kind, double y_max, double tol_gp_var, double u, int64_t n_noise,
-                             const double* X_rescaled_NxD, const double* sn2_new_N, const double* length_scale_D, int use_xf,
-                             const double* lb_eps_orig_D, const double* ub_eps_orig_D, double* acq_M, int64_t* order_M,
-                             double* X_sorted_MxD) {
+// ---- scoring a block of device rows: what vbmc_search_eval runs on the resident set and vbmc_search_cmaes
+// (api_cmaes.hip) on every generation's candidates.  The four steps are a call's order: check, list (the pieces go into
+// s.p.sc in front of the caller's own), upload (after predict_reserve: the hard bounds and the noise table, once per
+// call), rows (any number of times).
+
+int search_score_check(vbmc_ctx* ctx, const char* who, int kind, int64_t n_noise, const double* X_rescaled_NxD,
+                       const double* sn2_new_N, const double* length_scale_D, int use_xf, const double* lb_eps_orig_D,
+                       const double* ub_eps_orig_D, SearchScore& s) {
   if (!ctx || !lb_eps_orig_D || !ub_eps_orig_D) return VBMC_E_ARG;
   NEED_DEVICE(ctx);
-  if (kind < VBMC_ACQ_STD || kind > VBMC_ACQ_IS) return vbmc_fail(ctx, VBMC_E_UNSUP, "search_eval: unknown acquisition kind %d", kind);
-  if (!ctx->gp.set) return vbmc_fail(ctx, VBMC_E_ARG, "search_eval: GP not set");
-  const bool is_kind = kind == VBMC_ACQ_IS, noisy = is_kind || kind == VBMC_ACQ_NOISY;
-  const GpState& g = ctx->gp;
-  const int N = g.N, D = g.D, S = g.S;
-  if (!is_kind && !ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "search_eval: mixture not set");
-  if (!is_kind && ctx->D != D) return vbmc_fail(ctx, VBMC_E_ARG, "search_eval: GP/mixture D mismatch");
-  if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "search_eval: D=%d > 32 not supported", D);
-  const SearchState* st = (const SearchState*)ctx->search;
-  if (!st || st->D != D || (st->M > 0 && !st->d_X))
-    return vbmc_fail(ctx, VBMC_E_ARG, "search_eval: no search set for D=%d (vbmc_search_fill / vbmc_search_put)", D);
-  if (noisy && (n_noise < 1 || !X_rescaled_NxD || !sn2_new_N || !length_scale_D))
-    return vbmc_fail(ctx, VBMC_E_ARG, "search_eval: this acquisition needs X_rescaled, sn2_new and the length scale");
-  if (noisy && n_noise > ((int64_t)1 << 24)) return vbmc_fail(ctx, VBMC_E_UNSUP, "search_eval: more than 2^24 noise rows");
-  int64_t Na = 0;
+  if (kind < VBMC_ACQ_STD || kind > VBMC_ACQ_IS) return vbmc_fail(ctx, VBMC_E_UNSUP, "%s: unknown acquisition kind %d", who, kind);
+  if (!ctx->gp.set) return vbmc_fail(ctx, VBMC_E_ARG, "%s: GP not set", who);
+  s.kind = kind;
+  s.is_kind = kind == VBMC_ACQ_IS;
+  s.noisy = s.is_kind || kind == VBMC_ACQ_NOISY;
+  const int D = ctx->gp.D;
+  if (!s.is_kind && !ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "%s: mixture not set", who);
+  if (!s.is_kind && ctx->D != D) return vbmc_fail(ctx, VBMC_E_ARG, "%s: GP/mixture D mismatch", who);
+  if (D > 32) return vbmc_fail(ctx, VBMC_E_UNSUP, "%s: D=%d > 32 not supported", who, D);
+  if (s.noisy && (n_noise < 1 || !X_rescaled_NxD || !sn2_new_N || !length_scale_D))
+    return vbmc_fail(ctx, VBMC_E_ARG, "%s: this acquisition needs X_rescaled, sn2_new and the length scale", who);
+  if (s.noisy && n_noise > ((int64_t)1 << 24)) return vbmc_fail(ctx, VBMC_E_UNSUP, "%s: more than 2^24 noise rows", who);
+  s.n_noise = s.noisy ? n_noise : 0;
+  s.Na = 0;
   int rc = 0;
-  if (is_kind && (rc = acq_is_need(ctx, "search_eval", &Na))) return rc;
-  XfView t;
-  if (use_xf && (rc = xf_need(ctx, 0, D, "search_eval", t))) return rc;
-  const int64_t M = st->M;
-  if (M == 0) return VBMC_OK;
-  if (noisy && 2 * ((n_noise + 63) / 64) * M > kMaxLookup)
-    return vbmc_fail(ctx, VBMC_E_UNSUP, "search_eval: %lld points against %lld noise rows: the lookup's scratch is not batched",
-                     (long long)M, (long long)n_noise);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // The batch plans of vbmc_acq_eval / vbmc_acq_is_eval, then this call's own pieces:
-  //   dens (mb) or Kx (mb x N) | T (mb x Na) | as [S][mb];  res (3 mb);  sn2 (M);
-  //   acq (M) | order (M int64) | sorted points (M x D): one block, copied out in one piece;
-  //   keys (P uint64) | rows (P uint32);  hard bounds (2 D);
+  if (s.is_kind && (rc = acq_is_need(ctx, who, &s.Na))) return rc;
+  s.use_xf = use_xf;
+  if (use_xf && (rc = xf_need(ctx, 0, D, who, s.t))) return rc;
+  s.X_rescaled = X_rescaled_NxD;
+  s.sn2_new = sn2_new_N;
+  s.length_scale = length_scale_D;
+  s.lb_eps = lb_eps_orig_D;
+  s.ub_eps = ub_eps_orig_D;
+  return 0;
+}
+
+int search_score_list(vbmc_ctx* ctx, const char* who, int64_t M, SearchScore& s) {
+  if (s.noisy && 2 * ((s.n_noise + 63) / 64) * M > kMaxLookup)
+    return vbmc_fail(ctx, VBMC_E_UNSUP, "%s: %lld points against %lld noise rows: the lookup's scratch is not batched", who,
+                     (long long)M, (long long)s.n_noise);
+  // The batch plans of vbmc_acq_eval / vbmc_acq_is_eval, then the scoring's own pieces:
+  //   dens (mb) or Kx (mb x N) | T (mb x Na) | as [S][mb];  res (3 mb);  sn2 (M);  hard bounds (2 D);
   //   noise lookup: ell (D) | set / ell (M x D) | X_rescaled (Nn x D) | sn2_new (Nn) | centre (D) | column sums of both
   //   sets | tile minima and indices (2 tiles M) | argmin (M int64)
-  PredictPlan p;
-  if (is_kind) predict_plan(ctx, M, (int64_t)1 << 26, (int64_t)S * N + N + Na, 16384, p);
+  const GpState& g = ctx->gp;
+  const int N = g.N, D = g.D, S = g.S;
+  PredictPlan& p = s.p;
+  if (s.is_kind) predict_plan(ctx, M, (int64_t)1 << 26, (int64_t)S * N + N + s.Na, 16384, p);
   else predict_plan(ctx, M, (int64_t)1 << 27, (int64_t)S * N, 65536, p);
-  const size_t mb = (size_t)p.mb, Ms = (size_t)M, Nn = noisy ? (size_t)n_noise : 0, P = (size_t)search_sort_len(M);
-  const size_t nt = (Nn + 63) / 64;
-  const auto p_dens = p.sc.add(is_kind ? 0 : mb);
-  const auto p_Kx = p.sc.add(is_kind ? mb * N : 0), p_T = p.sc.add(is_kind ? mb * (size_t)Na : 0), p_as = p.sc.add(is_kind ? S * mb : 0);
-  const auto p_res = p.sc.add(3 * mb), p_sn2 = p.sc.add(noisy ? Ms : 0);
-  const auto p_acq = p.sc.add(Ms);
-  const auto p_ord = p.sc.add<int64_t>(Ms);
-  const auto p_Xs = p.sc.add(Ms * D);
-  const auto p_keys = p.sc.add<uint64_t>(P);
-  const auto p_idx = p.sc.add<uint32_t>(P);
-  const auto p_bnd = p.sc.add(2 * (size_t)D);
-  const auto p_ell = p.sc.add(noisy ? (size_t)D : 0), p_xsc = p.sc.add(Nn ? Ms * D : 0), p_b = p.sc.add(Nn * D);
-  const auto p_tab = p.sc.add(Nn), p_cen = p.sc.add(noisy ? (size_t)D : 0);
-  const auto p_part = p.sc.add(noisy ? 2 * (size_t)search_sum_blocks * D : 0), p_pmin = p.sc.add(2 * nt * (noisy ? Ms : 0));
-  const auto p_am = p.sc.add<int64_t>(noisy ? Ms : 0);
-  const size_t n_out = (2 + (size_t)D) * Ms;
-  if ((rc = predict_reserve(ctx, p, 0))) return rc;
-  if ((rc = ensure_pinned(ctx, n_out))) return rc;
-  double *d_res = p.sc.ptr(p_res), *d_sn2 = p.sc.ptr(p_sn2), *d_acq = p.sc.ptr(p_acq), *d_Xs = p.sc.ptr(p_Xs);
-  double* d_bnd = p.sc.ptr(p_bnd);
-  int64_t* d_ord = p.sc.ptr(p_ord);
-  uint64_t* d_keys = p.sc.ptr(p_keys);
-  uint32_t* d_idx = p.sc.ptr(p_idx);
-  std::vector<double> bnd(lb_eps_orig_D, lb_eps_orig_D + D);
-  bnd.insert(bnd.end(), ub_eps_orig_D, ub_eps_orig_D + D);
-  HIP_TRY(ctx, hipMemcpyAsync(d_bnd, bnd.data(), sizeof(double) * 2 * D, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = timing_begin(ctx, T_SEARCH_EVAL))) return rc;
-  if (noisy) {
+  const bool is_kind = s.is_kind, noisy = s.noisy;
+  const size_t mb = (size_t)p.mb, Ms = (size_t)M, Nn = (size_t)s.n_noise, nt = (Nn + 63) / 64;
+  s.M = M;
+  s.p_dens = p.sc.add(is_kind ? 0 : mb);
+  s.p_Kx = p.sc.add(is_kind ? mb * N : 0);
+  s.p_T = p.sc.add(is_kind ? mb * (size_t)s.Na : 0);
+  s.p_as = p.sc.add(is_kind ? S * mb : 0);
+  s.p_res = p.sc.add(3 * mb);
+  s.p_sn2 = p.sc.add(noisy ? Ms : 0);
+  s.p_bnd = p.sc.add(2 * (size_t)D);
+  s.p_ell = p.sc.add(noisy ? (size_t)D : 0);
+  s.p_xsc = p.sc.add(Nn ? Ms * D : 0);
+  s.p_b = p.sc.add(Nn * D);
+  s.p_tab = p.sc.add(Nn);
+  s.p_cen = p.sc.add(noisy ? (size_t)D : 0);
+  s.p_part = p.sc.add(noisy ? 2 * (size_t)search_sum_blocks * D : 0);
+  s.p_pmin = p.sc.add(2 * nt * (noisy ? Ms : 0));
+  s.p_am = p.sc.add<int64_t>(noisy ? Ms : 0);
+  return 0;
+}
+
+int search_score_upload(vbmc_ctx* ctx, SearchScore& s) {
+  const int D = ctx->gp.D;
+  const size_t Nn = (size_t)s.n_noise;
+  s.bnd.assign(s.lb_eps, s.lb_eps + D);
+  s.bnd.insert(s.bnd.end(), s.ub_eps, s.ub_eps + D);
+  HIP_TRY(ctx, hipMemcpyAsync(s.p.sc.ptr(s.p_bnd), s.bnd.data(), sizeof(double) * 2 * D, hipMemcpyHostToDevice, ctx->stream));
+  if (s.noisy) {
+    HIP_TRY(ctx, hipMemcpyAsync(s.p.sc.ptr(s.p_ell), s.length_scale, sizeof(double) * D, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.p.sc.ptr(s.p_b), s.X_rescaled, sizeof(double) * Nn * D, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.p.sc.ptr(s.p_tab), s.sn2_new, sizeof(double) * Nn, hipMemcpyHostToDevice, ctx->stream));
+  }
+  return 0;
+}
+
+int search_score_rows(vbmc_ctx* ctx, const SearchScore& s, const double* d_X, int64_t M, double y_max, double tol_gp_var,
+                      double u, double* d_acq) {
+  const PredictPlan& p = s.p;
+  const int D = ctx->gp.D;
+  const size_t mb = (size_t)p.mb;
+  const int64_t n_noise = s.n_noise;
+  double *d_res = p.sc.ptr(s.p_res), *d_sn2 = p.sc.ptr(s.p_sn2), *d_bnd = p.sc.ptr(s.p_bnd);
+  int rc = 0;
+  if (s.noisy) {
     // sn2_new[argmin_n |Xs / ell - X_rescaled_n|^2]   (abstract_acq_fcn.py:244-256)
-    double *d_ell = p.sc.ptr(p_ell), *d_xsc = p.sc.ptr(p_xsc), *d_b = p.sc.ptr(p_b), *d_tab = p.sc.ptr(p_tab);
-    double *d_cen = p.sc.ptr(p_cen), *d_part = p.sc.ptr(p_part), *d_pmin = p.sc.ptr(p_pmin);
-    int64_t* d_am = p.sc.ptr(p_am);
-    HIP_TRY(ctx, hipMemcpyAsync(d_ell, length_scale_D, sizeof(double) * D, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_b, X_rescaled_NxD, sizeof(double) * Nn * D, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_tab, sn2_new_N, sizeof(double) * Nn, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = launch_search_scale(ctx, st->d_X, M, D, d_ell, d_xsc))) return rc;
+    double *d_ell = p.sc.ptr(s.p_ell), *d_xsc = p.sc.ptr(s.p_xsc), *d_b = p.sc.ptr(s.p_b), *d_tab = p.sc.ptr(s.p_tab);
+    double *d_cen = p.sc.ptr(s.p_cen), *d_part = p.sc.ptr(s.p_part), *d_pmin = p.sc.ptr(s.p_pmin);
+    int64_t* d_am = p.sc.ptr(s.p_am);
+    if ((rc = launch_search_scale(ctx, d_X, M, D, d_ell, d_xsc))) return rc;
     if ((rc = launch_search_colsum(ctx, d_xsc, M, D, d_part))) return rc;
     if ((rc = launch_search_colsum(ctx, d_b, n_noise, D, d_part + (size_t)search_sum_blocks * D))) return rc;
     if ((rc = launch_search_centre(ctx, d_part, M, d_part + (size_t)search_sum_blocks * D, n_noise, D, d_cen))) return rc;
@@ -260,17 +284,57 @@ static int search_eval_queue(vbmc_ctx* ctx, int kind, double y_max, double tol_g
   }
   for (int64_t o = 0; o < M; o += p.mb) {
     const int64_t m = (M - o) < p.mb ? (M - o) : p.mb;
-    const double* d_xs = st->d_X + o * D;
-    if (is_kind) {
-      rc = launch_acq_is(ctx, p, m, d_xs, d_sn2 + o, u, p.sc.ptr(p_Kx), p.sc.ptr(p_T), p.sc.ptr(p_as), d_res);
+    const double* d_xs = d_X + o * D;
+    if (s.is_kind) {
+      rc = launch_acq_is(ctx, p, m, d_xs, d_sn2 + o, u, p.sc.ptr(s.p_Kx), p.sc.ptr(s.p_T), p.sc.ptr(s.p_as), d_res);
       if (!rc) rc = launch_search_is_finish(ctx, m, tol_gp_var, d_res + mb, d_res);
     } else {
-      rc = launch_acq_closed(ctx, p, m, d_xs, noisy ? d_sn2 + o : nullptr, kind, y_max, tol_gp_var, p.sc.ptr(p_dens), d_res);
+      rc = launch_acq_closed(ctx, p, m, d_xs, s.noisy ? d_sn2 + o : nullptr, s.kind, y_max, tol_gp_var, p.sc.ptr(s.p_dens), d_res);
     }
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(d_acq + o, d_res, sizeof(double) * m, hipMemcpyDeviceToDevice, ctx->stream));
   }
-  if ((rc = launch_search_mask(ctx, st->d_X, M, D, use_xf ? &t : nullptr, d_bnd, d_bnd + D, d_acq))) return rc;
+  return launch_search_mask(ctx, d_X, M, D, s.use_xf ? &s.t : nullptr, d_bnd, d_bnd + D, d_acq);
+}
+
+int search_set_rows_cap() { return (int)kMaxRows; }
+
+static int search_eval_queue(vbmc_ctx* ctx, int kind, double y_max, double tol_gp_var, double u, int64_t n_noise,
+                             const double* X_rescaled_NxD, const double* sn2_new_N, const double* length_scale_D, int use_xf,
+                             const double* lb_eps_orig_D, const double* ub_eps_orig_D, double* acq_M, int64_t* order_M,
+                             double* X_sorted_MxD) {
+  SearchScore s;
+  int rc = search_score_check(ctx, "search_eval", kind, n_noise, X_rescaled_NxD, sn2_new_N, length_scale_D, use_xf,
+                              lb_eps_orig_D, ub_eps_orig_D, s);
+  if (rc) return rc;
+  const int D = ctx->gp.D;
+  const SearchState* st = (const SearchState*)ctx->search;
+  if (!st || st->D != D || (st->M > 0 && !st->d_X))
+    return vbmc_fail(ctx, VBMC_E_ARG, "search_eval: no search set for D=%d (vbmc_search_fill / vbmc_search_put)", D);
+  const int64_t M = st->M;
+  if (M == 0) return VBMC_OK;
+  if ((rc = search_score_list(ctx, "search_eval", M, s))) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // behind the scoring's pieces, this call's own:
+  //   acq (M) | order (M int64) | sorted points (M x D): one block, copied out in one piece;
+  //   keys (P uint64) | rows (P uint32)
+  PredictPlan& p = s.p;
+  const size_t Ms = (size_t)M, P = (size_t)search_sort_len(M);
+  const auto p_acq = p.sc.add(Ms);
+  const auto p_ord = p.sc.add<int64_t>(Ms);
+  const auto p_Xs = p.sc.add(Ms * D);
+  const auto p_keys = p.sc.add<uint64_t>(P);
+  const auto p_idx = p.sc.add<uint32_t>(P);
+  const size_t n_out = (2 + (size_t)D) * Ms;
+  if ((rc = predict_reserve(ctx, p, 0))) return rc;
+  if ((rc = ensure_pinned(ctx, n_out))) return rc;
+  double *d_acq = p.sc.ptr(p_acq), *d_Xs = p.sc.ptr(p_Xs);
+  int64_t* d_ord = p.sc.ptr(p_ord);
+  uint64_t* d_keys = p.sc.ptr(p_keys);
+  uint32_t* d_idx = p.sc.ptr(p_idx);
+  if ((rc = timing_begin(ctx, T_SEARCH_EVAL))) return rc;
+  if ((rc = search_score_upload(ctx, s))) return rc;
+  if ((rc = search_score_rows(ctx, s, st->d_X, M, y_max, tol_gp_var, u, d_acq))) return rc;
   if ((rc = timing_end(ctx, T_SEARCH_EVAL))) return rc;
   if ((rc = timing_begin(ctx, T_SEARCH_SORT))) return rc;
   if ((rc = launch_search_sort(ctx, d_acq, M, d_keys, d_idx))) return rc;

@@ -11,6 +11,7 @@
 
 #include "../../include/vbmc_hip.h"
 #include "scratch.h"
+#include "transform.h"
 
 struct ncclComm;
 
@@ -146,9 +147,9 @@ struct ElboScratch {
 // The timed intervals of vbmc_last_kernel_ms (the numbers are ABI): entmc, glj, pdf, predict, elbo, predict's variance
 // product (timing level 2 only), the GP posterior's factorisation, the MCMC chains of vbmc_is_mcmc, one chunk of
 // vbmc_gp_lml (factorisation and gradient kernels), the three phases of the acquisition search (vbmc_search_fill's
-// launches; vbmc_search_eval's acquisition and mask; its sort and gather), all the rounds of one vbmc_gp_hyp_sample
+// launches; vbmc_search_eval's acquisition and mask; its sort and gather), all the rounds of one vbmc_gp_hyp_sample, all the rounds of one vbmc_search_cmaes
 enum TimingPair { T_ENTMC = 0, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML, T_SEARCH_FILL,
-                  T_SEARCH_EVAL, T_SEARCH_SORT, T_GP_HYP, T_COUNT };
+                  T_SEARCH_EVAL, T_SEARCH_SORT, T_GP_HYP, T_SEARCH_CMAES, T_COUNT };
 
 struct vbmc_ctx {
   int device = 0;
@@ -260,6 +261,7 @@ struct vbmc_ctx {
   int opt_is_mcmc_threads = 512;  // workgroup size of vbmc_is_mcmc's chains: 256, 512 or 768 (acq_is_mcmc.hip)
   int opt_gp_lml_chunk = 0;       // vbmc_gp_lml: n > 0 = candidates per chunk (test hook); 0 = the largest under the byte cap
   int opt_gp_hyp_rounds = 4;      // vbmc_gp_hyp_sample: rounds queued between two reads of the unfinished-chain count (test hook)
+  int opt_cmaes_rounds = 8;       // vbmc_search_cmaes: rounds queued between two reads of the count of runs not yet stopped
   void (*release_cb)(void*) = nullptr;  // vbmc_set_release_callback
   void* release_cb_user = nullptr;
   int opt_adam_fused = 1;     // the optimiser loop as one launch per batch where its shape applies (adam_fused.hip)
@@ -792,6 +794,57 @@ int64_t search_sort_len(int64_t M);
 int launch_search_sort(vbmc_ctx* ctx, const double* d_acq, int64_t M, uint64_t* d_keys, uint32_t* d_idx);
 int launch_search_gather(vbmc_ctx* ctx, const double* d_X, const uint32_t* d_idx, int64_t M, int D, int64_t* d_order,
                          double* d_Xs);
+// api_search.hip: scoring a block of device rows with the acquisition -- the noise lookup, launch_acq_closed / launch_acq_is
+// with launch_search_is_finish, launch_search_mask -- for vbmc_search_eval (the resident set) and vbmc_search_cmaes (a
+// generation's candidates).  A call's order: check (the arguments, before anything is launched), list (the pieces of
+// at most M rows into s.p.sc, the caller's own pieces behind them), predict_reserve(ctx, s.p, 0), upload (the hard
+// bounds and the noise table, once), rows (per set: scale, column sums, centre, sq_dist argmin, take, the acquisition in
+// batches, the mask; d_acq[0 .. m) written).
+struct SearchScore {
+  int kind = 0, use_xf = 0;
+  bool is_kind = false, noisy = false;
+  int64_t Na = 0, n_noise = 0, M = 0;
+  XfView t;
+  const double *X_rescaled = nullptr, *sn2_new = nullptr, *length_scale = nullptr, *lb_eps = nullptr, *ub_eps = nullptr;
+  std::vector<double> bnd;  // host source of the hard bounds' upload
+  PredictPlan p;
+  Piece<> p_dens, p_Kx, p_T, p_as, p_res, p_sn2, p_bnd, p_ell, p_xsc, p_b, p_tab, p_cen, p_part, p_pmin;
+  Piece<int64_t> p_am;
+};
+int search_score_check(vbmc_ctx* ctx, const char* who, int kind, int64_t n_noise, const double* X_rescaled_NxD,
+                       const double* sn2_new_N, const double* length_scale_D, int use_xf, const double* lb_eps_orig_D,
+                       const double* ub_eps_orig_D, SearchScore& s);
+int search_score_list(vbmc_ctx* ctx, const char* who, int64_t M, SearchScore& s);
+int search_score_upload(vbmc_ctx* ctx, SearchScore& s);
+int search_score_rows(vbmc_ctx* ctx, const SearchScore& s, const double* d_X, int64_t m, double y_max, double tol_gp_var,
+                      double u, double* d_acq);
+int search_set_rows_cap();                       // the search set's row cap (2^20)
+int search_fail_wait(vbmc_ctx* ctx, int rc);     // a failed call waits for the copies it queued from its own host memory
+// cmaes.hip: the lockstep CMA-ES runs of vbmc_search_cmaes.  One advance launch moves every run on by one generation:
+// run r consumes val[r lam .. r lam + lam) (round 1: val[r], the start's value) and writes its next lam candidates,
+// rounded, into rows[r lam ..] (round 0: the start into rows[r]).  All pointers device memory; the constants are the
+// host's float64 values (api_cmaes.hip).
+struct CmaesArgs {
+  int R = 0, D = 0, lam = 0, mu = 0, hist = 0;
+  long long max_fevals = 0;
+  uint64_t seed = 0;
+  double tol_fun = 0.0, tol_x = 0.0;  // tol_x <= 0: 1e-11 sigma0 of the run
+  // 1 - c_sigma, sqrt(c_sigma (2 - c_sigma) mu_eff), (1 - c_sigma)^2, (1.4 + 2 / (D + 1)) chi_D, 1 - c_c,
+  // sqrt(c_c (2 - c_c) mu_eff), 1 - c_1 - c_mu, c_1, c_mu, c_c (2 - c_c), c_sigma / d_sigma, 1 / chi_D
+  double one_cs = 0, a_ps = 0, q_cs = 0, hs_thresh = 0, one_cc = 0, a_pc = 0, c_old = 0, c1 = 0, cmu = 0, cc2 = 0, cs_ds = 0, inv_chi = 0;
+  const double* w = nullptr;  // [mu]
+  const double *x0 = nullptr, *sigma0 = nullptr, *lb = nullptr, *ub = nullptr;  // [R][D], [R], [D], [D]
+  uint32_t int_bits = 0;
+  int has_xf = 0;
+  XfView t;
+  const double* val = nullptr;  // [R lam]
+  double* rows = nullptr;       // [R lam][D]
+  double* state = nullptr;      // [R][CmaState(D, lam, hist).total], zeroed by the caller: a zeroed state is a run at its start
+  double *x_best = nullptr, *f_best = nullptr, *f0 = nullptr, *mean = nullptr, *sigma = nullptr, *C = nullptr;
+  long long* stats = nullptr;   // [R][4]: generations, evaluations, stop reason, generation of the best
+};
+int launch_cmaes_advance(vbmc_ctx* ctx, const CmaesArgs& a);
+int launch_cmaes_count(vbmc_ctx* ctx, const CmaesArgs& a, int* d_count);  // *d_count = runs not yet stopped
 // acq_is_mcmc.hip: the S slice-sampling chains of active_importance_sampling's step 2, one workgroup each, on ctx->stream
 // (all pointers device memory; d_invalid [S] zeroed by the caller), and the dynamic LDS a workgroup of `threads` needs
 size_t is_mcmc_lds_bytes(int N, int threads);

@@ -18,6 +18,9 @@
 //                                      draw i of chain s of GP hyper-parameter sampling (gp_hyp.hip), under that call's seed
 //     c = (r_lo, r_hi, pair, 7)        normals of dimensions 2 pair, 2 pair + 1 of row r of an affine-Gaussian or box-normal
 //                                      source of the acquisition search (search.hip), under the source's own key
+//     c = (n_lo, n_hi, pair, 8)        normals of dimensions 2 pair, 2 pair + 1 of candidate i of generation g of a CMA-ES
+//                                      run of the acquisition search's refinement (cmaes.hip), n = g lambda + i, under the
+//                                      run's own key
 // oracle/sample_ref.py restates both.  Component choice: inverse CDF of the weights
 // (np.random.choice(p=w), :316-319); with balance_flag the first sum_k floor(w_k N) samples
 // are split exactly according to the weights and the remaining ones are drawn from the

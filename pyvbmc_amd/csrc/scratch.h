@@ -36,3 +36,27 @@ struct Scratch {
     return base ? (T*)(base + p.off) : nullptr;
   }
 };
+
+// The state of one CMA-ES run of vbmc_search_cmaes in the search workspace (cmaes.hip), offsets in doubles: the head
+// (phase, stop reason, counters: 8 doubles) | p_sigma, p_c, 1 / diag L (D each) | L (D x D) | the generation's points,
+// steps y and repaired normals z' (lambda x D each) | the ring of generation-best values (hist).  The mean, sigma, C,
+// the best point and value and the stats are the call's outputs and live in its result block.
+struct CmaState {
+  size_t head = 0, ps = 0, pc = 0, rdiag = 0, L = 0, X = 0, Y = 0, Z = 0, ring = 0, total = 0;
+#if defined(__HIPCC__)
+  __host__ __device__
+#endif
+  CmaState(int D, int lam, int hist) {
+    const size_t d = (size_t)D, ld = (size_t)lam * d;
+    size_t o = 8;
+    ps = o; o += d;
+    pc = o; o += d;
+    rdiag = o; o += d;
+    L = o; o += d * d;
+    X = o; o += ld;
+    Y = o; o += ld;
+    Z = o; o += ld;
+    ring = o; o += (size_t)hist;
+    total = o;
+  }
+};

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Outputs of the entry points that list their device scratch through csrc/scratch.h and are not in tools/gp_dense_dump.py
 -- the sampler and its consumers (kl_div, moments, mtv, mode), the transformer, pdf_orig, kde_1d, the importance-sampling
-preparation and its MCMC step, neg_elcbo_batch, the device-built GP posterior and its append -- for a fixed list of small
+preparation and its MCMC step, neg_elcbo_batch, the device-built GP posterior and its append, GP hyper-parameter sampling,
+the acquisition search's evaluation of a resident set and its CMA-ES refinement -- for a fixed list of small
 cases, written to an .npz: run once per library (VBMC_HIP_LIB names the one to load, as in tools/ab_libs.sh) and compare.
     VBMC_HIP_LIB=$PWD/variants/libvbmc_parent.so python tools/entry_dump.py parent.npz
     python tools/entry_dump.py new.npz
@@ -216,6 +217,44 @@ def main(out):
                                    st.ctypes.data_as(C.POINTER(C.c_int64)), inv.ctypes.data_as(C.POINTER(C.c_int32))))
     for k, v in zip(("samples", "log_post", "log_priors", "stats", "invalid"), (smp, lpo, lpr, st, inv)):
         res[f"gp_hyp_sample/{k}"] = v
+    # ---- vbmc_search_put / vbmc_search_eval on 300 resident points, every kind; then vbmc_search_cmaes, whose scoring
+    # is the same code (a library from before that entry point: the search arrays alone)
+    r3 = np.random.default_rng(2025)
+    D, K, N, S, M = 3, 2, 65, 2, 300
+    set_mixture(mixture(r3, D, K), D, K)
+    set_transformer(0, D, 0.0)
+    upload_gp(make_gp(ctx, r3, N, D, S), ctx)
+    Xs = f64(0.8 * r3.standard_normal((M, D)))
+    ell, Xr, sn2n = f64(0.8 + 0.3 * r3.random(D)), f64(r3.standard_normal((N, D))), f64(0.01 + r3.random(N))
+    lbe, ube = f64([-np.inf, -2.5, -3.5]), f64([np.inf, 3.5, 4.5])
+    Na = 40
+    Xa, fs2a = f64(r3.standard_normal((Na, D))), f64(0.5 + r3.random((Na, S)))
+    ctx.check(L.vbmc_acq_is_build(h, Na, p(Xa), 0, p(fs2a), None, None, None))
+    ctx.check(L.vbmc_search_put(h, M, D, p(Xs), 1 << 1, 1))
+    for kind in range(5):
+        for tol in (0.0, 0.05):
+            noisy = kind >= 3
+            acq, order, Xo = np.empty(M), np.empty(M, dtype=np.int64), np.empty((M, D))
+            ctx.check(L.vbmc_search_eval(h, kind, 0.3, tol, 0.6744897501960817, N if noisy else 0, p(Xr) if noisy else None,
+                                         p(sn2n) if noisy else None, p(ell) if noisy else None, 1, p(lbe), p(ube), p(acq),
+                                         order.ctypes.data_as(C.POINTER(C.c_int64)), p(Xo)))
+            acq[np.isnan(acq)] = -12345.0  # (np.array_equal could not compare NaN)
+            for k, v in zip(("acq", "order", "X_sorted"), (acq, order, Xo)):
+                res[f"search/k{kind}_t{tol}/{k}"] = v
+    if hasattr(L, "vbmc_search_cmaes"):
+        R = 3
+        x0 = f64(0.3 * r3.standard_normal((R, D)))
+        for kind in (1, 3, 4):
+            noisy = kind >= 3
+            opts = _lib.CmaesOpts(0, 1 + 7 * 12, 1e-2, 0.0, 99)
+            o = [np.empty((R, D)), np.empty(R), np.empty(R), np.empty((R, D)), np.empty(R), np.empty((R, D, D))]
+            st = np.zeros((R, 4), dtype=np.int64)
+            ctx.check(L.vbmc_search_cmaes(h, kind, 0.3, 0.0, 0.6744897501960817, N if noisy else 0, p(Xr) if noisy else None,
+                                          p(sn2n) if noisy else None, p(ell) if noisy else None, 1, p(lbe), p(ube), R, p(x0),
+                                          p(f64(np.full(R, 0.5))), p(f64(np.full(D, -2.0))), p(f64(np.full(D, 2.0))), 1 << 1,
+                                          C.byref(opts), *[p(a) for a in o], st.ctypes.data_as(C.POINTER(C.c_int64))))
+            for k, v in zip(("x_best", "f_best", "f0", "mean", "sigma", "C", "stats"), o + [st]):
+                res[f"search_cmaes/k{kind}/{k}"] = v
     ctx.close()
     nans = sorted(k for k, v in res.items() if np.asarray(v).dtype.kind == "f" and np.isnan(v).any())
     assert not nans, f"NaN in {nans}: np.array_equal could not compare them"
