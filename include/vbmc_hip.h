@@ -928,6 +928,51 @@ int vbmc_mixture_mode(vbmc_ctx* ctx, int n_opts, int orig_flag, int64_t n, const
                       uint64_t seed, int max_iter, double step_tol, double* x_D, double* f_out,
                       double* rec_Rx5, double* pts_RxD, double* ys_RxD);
 
+/* ---- input warping / rotoscaling (whitening/whitening.py:7-375) ----
+ *
+ * The composed map "old inference space -> original space -> new inference space" on the device.  Transformer slot 0
+ * holds the OLD transformer, slot 1 the NEW one (vbmc_set_transformer), both of dimension D <= 32 (VBMC_E_UNSUP above,
+ * before any launch).  FP64 throughout; every reduction runs in a fixed order, so a call is bit-reproducible.  A `source`
+ * argument says which space the input points are in:
+ *   VBMC_WARP_FROM_OLD   slot 0's inference space:  y = new(old^-1(x))          (needs both slots)
+ *   VBMC_WARP_FROM_ORIG  the original space:        y = new(x)                  (slot 1 only)
+ *   VBMC_WARP_IN_NEW     slot 1's inference space:  y = x (for the log-Jacobian at a given point; slot 1 only) */
+enum { VBMC_WARP_FROM_OLD = 0, VBMC_WARP_FROM_ORIG = 1, VBMC_WARP_IN_NEW = 2 };
+
+/* n points mapped as `source` says: warp_input's re-map of the training set (:191-200) and of the search cache
+ * (:221-223), the dy / dy_old terms of warp_gp_and_vp (:309-313, :331-332, :369-370).  Outputs, all nullable:
+ * y_NxD, lj_new_N = log|det J| of slot 1 at y, lj_old_N = log|det J| of slot 0 at x (VBMC_WARP_FROM_OLD only:
+ * VBMC_E_ARG otherwise).  n = 0 returns at once, nothing launched. */
+int vbmc_warp_points(vbmc_ctx* ctx, int D, int64_t n, int source, const double* x_NxD, double* y_NxD, double* lj_new_N,
+                     double* lj_old_N);
+
+/* unscent_warp (:7-77) with the warp fixed to new(old^-1(.)): base points x_NxD, scales sigma (sigma_rows x D,
+ * sigma_rows = n or 1: one row is broadcast, :50-53).  Per base point the U = 2 D + 1 sigma points x, x +- sqrt(D)
+ * sigma_d e_d are warped; mean_NxD is their mean and std_NxD their ddof = 1 standard deviation, taken in two passes
+ * about the mean, both summed in the order u = 0 .. U - 1.  pts_UxNxD (nullable): the warped points in the
+ * reference's layout.  n >= 1; sigma_rows other than 1 or n -> VBMC_E_ARG. */
+int vbmc_warp_unscent(vbmc_ctx* ctx, int D, int64_t n, const double* x_NxD, int64_t sigma_rows, const double* sigma,
+                      double* mean_NxD, double* std_NxD, double* pts_UxNxD);
+
+/* The GP branch of warp_gp_and_vp (:296-313) for all S hyper-parameter samples in one launch: per sample s and
+ * training point X_n the unscented warp with ell_s = exp(hyp_SxP[s][0 .. D)) (the host's libm), then
+ * logell_SxD[s] = mean_n log(ell_new) (:303).  Also mean_n of dy = log|det J| of slot 1 at new(old^-1(X_n)) and of
+ * dy_old = log|det J| of slot 0 at X_n (dy_mean, dy_old_mean: one double each, nullable; ConstantMean, :309-313).
+ * The means over n are sums in a fixed order divided by N.  N >= 1, S >= 1, P >= D; a state of more than 2^27 doubles
+ * -> VBMC_E_UNSUP. */
+int vbmc_warp_gp(vbmc_ctx* ctx, int D, int N, int S, int P, const double* X_NxD, const double* hyp_SxP,
+                 double* logell_SxD, double* dy_mean, double* dy_old_mean);
+
+/* warp_input's box statistics (:168-180, :208-219): n uniform draws in the box [lo_D, hi_D], u (hi - lo) + lo, mapped
+ * as `source` says.  The uniforms u_NxD are the caller's (np.random.rand(n, D)), or NULL = drawn on the device: draw i's
+ * dimensions 2 p, 2 p + 1 are the two 53-bit uniforms of Philox block (i, p, stream 9) under `seed` (the streams are
+ * listed in csrc/sample.hip).  mode 0: out_2xD = the 0.05 and 0.95 quantiles per dimension by np.quantile's default rule
+ * (linear interpolation between the exact order statistics: the columns are sorted); mode 1: the minimum and maximum.
+ * sorted_Dxn (nullable, mode 0): the sorted columns.  1 <= n <= 2^30; a non-finite mapped value -> VBMC_E_NONFINITE
+ * (mode 0). */
+int vbmc_warp_box(vbmc_ctx* ctx, int D, int64_t n, int source, const double* lo_D, const double* hi_D,
+                  const double* u_NxD, uint64_t seed, int mode, double* out_2xD, double* sorted_Dxn);
+
 /* ---- multi-GPU: one process per GPU, one collective ---------- */
 
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by

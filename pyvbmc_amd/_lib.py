@@ -261,6 +261,10 @@ SIGNATURES = {
                            C.POINTER(C.c_int64)]),
     "vbmc_mixture_mode": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int64, _dp, C.c_uint64, C.c_int, C.c_double, _dp, _dp,
                                     _dp, _dp, _dp]),
+    "vbmc_warp_points": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, _dp, _dp, _dp, _dp]),
+    "vbmc_warp_unscent": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
+    "vbmc_warp_gp": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "vbmc_warp_box": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, _dp, _dp, _dp, C.c_uint64, C.c_int, _dp, _dp]),
     "vbmc_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),
     "vbmc_comm_init": (C.c_int, [_vp, C.POINTER(C.c_uint8), C.c_int, C.c_int]),
     "vbmc_comm_destroy": (C.c_int, [_vp]),

@@ -45,6 +45,8 @@ SOURCES = [
     "transform.hip",
     "kde.hip",
     "mode.hip",
+    "warp.hip",
+    "api_warp.hip",
     "comm.hip",
     "host_randn.hip",
     "device_randn.hip",

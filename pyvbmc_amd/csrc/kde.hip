@@ -22,14 +22,12 @@
 #include <cstring>
 #include <vector>
 
+#include "colsort.h"  // kThreads, kChunk, KdeSrc, the keys, kde_sort_chunks_kernel, column_merge
 #include "common.h"
 #include "transform.h"
 
 namespace {
 
-constexpr int kThreads = 512;          // kde_column_kernel / kde_sort_chunks_kernel (2 waves / SIMD: 256 VGPRs)
-constexpr int kWaves = kThreads / 64;
-constexpr int kChunk = 8192;           // keys per LDS sort chunk (64 KiB)
 constexpr int kMaxMesh = 1 << 14;      // n <= 2^14: the FFT buffer is n doubles (128 KiB of LDS)
 constexpr int kMtvMesh = 1 << 13;     // nkde = 2**13 (:976); the spline needs 2 n doubles of LDS
 constexpr int kSegPts = 100000;        // mtv: points per linspace segment (:1024)
@@ -44,14 +42,6 @@ enum { CP_X0, CP_XL, CP_STEP, CP_DX, CP_BW, CP_T, CP_DELTA, CP_LOWER, CP_N };
 enum { KF_SCOTT = 1, KF_NONFINITE = 2, KF_DEGENERATE = 4, KF_ROOT_STUCK = 8 };
 // bound modes
 enum { BND_KDE = 0, BND_MTV = 1 };
-
-struct KdeSrc {
-  const double* x[2];
-  int64_t n[2];
-  int64_t rs[2];  // row stride (elements)
-  int64_t cs[2];  // column stride
-  int ncol0;      // columns of side 0
-};
 
 // the constants of _fixed_point per order s = 2 .. 7 (kde_1d.py:47-73), from the host's libm
 struct FpConsts {
@@ -78,73 +68,6 @@ struct KdeArgs {
   double* colp;        // ncol x CP_N
   int64_t* stat;       // ncol x 2: len(np.unique), flags
 };
-
-__host__ __device__ inline int64_t next_pow2(int64_t v) {
-  int64_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
-__device__ inline uint64_t to_key(double v) {
-  const uint64_t b = (uint64_t)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ inline double from_key(uint64_t k) {
-  const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-
-__device__ inline void cas_keys(uint64_t* a, uint64_t* b, bool asc) {
-  const uint64_t x = *a, y = *b;
-  if ((x > y) == asc) {
-    *a = y;
-    *b = x;
-  }
-}
-
-// the index pair of compare-exchange number i at stride j
-__device__ inline int64_t pair_lo(int64_t i, int64_t j) { return ((i & ~(j - 1)) << 1) | (i & (j - 1)); }
-
-// bitonic passes j = jtop .. 1 of stage k on an LDS chunk whose first key has global index g0
-__device__ void lds_bitonic(uint64_t* sk, int64_t g0, int64_t k, int jtop) {
-  for (int j = jtop; j > 0; j >>= 1) {
-    for (int i = threadIdx.x; i < kChunk / 2; i += kThreads) {
-      const int lo = (int)pair_lo(i, j);
-      cas_keys(&sk[lo], &sk[lo + j], ((g0 + lo) & k) == 0);
-    }
-    __syncthreads();
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void kde_sort_chunks_kernel(KdeSrc s, uint64_t* __restrict__ keys,
-                                                                   int64_t pmax, unsigned* __restrict__ nonfinite) {
-  __shared__ uint64_t sk[kChunk];
-  const int c = blockIdx.y;
-  const int side = c >= s.ncol0;
-  const int col = side ? c - s.ncol0 : c;
-  const int64_t n = s.n[side];
-  const int64_t P = next_pow2(n > kChunk ? n : kChunk);
-  const int64_t g0 = (int64_t)blockIdx.x * kChunk;
-  if (g0 >= P) return;
-  const double* x = s.x[side] + (int64_t)col * s.cs[side];
-  const int64_t rs = s.rs[side];
-  bool bad = false;
-  for (int i = threadIdx.x; i < kChunk; i += kThreads) {
-    const int64_t g = g0 + i;
-    uint64_t key = ~0ull;  // padding sorts last
-    if (g < n) {
-      const double v = x[g * rs];
-      bad |= !isfinite(v);
-      key = to_key(v);
-    }
-    sk[i] = key;
-  }
-  if (bad) atomicOr(&nonfinite[c], 1u);
-  __syncthreads();
-  for (int64_t k = 2; k <= kChunk; k <<= 1) lds_bitonic(sk, g0, k, (int)(k >> 1));
-  uint64_t* out = keys + (int64_t)c * pmax + g0;
-  for (int i = threadIdx.x; i < kChunk; i += kThreads) out[i] = sk[i];
-}
 
 // ---- workgroup reductions (fixed order: a wave butterfly, then the wave sums in order) ----
 __device__ inline double wg_sum(double v, double* red) {
@@ -310,23 +233,7 @@ __global__ __launch_bounds__(kThreads) void kde_column_kernel(KdeArgs A) {
 
   // ---- 1. the remaining bitonic stages (one workgroup owns the column) ----
   if (!bad) {
-    uint64_t* sk = (uint64_t*)sh;
-    for (int64_t k = 2 * (int64_t)kChunk; k <= P; k <<= 1) {
-      for (int64_t j = k >> 1; j >= kChunk; j >>= 1) {
-        for (int64_t i = tid; i < P / 2; i += kThreads) {
-          const int64_t lo = pair_lo(i, j);
-          cas_keys(&gk[lo], &gk[lo + j], (lo & k) == 0);
-        }
-        __syncthreads();
-      }
-      for (int64_t g0 = 0; g0 < P; g0 += kChunk) {
-        for (int i = tid; i < kChunk; i += kThreads) sk[i] = gk[g0 + i];
-        __syncthreads();
-        lds_bitonic(sk, g0, k, kChunk / 2);
-        for (int i = tid; i < kChunk; i += kThreads) gk[g0 + i] = sk[i];
-        __syncthreads();
-      }
-    }
+    column_merge(gk, P, (uint64_t*)sh);
   }
 
   // ---- 2. statistics of the sorted column ----

@@ -21,6 +21,8 @@
 //     c = (n_lo, n_hi, pair, 8)        normals of dimensions 2 pair, 2 pair + 1 of candidate i of generation g of a CMA-ES
 //                                      run of the acquisition search's refinement (cmaes.hip), n = g lambda + i, under the
 //                                      run's own key
+//     c = (n_lo, n_hi, p,    9)        box draw n of warp_input's plausible / search box (warp.hip): words 0, 1 and 2, 3
+//                                      as the 53-bit uniforms of dimensions 2 p, 2 p + 1
 // oracle/sample_ref.py restates both.  Component choice: inverse CDF of the weights
 // (np.random.choice(p=w), :316-319); with balance_flag the first sum_k floor(w_k N) samples
 // are split exactly according to the weights and the remaining ones are drawn from the

@@ -37,6 +37,60 @@ struct Scratch {
   }
 };
 
+// The scratch of the four input-warping entry points (api_warp.hip), one list each; a piece an entry does not use has
+// count 0.
+//   vbmc_warp_points   x (n x D) | y (n x D) | lj_new (n) | lj_old (n)
+//   vbmc_warp_unscent  x (n x D) | sigma (rows x D) | mean, sd (n x D each) | pts (U x n x D, on request)
+//   vbmc_warp_gp       x (N x D) | sigma = ell (S x D) | mean, sd = log ell_new (S x N x D each) | lj_new, lj_old (N) |
+//                      out (S x D + 2)
+//   vbmc_warp_box      x = the uniforms (n x D, uploaded draws only) | box (2 D) | y (n x D) | keys (D x pmax) and
+//                      nonfinite flags (D) (quantile mode) | out (2 D) | sorted (D x n, on request)
+struct WarpWs {
+  Scratch sc;
+  Piece<> x, sigma, box, y, mean, sd, pts, lj_new, lj_old, out, sorted;
+  Piece<unsigned long long> keys;
+  Piece<unsigned> nonfinite;
+};
+inline WarpWs warp_points_ws(size_t n, size_t D, bool want_y, bool want_new, bool want_old) {
+  WarpWs w;
+  w.x = w.sc.add(n * D);
+  w.y = w.sc.add(want_y ? n * D : 0);
+  w.lj_new = w.sc.add(want_new ? n : 0);
+  w.lj_old = w.sc.add(want_old ? n : 0);
+  return w;
+}
+inline WarpWs warp_unscent_ws(size_t n, size_t D, size_t sigma_rows, bool want_pts) {
+  WarpWs w;
+  w.x = w.sc.add(n * D);
+  w.sigma = w.sc.add(sigma_rows * D);
+  w.mean = w.sc.add(n * D);
+  w.sd = w.sc.add(n * D);
+  w.pts = w.sc.add(want_pts ? (2 * D + 1) * n * D : 0);
+  return w;
+}
+inline WarpWs warp_gp_ws(size_t N, size_t D, size_t S) {
+  WarpWs w;
+  w.x = w.sc.add(N * D);
+  w.sigma = w.sc.add(S * D);
+  w.mean = w.sc.add(S * N * D);
+  w.sd = w.sc.add(S * N * D);
+  w.lj_new = w.sc.add(N);
+  w.lj_old = w.sc.add(N);
+  w.out = w.sc.add(S * D + 2);
+  return w;
+}
+inline WarpWs warp_box_ws(size_t n, size_t D, bool uploaded, bool quantiles, size_t pmax, bool want_sorted) {
+  WarpWs w;
+  w.x = w.sc.add(uploaded ? n * D : 0);
+  w.box = w.sc.add(2 * D);
+  w.y = w.sc.add(n * D);
+  w.keys = w.sc.add<unsigned long long>(quantiles ? D * pmax : 0);
+  w.nonfinite = w.sc.add<unsigned>(quantiles ? D : 0);
+  w.out = w.sc.add(2 * D);
+  w.sorted = w.sc.add(want_sorted ? D * n : 0);
+  return w;
+}
+
 // The state of one CMA-ES run of vbmc_search_cmaes in the search workspace (cmaes.hip), offsets in doubles: the head
 // (phase, stop reason, counters: 8 doubles) | p_sigma, p_c, 1 / diag L (D each) | L (D x D) | the generation's points,
 // steps y and repaired normals z' (lambda x D each) | the ring of generation-best values (hist).  The mean, sigma, C,

@@ -45,12 +45,14 @@ from . import minimize_adam as _adam
 from . import variational_optimization as _avo
 from .active_importance_sampling import active_importance_sampling as _ais_mirror
 from .active_search import get_search_points as _gsp_mirror
+from . import whitening as _whitening
 
 _SAVED = "_pyvbmc_amd_saved"
 _LEAVES = ("entmc_vbmc", "entlb_vbmc", "_gp_log_joint", "_neg_elcbo")
 
 
-_MIRROR_ONLY_KW = ("rng", "seed", "eps_half", "ctx", "rows", "return_raw", "sampler", "products", "device")  # keyword-only extras of the mirrors
+_MIRROR_ONLY_KW = ("rng", "seed", "eps_half", "ctx", "rows", "return_raw", "sampler", "products", "device",
+                   "n_plausible", "n_search")  # keyword-only extras of the mirrors
 
 
 def _with_reference_fallback(fast, ref):
@@ -271,4 +273,40 @@ def unpatch_active_sampling(mod):
         else:
             setattr(mod, name, ref)
         delattr(mod, saved)
+    return mod
+
+
+_SAVED_WARP = "_pyvbmc_amd_saved_whitening"
+_WARP_NAMES = ("warp_input", "warp_gp_and_vp")
+
+
+def patch_whitening(mod=None):
+    """Rebind ``warp_input`` and ``warp_gp_and_vp`` on ``mod`` (default: ``pyvbmc.vbmc.vbmc``, which binds both names by
+    value, vbmc.py:24) to the device mirrors of pyvbmc_amd/whitening.py, with the reference's functions behind them for
+    ``_lib.UnsupportedShape`` (an unrecognised transformer, D > 32).  Opt-in: ``patch()`` does not call it.  Idempotent;
+    returns ``mod``."""
+    if mod is None:
+        import importlib
+
+        mod = importlib.import_module("pyvbmc.vbmc.vbmc")
+    if hasattr(mod, _SAVED_WARP):
+        unpatch_whitening(mod)
+    saved = {n: getattr(mod, n, None) for n in _WARP_NAMES}
+    setattr(mod, _SAVED_WARP, saved)
+    for n in _WARP_NAMES:
+        fast = getattr(_whitening, n)
+        setattr(mod, n, _with_reference_fallback(fast, saved[n]) if callable(saved[n]) else fast)
+    return mod
+
+
+def unpatch_whitening(mod):
+    """Put back what ``patch_whitening`` replaced."""
+    if not hasattr(mod, _SAVED_WARP):
+        return mod
+    for n, ref in getattr(mod, _SAVED_WARP).items():
+        if ref is None:
+            delattr(mod, n)
+        else:
+            setattr(mod, n, ref)
+    delattr(mod, _SAVED_WARP)
     return mod

@@ -47,11 +47,68 @@ def rel(a, b):
     return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300))
 
 
+def warp_row(ctx, device_name, D=10, K=50, N=400, S=8):
+    """Row ``warp``: warp_input + warp_gp_and_vp (whitening/whitening.py:80-375), the device route against
+    ``device=False`` (the same code over the host transformer) on the same box: five repeats after a warm-up each."""
+    from types import SimpleNamespace
+
+    sys.path.insert(0, str(ROOT / "tests"))
+    from transform_host import RefShapedTransformer
+
+    from pyvbmc_amd import whitening
+
+    r = np.random.default_rng(5)
+    typ = np.resize([0.0, 3.0, 12.0, 13.0], D)
+    lb, ub = np.where(typ == 0, -np.inf, -3.0 - r.random(D)), np.where(typ == 0, np.inf, 4.0 + r.random(D))
+    pt = RefShapedTransformer(typ, lb, ub, 0.1 * r.standard_normal(D), 1.0 + r.random(D))
+    lam = 0.5 + r.random((D, 1))
+    w = 0.2 + r.random((1, K))
+    vp = SimpleNamespace(D=D, K=K, mu=0.8 * r.standard_normal((D, K)), sigma=0.3 + 0.5 * r.random((1, K)),
+                         lambd=lam / np.sqrt(np.sum(lam**2) / D), w=w / np.sum(w), parameter_transformer=pt)
+    mean = np.sum(vp.w * vp.mu, axis=1)
+    dev = vp.mu - mean[:, None]
+    cov = np.sum(vp.w * vp.sigma**2) * np.diag(vp.lambd.ravel()**2) + (vp.w * dev) @ dev.T
+    vp.moments = lambda orig_flag=False, cov_flag=True: (mean.reshape(1, -1), cov)
+    X = 0.9 * r.standard_normal((N, D))
+    y = -0.5 * np.sum(X**2, axis=1, keepdims=True)
+    plb = np.where(typ == 0, -2.0, 0.5 * (np.where(typ == 0, 0, lb) + np.where(typ == 0, 0, ub)) - 1.0)
+    state = {"plb_orig": plb.reshape(1, -1), "pub_orig": plb.reshape(1, -1) + 2.0, "lb_search": np.full((1, D), -1.5),
+             "ub_search": np.full((1, D), 1.5), "search_cache": 0.7 * r.standard_normal((20, D)), "warping_count": 0,
+             "iter": 3, "N": N, "run_mean": [], "run_cov": [], "last_run_avg": np.nan}
+    flog = SimpleNamespace(X=X.copy(), y=y + pt.log_abs_det_jacobian(X).reshape(-1, 1), X_orig=pt.inverse(X), y_orig=y,
+                           X_flag=np.ones(N, dtype=bool), parameter_transformer=pt)
+    options = {"warp_rotoscaling": True, "warp_nonlinear": False, "warp_roto_corr_thresh": 0.05, "warp_cov_reg": 0}
+    hyp = 0.3 * r.standard_normal((S, 3 * D + 3))
+    count = lambda n: SimpleNamespace(hyperparameter_count=lambda *a: n)  # noqa: E731
+    gp = SimpleNamespace(covariance=count(D + 1), noise=count(1), mean=gpm.NegativeQuadratic(), X=X,
+                         posteriors=[SimpleNamespace(hyp=h) for h in hyp])
+
+    def run(device):
+        np.random.seed(1)
+        new, st2, _, _ = whitening.warp_input(vp, state, flog, options, device=device, ctx=ctx if device else None)
+        vp2, hw = whitening.warp_gp_and_vp(new, gp, vp, SimpleNamespace(D=D, optim_state=st2), device=device,
+                                           ctx=ctx if device else None)
+        return st2["plb_tran"], st2["lb_search"], vp2.mu, hw
+
+    t_dev, out_d = med(lambda: run(True), reps=5, warm=1)
+    t_cpu, out_h = med(lambda: run(False), reps=5, warm=1)
+    return {"row": "warp", "reference": "whitening/whitening.py:80-375 (warp_input + warp_gp_and_vp)",
+            "shape": f"D={D} K={K} N={N} S={S}, 100000 + 1000 box draws (np.random, uploaded)",
+            "device_ms": 1e3 * t_dev, "host_route_ms": 1e3 * t_cpu, "speedup": t_cpu / t_dev,
+            "cpu_note": "device=False: the same code over the host transformer, same box, median of 5 after 1 warm-up",
+            "parity_max_rel_err": max(rel(a, b) for a, b in zip(out_d, out_h)), "device": device_name}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, default=3)
+    ap.add_argument("--only", default=None, help="warp: print that row alone (profiles/warp_rows.json)")
     a = ap.parse_args()
     ctx = _lib.Context(0)
+    if a.only == "warp":
+        print(json.dumps(warp_row(ctx, ctx.device_info()["name"].strip())), flush=True)
+        ctx.close()
+        return
 
     def kernel_ms(fn, which):
         """One extra call with the HIP event pair around the dominant kernel switched on (the rows'
@@ -293,6 +350,8 @@ def main():
     tc, klo = once(lambda: sample_ref.kl_div_mc(mix, mix2, Nkl, 31))
     emit("8f-4 vp.kl_div(vp2, N=1e5), Monte-Carlo branch, one device call", "variational_posterior.py:1107-1126", f"N={Nkl} D={D} K={K}",
          t, tc, "oracle on the same draws, full", rel(kld, klo))
+    # ---- input warping ----------------------------------------------------------------------------
+    print(json.dumps(warp_row(ctx, info["name"].strip())), flush=True)
     ctx.close()
 
 
