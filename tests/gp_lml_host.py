@@ -30,6 +30,8 @@ CASES = [
     (65, 3, 2, gp_ref.MEAN_NEGQUAD),
     (130, 10, 3, gp_ref.MEAN_NEGQUAD),
     (257, 20, 2, gp_ref.MEAN_NEGQUAD),
+    (65, 32, 2, gp_ref.MEAN_NEGQUAD),  # D = DMX: the gradient tile's coordinate panels at their full height
+    (130, 13, 2, gp_ref.MEAN_CONST),  # an odd D between the workload's two
 ]
 
 

@@ -56,11 +56,11 @@ def prior_bound(h, priors):
 
 
 class Case:
-    """One replay case: data, C = 3 starts, the chain's arguments."""
+    """One replay case: data, C starts (3 unless given), the chain's arguments."""
 
-    def __init__(self, N, D, mean, with_s2, seed):
+    def __init__(self, N, D, mean, with_s2, seed, chains=3, n=2, thin=2, burn_in=1):
         self.N, self.D, self.mean, self.seed = N, D, mean, seed
-        self.X, self.y, self.x0 = gph.make_case(N, D, 3, mean, seed=100 + N)
+        self.X, self.y, self.x0 = gph.make_case(N, D, chains, mean, seed=100 + N)
         self.s2 = glh.reference(N, D, 2, mean, True)[3] if with_s2 else None
         P = self.x0.shape[1]
         self.P = P
@@ -71,7 +71,7 @@ class Case:
         pri["mu"][:D], pri["sigma"][:D], pri["df"][:D] = np.log(1.5), 1.0, 3.0
         pri["mu"][D + 1], pri["sigma"][D + 1], pri["df"][D + 1] = np.log(0.3), 0.5, 3.0
         self.priors = pri
-        self.n, self.thin, self.burn_in = 2, 2, 1
+        self.n, self.thin, self.burn_in = n, thin, burn_in
 
     def value(self, h):
         """dict(f, lml_bound = factor_of(h) vabs, prior_bound) of one point; f = -inf (bounds 0) when it does not
@@ -111,16 +111,22 @@ CASES = {
     65: (65, 3, gp_ref.MEAN_NEGQUAD, False, 2),
     63: (63, 3, gp_ref.MEAN_CONST, True, 2),
     130: (130, 2, gp_ref.MEAN_ZERO, False, 3),
+    # the workload's dimensions (bench.py: D = 10 and 20): P = 3 D + 3 = 33 and 63 hyper-parameters in the sweep and in the
+    # prior arrays.  The host statement costs seconds per chain there, so D = 20 runs two chains of burn-in 1 and one kept
+    # sweep: every coordinate is still swept twice.
+    "d10": (65, 10, gp_ref.MEAN_NEGQUAD, False, 1),
+    "d20": (70, 20, gp_ref.MEAN_NEGQUAD, True, 1, dict(chains=2, n=1, thin=1, burn_in=1)),
 }
 
 
 @lru_cache(maxsize=None)
 def case(key):
-    return Case(*CASES[key])
+    spec = CASES[key]
+    return Case(*spec[:5], **(spec[5] if len(spec) > 5 else {}))
 
 
 @lru_cache(maxsize=None)
 def replay(key):
-    """The three chains of a case on the host, computed once."""
+    """The chains of a case on the host, computed once."""
     cs = case(key)
-    return [cs.chain(c) for c in range(3)]
+    return [cs.chain(c) for c in range(cs.x0.shape[0])]

@@ -352,7 +352,7 @@ def rank(X_search, idx_cache, acq_fast, optim_state, options):
 
 
 # ---------------------------------------------------------------------------------------------- fixtures for the GPU tests
-def wide_case(D=32, K=2, N=40, number_of_points=300, seed=5, centre=25.0):
+def wide_case(D=32, K=2, N=40, number_of_points=300, seed=5, centre=25.0, sigma_scale=1.0):
     """A case like tests/golden/search.npz's at another shape (nothing recorded): unbounded transformer dimensions with a
     shift and a scale, a 4-row cache, search cache and HPD on.  Everything lies around ``centre``, far from zero in units
     of its spread: no element of a point is a sum that cancels, so a relative tolerance means the same for all of them."""
@@ -362,7 +362,7 @@ def wide_case(D=32, K=2, N=40, number_of_points=300, seed=5, centre=25.0):
     pt = RefShapedTransformer(np.zeros(D), np.full(D, -np.inf), np.full(D, np.inf), 0.1 * r.standard_normal(D),
                               0.5 + r.random(D))
     lam = 0.5 + r.random(D)
-    mix = mixture_ref.Mixture.make(centre + r.standard_normal((D, K)), 0.4 + 0.5 * r.random(K),
+    mix = mixture_ref.Mixture.make(centre + r.standard_normal((D, K)), sigma_scale * (0.4 + 0.5 * r.random(K)),
                                    lam / np.sqrt(np.sum(lam**2) / D), np.full(K, 1.0 / K))
     X = centre + 1.2 * r.standard_normal((N, D))
     y = (-0.5 * np.sum((X - centre) ** 2, axis=1) + 0.1 * r.standard_normal(N)).reshape(-1, 1)
@@ -377,15 +377,17 @@ def wide_case(D=32, K=2, N=40, number_of_points=300, seed=5, centre=25.0):
                            number_of_points=number_of_points)
 
 
-def gp_fixture(case, S=2, seed=9):
+def gp_fixture(case, S=2, seed=9, length_mult=1.0):
     """An oracle GP (S hyper-parameter samples, negative-quadratic mean) on the case's evaluated points, with the
-    per-point noise table and length scale of the noisy acquisition functions."""
+    per-point noise table and length scale of the noisy acquisition functions.  ``length_mult`` multiplies the length
+    scales (0.8 .. 1.1): at D = 20 and more, a search point of the wide case and a training point are so far apart in
+    units of those that their median covariance is 3e-12 sf^2 (4e-17 at D = 32), below every bound the values are held to."""
     from oracle import gp_ref
 
     r = np.random.default_rng(seed)
     D = case.D
     X, y = case.flog.X[case.flog.X_flag], case.flog.y[case.flog.X_flag]
-    hyp = np.array([np.concatenate([np.log(0.8 + 0.3 * r.random(D)), [np.log(2.0)], [np.log(0.05 * (s + 1))], [0.1], np.zeros(D),
+    hyp = np.array([np.concatenate([np.log(length_mult * (0.8 + 0.3 * r.random(D))), [np.log(2.0)], [np.log(0.05 * (s + 1))], [0.1], np.zeros(D),
                                     np.zeros(D)]) for s in range(S)])
     ogp = gp_ref.make_gp(X, y, hyp, gp_ref.MEAN_NEGQUAD)
     length = np.exp(hyp[:, :D].mean(axis=0))

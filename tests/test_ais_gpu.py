@@ -195,6 +195,18 @@ def test_products_false_dict_survives_a_displaced_state(ctx, golden):
 
 
 # ------------------------------------------------------------------------------------------------ 3. tile edges
+def check_quantile_acq(acq, gp, vp, ogp, length, sn2_new, Xs, out, host, kind=ais_host.IMIQR):
+    """The quantile acquisition over the installed state ``out`` at the points Xs against the host's over ``host``."""
+    sn2 = nearest_sn2(Xs, ogp.X, length, sn2_new)
+    with np.errstate(all="ignore"):
+        ref = ais_host.quantile_acq(ogp, Xs, sn2, host, kind)
+    v = acq(Xs.copy(), gp, vp, SimpleNamespace(y_max=0.0), optim_state(ogp.X, length, out))
+    err = float(np.max(np.abs(v - ref)))
+    print(f"acq at {Xs.shape[0]} points: max |device - host| = {err:.2e} (max |acq| {np.max(np.abs(ref)):.2f})")
+    assert err <= 1e-9
+    return err
+
+
 @pytest.fixture(scope="module")
 def larger():
     return ais_host.larger_case()
@@ -228,13 +240,7 @@ def test_tile_edges_vs_host(ctx, larger, n_vp, n_box, n_mcmc):
         with np.errstate(all="ignore"):
             host = ais_host.from_points(ogp, mix, out["X"], ais_host.IMIQR, n_vp, n_box)
     check_state(out, host, ogp, f"tile edges {n_vp}+{n_box} mcmc {n_mcmc}")
-    sn2 = nearest_sn2(Xs, ogp.X, length, sn2_new)
-    with np.errstate(all="ignore"):
-        ref = ais_host.quantile_acq(ogp, Xs, sn2, host, ais_host.IMIQR)
-    v = acq(Xs.copy(), gp, vp, SimpleNamespace(y_max=0.0), optim_state(ogp.X, length, out))
-    err = float(np.max(np.abs(v - ref)))
-    print(f"acq at 200 points: max |device - host| = {err:.2e} (max |acq| {np.max(np.abs(ref)):.2f})")
-    assert err <= 1e-9
+    check_quantile_acq(acq, gp, vp, ogp, length, sn2_new, Xs, out, host)
 
 
 # ------------------------------------------------------------------------------------------------ 4. MCMC plumbing
@@ -300,11 +306,11 @@ def test_viqr_fess_mcmc_branch_vs_host(ctx, larger):
 
 
 # ------------------------------------------------------------------------------------------------ 5. philox
-@pytest.mark.parametrize("n_vp,n_box", [(30, 18), (0, 20), (20, 0)])
-def test_philox_imiqr(ctx, larger, n_vp, n_box):
+def check_philox_imiqr(ogp, mix, sn2_new, n_vp, n_box, what="philox"):
+    """The Philox route of the IMIQR importance state on a GP and mixture: reproducible, NumPy's stream untouched, the box
+    draws near training points, and the state against the host's at the device's points."""
     from pyvbmc_amd.active_importance_sampling import active_importance_sampling
 
-    ogp, mix, _, sn2_new = larger
     gp, _ = plain_gp(ogp, sn2_new)
     vp, acq = PlainVP(mix), mirror_acq(ais_host.IMIQR)
     opts = dict(active_importance_sampling_vp_samples=n_vp, active_importance_sampling_box_samples=n_box,
@@ -317,17 +323,24 @@ def test_philox_imiqr(ctx, larger, n_vp, n_box):
         assert np.array_equal(a[k], b[k]), k
     other = active_importance_sampling(vp, gp, acq, opts, rng="philox", seed=6, products=False)
     assert not np.array_equal(other["X"], a["X"])
-    assert a["X"].shape == (n_vp + n_box, 4) and np.all(np.isfinite(a["X"]))
+    assert a["X"].shape == (n_vp + n_box, ogp.D) and np.all(np.isfinite(a["X"]))
     if n_box:
         rect_delta = 2 * np.std(ogp.X, ddof=1, axis=0)
         box = a["X"][n_vp:]
         near = np.all(np.abs(box[:, None, :] - ogp.X[None, :, :]) <= rect_delta, axis=2).any(axis=1)
         assert near.all()
-        assert len(np.unique(box[:, 0])) == n_box  # distinct draws
+        for d in range(ogp.D):
+            assert len(np.unique(box[:, d])) == n_box  # distinct draws, in every dimension
         assert not np.any(np.all(box[:, None, :] == ogp.X[None, :, :], axis=2))  # ... off the training points
     with np.errstate(all="ignore"):
         host = ais_host.from_points(ogp, mix, a["X"], ais_host.IMIQR, n_vp, n_box)
-    check_state(a, host, ogp, f"philox {n_vp}+{n_box}")
+    return check_state(a, host, ogp, f"{what} {n_vp}+{n_box}")
+
+
+@pytest.mark.parametrize("n_vp,n_box", [(30, 18), (0, 20), (20, 0)])
+def test_philox_imiqr(ctx, larger, n_vp, n_box):
+    ogp, mix, _, sn2_new = larger
+    check_philox_imiqr(ogp, mix, sn2_new, n_vp, n_box)
 
 
 def test_philox_viqr_and_env_default(ctx, larger, monkeypatch):

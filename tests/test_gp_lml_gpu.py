@@ -15,7 +15,8 @@ from test_gp_post_gpu import CountingLib, mirror_gp, points
 
 pytestmark = pytest.mark.gpu
 
-# (N, D, B, mean): the block edge and one column past it, three and five block steps with remainders, a padded D
+# (N, D, B, mean): the block edge and one column past it, three and five block steps with remainders, a padded D, the
+# widest D (the [DMX][64] coordinate panels of the gradient tile full) and an odd D between the workload's two
 CASES = [
     (1, 2, 1, gp_ref.MEAN_ZERO),
     (63, 3, 2, gp_ref.MEAN_CONST),
@@ -23,6 +24,8 @@ CASES = [
     (65, 3, 2, gp_ref.MEAN_NEGQUAD),
     (130, 10, 5, gp_ref.MEAN_NEGQUAD),
     (257, 20, 2, gp_ref.MEAN_NEGQUAD),
+    (65, 32, 2, gp_ref.MEAN_NEGQUAD),
+    (130, 13, 2, gp_ref.MEAN_CONST),
 ]
 
 

@@ -76,7 +76,7 @@ def test_replay_preconditions(key):
           f"evaluations {[int(r['stats'][0]) for r in res]}")
     for r in res:
         assert r["stats"][2] == 0 and r["stats"][3] == 0
-        assert r["samples"].shape == (2, hs.case(key).P)
+        assert r["samples"].shape == (hs.case(key).n, hs.case(key).P)
     assert bound > 0 and margin >= 10 * bound
 
 

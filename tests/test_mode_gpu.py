@@ -114,14 +114,9 @@ def _call(ctx, vp, orig, n, cand, seed, n_opts):
     return x, f[0], rec, pts
 
 
-@pytest.mark.parametrize("name, orig", [("d10", False), ("d2_bounded", True), ("d10_bounded", True)])
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 100000])
-def test_start_selection_is_the_host_argmin(ctx, golden, name, orig, n):
-    """Per round the device's start index is np.argmin of -pdf over the same candidates, centres included (tile
-    sizes 1, 63, 64, 65 and 1e5 + K)."""
-    vp = mh.golden_vp(golden, name)
+def check_start_selection(ctx, vp, orig, n, n_opts=3):
+    """Per round the device's start index is np.argmin of -pdf over the same n candidates, centres included."""
     vp.ctx = ctx
-    n_opts = 3
     np.random.seed(5)
     cand = np.ascontiguousarray(np.stack([vp.sample(n, orig)[0] for _ in range(n_opts)]))
     _, _, rec, _ = _call(ctx, vp, orig, n, cand, 0, n_opts)
@@ -133,6 +128,14 @@ def test_start_selection_is_the_host_argmin(ctx, golden, name, orig, n):
         vals = -vp.pdf(np.ascontiguousarray(pts), orig_flag=orig, log_flag=True).ravel()
         assert int(rec[r, 0]) == int(np.argmin(vals))
         assert abs(rec[r, 1] + vals[int(rec[r, 0])]) <= PDF_PARITY * max(1.0, abs(rec[r, 1]))
+
+
+@pytest.mark.parametrize("name, orig", [("d10", False), ("d2_bounded", True), ("d10_bounded", True)])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 100000])
+def test_start_selection_is_the_host_argmin(ctx, golden, name, orig, n):
+    """Per round the device's start index is np.argmin of -pdf over the same candidates, centres included (tile
+    sizes 1, 63, 64, 65 and 1e5 + K)."""
+    check_start_selection(ctx, mh.golden_vp(golden, name), orig, n)
 
 
 def test_start_selection_tie_goes_to_the_lowest_index(ctx, golden):
@@ -150,14 +153,10 @@ def test_start_selection_tie_goes_to_the_lowest_index(ctx, golden):
     assert int(rec[0, 0]) == 130
 
 
-@pytest.mark.parametrize("name, orig", [("d10", False), ("d10", True), ("d10_bounded", True), ("d2_bounded", False),
-                                        ("d6_overlap", False), ("d20", True)])
-def test_philox_repeats_is_stationary_and_beats_the_centres(ctx, golden, name, orig, monkeypatch):
+def check_philox_mode(vp, pt, obj, orig, monkeypatch):
+    """``mode(rng="philox")`` calls no host method, repeats bit for bit, ends at a stationary point and beats the centres."""
     from pyvbmc_amd import VariationalPosterior
 
-    vp = mh.golden_vp(golden, name)
-    pt = mh.golden_transformer(golden, name)
-    obj = _objective(vp, golden, name, orig)
     vp.pdf(vp.mu.T[:1], orig_flag=orig)  # (uploads before the methods are patched)
 
     def boom(*a, **k):
@@ -174,6 +173,14 @@ def test_philox_repeats_is_stationary_and_beats_the_centres(ctx, golden, name, o
     centres = vp.mu.T if not (orig and pt is not None) else pt.inverse(vp.mu.T)
     fc = np.max(mh.host_log_pdf(vp.mu, vp.sigma, vp.lambd, vp.w, pt, centres, orig))
     assert f >= fc - mh.f_tol(vp.K, vp.D, f)
+    return x, f
+
+
+@pytest.mark.parametrize("name, orig", [("d10", False), ("d10", True), ("d10_bounded", True), ("d2_bounded", False),
+                                        ("d6_overlap", False), ("d20", True)])
+def test_philox_repeats_is_stationary_and_beats_the_centres(ctx, golden, name, orig, monkeypatch):
+    vp = mh.golden_vp(golden, name)
+    check_philox_mode(vp, mh.golden_transformer(golden, name), _objective(vp, golden, name, orig), orig, monkeypatch)
 
 
 def test_philox_start_is_the_best_philox_sample(ctx, golden):

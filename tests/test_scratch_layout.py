@@ -74,3 +74,30 @@ def test_predict_plan_layout(carve):
     ld, rows, ntiles = 128, 64, 2
     off, total = carve([(mb * D, 8, 1), (S * rows * ld, 8, 32), (2 * S * ntiles * mb, 8, 1), (S * mb, 8, 1), (S * mb, 8, 1)])
     assert off == [0, 32, 16416, 16456, 16466] and total == 16476
+
+
+def test_every_dispatch_width_has_a_sweep_dimension():
+    """Every width VBMC_DISPATCH_DP (csrc/common.h) instantiates is the padded width of a D in {2, 3} or SWEEP_D
+    (tests/width_cases.py): a width added to the macro without a case, or a D taken out of the list, fails here."""
+    import re
+
+    import width_cases as wc
+
+    widths = wc.dispatch_widths()
+    assert len(widths) >= 10 and list(widths) == sorted(set(widths)) and widths[-1] == 32
+    # the macro's thresholds are its widths: "(D) <= w" picks CALL(w), the last width takes the rest
+    text = wc.COMMON_H.read_text()
+    body = text[text.index("#define VBMC_DISPATCH_DP"):].split("while (0)")[0]
+    assert tuple(int(t) for t in re.findall(r"\(D\) <= (\d+)", body)) == widths[:-1]
+    dims = wc.SMALL_D + wc.SWEEP_D
+    reached = {wc.padded_width(D, widths) for D in dims}
+    assert reached == set(widths), f"no sweep dimension for the widths {sorted(set(widths) - reached)}"
+    assert len(dims) == len(widths)  # one D per width
+    ws = [wc.padded_width(D, widths) for D in wc.SWEEP_D]
+    assert all(D == w or (D % 2 == 1 and D < w) for D, w in zip(wc.SWEEP_D, ws))  # the width itself, or odd and padded
+    assert any(D == w for D, w in zip(wc.SWEEP_D, ws)) and any(D < w for D, w in zip(wc.SWEEP_D, ws))
+    assert set(wc.WORKLOAD_D) <= set(wc.SWEEP_D)
+    assert {wc.padded_width(D, widths) for D in (1, 2, 6, 10, 20, 32) + wc.MODE_D} == set(widths)
+    # removing any one dimension leaves a width without a case
+    for D in dims:
+        assert {wc.padded_width(d, widths) for d in dims if d != D} != set(widths)

@@ -51,9 +51,9 @@ def full_set(res, options):
     return np.insert(res.X_search, idx, res.X_acq[0], axis=0), idx
 
 
-def search_setup(case, ctx, S=2, acq_name="AcqFcnVIQR"):
+def search_setup(case, ctx, S=2, acq_name="AcqFcnVIQR", length_mult=1.0):
     """Device-side arguments of ``search`` for a case, and the oracle objects of the restatement."""
-    ogp, length, sn2_new = sh.gp_fixture(case, S)
+    ogp, length, sn2_new = sh.gp_fixture(case, S, length_mult=length_mult)
     gp = PlainGP(ogp)
     gp._ctx = ctx
     gp.temporary_data["X_rescaled"] = ogp.X / length
@@ -89,13 +89,12 @@ def check_rank(res, state, options, idx_cache_len):
 POINT_SEEDS = {"a": 112, "b": 292, "d": 49, "e": 33, "f": 2, "wide": 1}
 
 
-@pytest.mark.parametrize("name", list(POINT_SEEDS))
-def test_philox_points_equal_the_restatement(ctx, golden, name):
+def check_philox_points(ctx, c, seed, name, expect_clamped=True):
+    """``get_search_points`` on the Philox streams against the restatement for one case and seed: the conditioning
+    precondition, the index column, the rows at their two bounds, the clamp, reproducibility."""
     from pyvbmc_amd import active_search
 
-    c = the_case(golden, name)
     vp = sh.package_vp(c, ctx)
-    seed = POINT_SEEDS[name]
     detail = {}
     Xh, idxh, blocks = sh.points_philox(c.number_of_points, c.optim_state, c.flog, c.mix, c.options, seed, detail=detail)
     assert np.nanmax(detail["cond"]) <= 100
@@ -111,7 +110,7 @@ def test_philox_points_equal_the_restatement(ctx, golden, name):
     np.testing.assert_allclose(X[n_cache:], Xh[n_cache:], rtol=1e-13, atol=0)
     lb, ub = c.optim_state["lb_search"], c.optim_state["ub_search"]
     clamped = (Xh == lb) | (Xh == ub)
-    assert np.array_equal(X[clamped], Xh[clamped]) and (name in ("b",) or clamped.any())
+    assert np.array_equal(X[clamped], Xh[clamped]) and (not expect_clamped or clamped.any())
     assert np.all(X >= lb) and np.all(X <= ub)
     X2, _ = active_search.get_search_points(c.number_of_points, c.optim_state, c.flog, vp, c.options, rng="philox",
                                             seed=seed, ctx=ctx)
@@ -119,6 +118,12 @@ def test_philox_points_equal_the_restatement(ctx, golden, name):
     X3, _ = active_search.get_search_points(c.number_of_points, c.optim_state, c.flog, vp, c.options, rng="philox",
                                             seed=seed + 1, ctx=ctx)
     assert not np.array_equal(X3[n_cache:], X[n_cache:])
+    return float(rel[:n_cache].max()) if n_cache else 0.0, float(rel[n_cache:].max())
+
+
+@pytest.mark.parametrize("name", list(POINT_SEEDS))
+def test_philox_points_equal_the_restatement(ctx, golden, name):
+    check_philox_points(ctx, the_case(golden, name), POINT_SEEDS[name], name, expect_clamped=name not in ("b",))
 
 
 def test_d_above_32_is_an_unsupported_shape(ctx):
@@ -165,18 +170,17 @@ def test_integer_rounding_and_hard_bound_mask(ctx, golden):
     assert np.all(res.acq_fast[res.order[-int(mask.sum()):]] == np.inf)
 
 
-def test_integer_rounding_at_d32(ctx):
-    """D = 32, the widest shape, with integer dimensions 0, 17 and 31 (the mask's last bit), through both entry points."""
+def check_integer_rounding(ctx, c, int_dims, seed):
+    """Integer dimensions ``int_dims`` of a case through both entry points: the fill of the Philox sources and
+    ``vbmc_search_put`` of host-drawn points."""
     from pyvbmc_amd import _lib, active_search
 
-    c = sh.wide_case()
     vp = sh.package_vp(c, ctx)
     D = c.D
     integer_vars = np.zeros(D, dtype=bool)
-    integer_vars[[0, 17, 31]] = True
+    integer_vars[list(int_dims)] = True
     int_bits = active_search._int_bits(integer_vars, D)
-    assert int_bits == (1 << 0) | (1 << 17) | (1 << 31)
-    seed = POINT_SEEDS["wide"]
+    assert int_bits == sum(1 << d for d in set(int_dims))
     Xh, _, blocks = sh.points_philox(c.number_of_points, c.optim_state, c.flog, c.mix, c.options, seed)
     Xr, pre = sh.real2int(Xh, c.pt, integer_vars, return_pre=True)
     assert np.min(np.abs(pre - np.floor(pre) - 0.5)) > 1e-9  # clear of the rounding's discontinuities
@@ -190,7 +194,7 @@ def test_integer_rounding_at_d32(ctx):
     np.testing.assert_allclose(X[:, integer_vars], Xr[:, integer_vars], rtol=1e-12, atol=0)
     np.testing.assert_allclose(X[n_cache:, ~integer_vars], Xr[n_cache:, ~integer_vars], rtol=1e-13, atol=0)
     np.testing.assert_allclose(X[:n_cache, ~integer_vars], Xr[:n_cache, ~integer_vars], rtol=1e-12, atol=0)
-    assert not np.array_equal(X[:, 31], Xh[:, 31])  # the last dimension was rounded
+    assert not np.array_equal(X[:, D - 1], Xh[:, D - 1])  # the last dimension was rounded
     # host-drawn points take the same rounding: vbmc_search_put accepts the mask, and the fill of one copy source (what put
     # is, with a read-back) rounds the integer columns and leaves the others as they came
     active_search.put_points(ctx, Xh, int_bits, use_xf)
@@ -198,6 +202,13 @@ def test_integer_rounding_at_d32(ctx):
     Xp = active_search._fill(ctx, D, [(_lib.SRC_COPY, Xh.shape[0], Xh, 0.0, 0)], -inf, inf, int_bits, use_xf, True)
     np.testing.assert_allclose(Xp[:, integer_vars], Xr[:, integer_vars], rtol=1e-12, atol=0)
     assert np.array_equal(bits(Xp[:, ~integer_vars]), bits(Xh[:, ~integer_vars]))
+
+
+def test_integer_rounding_at_d32(ctx):
+    """D = 32, the widest shape, with integer dimensions 0, 17 and 31 (the mask's last bit), through both entry points."""
+    from pyvbmc_amd import _lib
+
+    check_integer_rounding(ctx, sh.wide_case(), (0, 17, 31), POINT_SEEDS["wide"])
     for bad in (1 << 5,):  # a bit at or above D is an argument error, at D < 32 only
         with pytest.raises(ValueError):
             ctx.check(ctx._lib.vbmc_search_put(ctx._h, 1, 5, _lib.ptr(np.zeros((1, 5))), bad, 0))
@@ -228,28 +239,46 @@ def close(a, b, tol, what):
     err = float(np.max(np.abs(a[~inf] - b[~inf]) / np.maximum(1.0, np.abs(b[~inf]))))
     print(what, f"{err:.2e}")
     assert err < tol, (what, err)
+    return err
+
+
+def check_values(ctx, c, s, acq_name, seed, what, cache_rtol=1e-12, points_conditioned=True):
+    """One search of a prepared case: the ranking, the points, and the values against the restatement and against the
+    package's own call at the returned points.  Returns (result, points, the two largest errors).
+    ``points_conditioned``: the case and seed meet the conditioning precondition of check_philox_points, so the points are
+    held to its relative bounds; without it (a case centred on zero, whose coordinates are sums that cancel) they are held
+    to the same bounds relative to the largest coordinate."""
+    from pyvbmc_amd import active_search
+
+    res = active_search.search(acq_name + "()", s.gp, s.vp, s.flog, s.state, s.options, rng="philox", seed=seed, ctx=ctx)
+    detail = {}
+    Xh, idxh, blocks = sh.points_philox(c.number_of_points, c.optim_state, c.flog, c.mix, c.options, seed, detail=detail)
+    assert res.acq_fast.shape == (c.number_of_points,)
+    X, idx = check_rank(res, s.state, s.options, idxh.size)
+    n_cache = blocks["cache"][1] if "cache" in blocks else 0
+    scale = 0.0 if points_conditioned else float(np.max(np.abs(Xh)))
+    if scale:  # the terms an element is added up from stay within a factor 100 of the largest coordinate
+        assert np.nanmax(detail["cond"] * np.abs(detail["raw"])) <= 100 * scale
+    np.testing.assert_allclose(X[:n_cache], Xh[:n_cache], rtol=0.0 if scale else cache_rtol, atol=cache_rtol * scale)
+    np.testing.assert_allclose(X[n_cache:], Xh[n_cache:], rtol=0.0 if scale else 1e-13, atol=1e-13 * scale)
+    assert ("active_importance_sampling" in s.state) == (acq_name in ("AcqFcnVIQR", "AcqFcnIMIQR"))
+    host, own = eval_both(acq_name, s, c, X)
+    e_own = close(res.acq_fast, own, 1e-9, f"{what} vs the package's own call")
+    e_host = close(res.acq_fast, host, 1e-9, f"{what} vs the restatement")
+    assert np.isposinf(res.acq_fast).any() and np.isfinite(res.acq_fast).any()
+    return res, X, (e_own, e_host)
 
 
 @pytest.mark.parametrize("reg", [False, True])
 @pytest.mark.parametrize("acq_name", list(CLOSED) + ["AcqFcnVIQR", "AcqFcnIMIQR"])
 def test_values_equal_the_restatement_and_the_package(ctx, golden, acq_name, reg):
-    from pyvbmc_amd import active_search
-
     c = the_case(golden, "d")
     s = search_setup(c, ctx, acq_name=acq_name)
     s.state["variance_regularized_acq_fcn"] = reg
     s.state["tol_gp_var"] = 0.05  # (above the predictive variance near the training points: the penalty acts)
     seed = POINT_SEEDS["d"]  # (the points are compared too: a seed of the conditioning precondition above)
-    res = active_search.search(acq_name + "()", s.gp, s.vp, s.flog, s.state, s.options, rng="philox", seed=seed, ctx=ctx)
-    Xh, idxh, _ = sh.points_philox(c.number_of_points, c.optim_state, c.flog, c.mix, c.options, seed)
+    res, _, _ = check_values(ctx, c, s, acq_name, seed, f"{acq_name} reg={reg}", cache_rtol=1e-13)
     assert res.acq_fast.shape == (300,)
-    X, idx = check_rank(res, s.state, s.options, idxh.size)
-    np.testing.assert_allclose(X, Xh, rtol=1e-13, atol=0)
-    assert ("active_importance_sampling" in s.state) == (acq_name in ("AcqFcnVIQR", "AcqFcnIMIQR"))
-    host, own = eval_both(acq_name, s, c, X)
-    close(res.acq_fast, own, 1e-9, f"{acq_name} reg={reg} vs the package's own call")
-    close(res.acq_fast, host, 1e-9, f"{acq_name} reg={reg} vs the restatement")
-    assert np.isposinf(res.acq_fast).any() and np.isfinite(res.acq_fast).any()
 
 
 # ---------------------------------------------------------------------------------------------- ranking

@@ -370,6 +370,69 @@ def run_warp_gp_and_vp(c, dtype=np.float64):
                           sigma=c.sigma, lambd=c.lambd, w=c.w, temperature=c.temperature)
 
 
+# ---- cases at any dimension (nothing recorded) ------------------------------------------------------------------------
+WIDE_TYPES = (0, 3, 12, 13)
+
+
+def box_uniforms(n, D, seed):
+    """The (n, D) uniforms of csrc/warp.hip's Philox box draws: dimensions 2 p and 2 p + 1 of draw i are the two 53-bit
+    uniforms of block (i, p, stream 9) under the key ``seed``."""
+    from oracle import philox_ref as pr
+
+    lo, hi = pr._split(np.arange(n, dtype=np.uint64))
+    out = np.empty((n, D))
+    for p in range((D + 1) // 2):
+        x = pr.philox4x32_10(lo, hi, np.full_like(lo, p), np.full_like(lo, 9), int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+        for h in range(2):
+            if 2 * p + h < D:
+                word = (x[2 * h].astype(np.uint64) << np.uint64(32)) | x[2 * h + 1].astype(np.uint64)
+                out[:, 2 * p + h] = (word >> np.uint64(11)).astype(np.float64) * 2.0**-53
+    return out
+
+
+def wide_case(D, K=3, S=2, N=37, wide_golden=None):
+    """A case of the entry-point tests at dimension D, with the fields ``load_case`` gives them (no recorded outputs).
+
+    The old transformer cycles the type codes 0, 3, 12, 13 over its dimensions and is rotated and scaled.  Where
+    ``wide_golden`` (tests/golden/transform_wide.npz) has a case of this D, a bounded dimension of it lends its finite
+    bounds, mu and delta; everything else is drawn from ``default_rng(D)``.  The new transformer is the whitening
+    transform ``rotoscale`` derives from the K-component mixture's covariance.  Points, box edges and unscented steps are
+    sized so that the centred coordinates stay within about one delta: no bounded map is driven into its saturated tail,
+    where the float64 statement itself loses its digits."""
+    r = np.random.default_rng(D)
+    types = np.array([WIDE_TYPES[d % 4] for d in range(D)], dtype=np.float64)
+    lb = r.uniform(-10.0, 0.0, D)
+    ub = lb + r.uniform(1.0, 12.0, D)
+    mu, delta = 0.2 * r.standard_normal(D), r.uniform(0.5, 2.0, D)
+    name = f"w{D}"
+    if wide_golden is not None and f"{name}_type" in wide_golden:
+        glb, gub = np.ravel(wide_golden[f"{name}_lb"]), np.ravel(wide_golden[f"{name}_ub"])
+        take = np.isfinite(glb) & np.isfinite(gub)
+        lb, ub = np.where(take, glb, lb), np.where(take, gub, ub)
+        mu, delta = np.where(take, wide_golden[f"{name}_mu"], mu), np.where(take, wide_golden[f"{name}_delta"], delta)
+    lb, ub = np.where(types == 0, -np.inf, lb), np.where(types == 0, np.inf, ub)
+    R, _ = np.linalg.qr(r.standard_normal((D, D)))
+    old = Xf(types, lb, ub, mu, delta, R, r.uniform(0.5, 1.0, D))
+    c = SimpleNamespace(name=f"wide{D}", D=D, K=K, S=S, old=old)
+    c.mu = 0.3 * r.standard_normal((D, K))
+    c.sigma = (0.3 / np.sqrt(D)) * r.uniform(0.5, 1.0, (1, K))
+    c.lambd = r.uniform(0.7, 1.3, (D, 1))
+    c.w = r.uniform(0.5, 1.0, (1, K))
+    c.w = c.w / np.sum(c.w)
+    Rn, scale = rotoscale(mixture_cov(c.mu, c.sigma, c.lambd, c.w), old, 0.0, 0.0)
+    c.new = Xf(types, lb, ub, np.zeros(D), np.ones(D), Rn, scale)
+    c.gp_X = 0.3 * r.standard_normal((N, D))
+    c.hyp = np.hstack([np.log((0.3 / np.sqrt(D)) * r.uniform(0.5, 1.0, (S, D))), r.standard_normal((S, 2 * D + 3))])
+    c.X_orig = old.inverse(0.3 * r.standard_normal((N, D)))
+    c.X_flag = np.ones(N, dtype=bool)
+    centre = old.inverse(np.zeros((1, D)))
+    half = np.where(types == 0, 1.0, 0.2 * (np.where(types == 0, 1.0, ub) - np.where(types == 0, 0.0, lb)))
+    c.plb_orig, c.pub_orig = centre - half * r.uniform(0.5, 1.0, D), centre + half * r.uniform(0.5, 1.0, D)
+    h = 1.0 / np.sqrt(D)
+    c.lb_search, c.ub_search = (-h * r.uniform(0.5, 1.0, D)).reshape(1, D), (h * r.uniform(0.5, 1.0, D)).reshape(1, D)
+    return c
+
+
 # ---- stand-ins with the reference objects' attribute names, for the package's functions ---------------------------------
 class PlainVP:
     """The attributes ``pyvbmc_amd.whitening`` reads of a posterior."""
