@@ -424,6 +424,15 @@ int vbmc_gp_posterior(vbmc_ctx* ctx, int N, int D, int S, int P, int mean_kind, 
  * N + 1 points. */
 int vbmc_gp_append(vbmc_ctx* ctx, const double* x_D, double y, double* alpha_SxN1, double* L_SxN1xN1);
 
+/* The same append under per-point noise: sn2_new_S is, per sample, the new point's total noise variance (the noise
+ * function at the new point, a user-provided s2 included).  The resident state may have constant or per-point noise,
+ * but must be device-built (VBMC_E_ARG otherwise).  Applies while sn2_new_S[s] >= sl[s] for every s -- the new point
+ * then leaves sn2_div, the scale of the factor, as it is; VBMC_E_UNSUP otherwise (the caller rebuilds with
+ * vbmc_gp_posterior).  The new state's sn2 is the old rows plus the new entry; vbmc_gp_append applies to it afterwards
+ * only if the old state had constant noise and every new entry equals sl.  Errors and outputs as vbmc_gp_append. */
+int vbmc_gp_append_noisy(vbmc_ctx* ctx, const double* x_D, double y, const double* sn2_new_S, double* alpha_SxN1,
+                         double* L_SxN1xN1);
+
 /* Copy the resident posterior out: alpha (S x N) and L (S x N x N), both nullable. */
 int vbmc_gp_fetch(vbmc_ctx* ctx, double* alpha_SxN, double* L_SxNxN);
 

@@ -19,11 +19,14 @@ from .active_search import get_search_points, refine, search  # noqa: F401
 from . import whitening  # noqa: F401
 from .dropin import patch, patch_active_sampling, unpatch, unpatch_active_sampling  # noqa: F401  (pyvbmc_amd.patch(vo): the whole drop-in in one call)
 from .dropin import patch_whitening, unpatch_whitening  # noqa: F401
+from .dropin import patch_active_sample_loop, unpatch_active_sample_loop  # noqa: F401
 from .entropy import entlb_vbmc, entmc_vbmc  # noqa: F401
-from .gp import GP, log_marginal_likelihood  # noqa: F401
+from .gp import GP, append_point, log_marginal_likelihood, reupdate  # noqa: F401
 from .variational_posterior import VariationalPosterior  # noqa: F401
+from .active_sample import active_sample  # noqa: F401
 
 __all__ = ["VariationalPosterior", "entmc_vbmc", "entlb_vbmc", "patch", "unpatch", "active_importance_sampling",
            "active_sample_proposal_pdf", "fess", "get_mcmc_opts", "renormalize_weights", "patch_active_sampling",
            "unpatch_active_sampling", "GP", "log_marginal_likelihood", "get_search_points", "search", "refine",
-           "whitening", "patch_whitening", "unpatch_whitening"]
+           "whitening", "patch_whitening", "unpatch_whitening", "active_sample", "append_point", "reupdate",
+           "patch_active_sample_loop", "unpatch_active_sample_loop"]

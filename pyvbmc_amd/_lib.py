@@ -194,6 +194,7 @@ SIGNATURES = {
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
     ),
     "vbmc_gp_append": (C.c_int, [_vp, _dp, C.c_double, _dp, _dp]),
+    "vbmc_gp_append_noisy": (C.c_int, [_vp, _dp, C.c_double, _dp, _dp, _dp]),
     "vbmc_gp_fetch": (C.c_int, [_vp, _dp, _dp]),
     "vbmc_gp_lml": (
         C.c_int,

@@ -305,3 +305,25 @@ def string_to_acq(string):
     return names[call.func.id](*args, **kwargs)
 
 
+def as_package_acq(obj):
+    """An entry of ``options["search_acq_fcn"]`` as one of this module's objects: a constructor string is evaluated
+    (``string_to_acq``), an object of this module is returned as it is, and a foreign object -- the reference's -- is
+    mapped by its class name to the class of that name here, with its ``acq_info["quantile"]`` for VIQR / IMIQR.
+    Anything else raises ``_lib.UnsupportedShape``: there is no device route for it."""
+    if isinstance(obj, str):
+        try:
+            return string_to_acq(obj)
+        except ValueError as e:
+            raise _lib.UnsupportedShape(f"acquisition function {obj!r} has no device route") from e
+    if isinstance(obj, AbstractAcqFcn):
+        if obj._kind is None:
+            raise _lib.UnsupportedShape("the abstract acquisition function has no device route")
+        return obj
+    names = {c.__name__: c for c in (AcqFcn, AcqFcnLog, AcqFcnVanilla, AcqFcnNoisy, AcqFcnVIQR, AcqFcnIMIQR)}
+    cls = names.get(type(obj).__name__)
+    if cls is None:
+        raise _lib.UnsupportedShape(f"acquisition function {type(obj).__name__} has no device route")
+    if issubclass(cls, _QuantileAcq):
+        return cls(quantile=obj.acq_info["quantile"])
+    return cls()
+

@@ -1,4 +1,5 @@
-// C-ABI entry points of the device-built GP posterior: vbmc_gp_posterior, vbmc_gp_append, vbmc_gp_fetch.
+// C-ABI entry points of the device-built GP posterior: vbmc_gp_posterior, vbmc_gp_append, vbmc_gp_append_noisy,
+// vbmc_gp_fetch.
 // They stand in for gp.py's GP._posterior (SURVEY Appendix A "Posterior"; gpyreg itself is not in the reference tree)
 // followed by vbmc_set_gp.  The new state is built in ctx->gp_next and swapped with ctx->gp only when every sample
 // factorised, so a failed call leaves the installed state as it was.
@@ -132,6 +133,7 @@ extern "C" int vbmc_gp_posterior(vbmc_ctx* ctx, int N, int D, int S, int P, int 
   w.h_y.assign(y_N, y_N + N);
   w.hyp.assign(hyp_SxP, hyp_SxP + (size_t)S * P);
   w.h_sl.assign(sn2_div_S, sn2_div_S + S);  // sn2_mult = 1
+  w.h_sn2.assign(sn2_SxN, sn2_SxN + (size_t)S * N);
   w.homo = true;
   for (int s = 0; s < S && w.homo; ++s)
     for (int n = 0; n < N && w.homo; ++n) w.homo = sn2_SxN[(size_t)s * N + n] == sn2_div_S[s];
@@ -149,13 +151,10 @@ extern "C" int vbmc_gp_posterior(vbmc_ctx* ctx, int N, int D, int S, int P, int 
   return fetch(ctx, alpha_SxN, L_SxNxN);
 }
 
-extern "C" int vbmc_gp_append(vbmc_ctx* ctx, const double* x_D, double y, double* alpha_out, double* L_out) {
-  if (!ctx || !x_D) return VBMC_E_ARG;
-  NEED_DEVICE(ctx);
-  if (!ctx->gp.set || !ctx->gp.dev_built)
-    return vbmc_fail(ctx, VBMC_E_ARG, "gp_append: the context holds no posterior built by vbmc_gp_posterior");
-  if (!ctx->gp.homo)
-    return vbmc_fail(ctx, VBMC_E_UNSUP, "gp_append: the resident posterior has per-point noise: update it instead");
+// One point appended to the device-built posterior.  sn2_new_S == nullptr: constant noise (vbmc_gp_append: the resident
+// state is homo and the new entry is read from its d_sn2, as before); else the new point's noise variance per sample.
+static int append_point(vbmc_ctx* ctx, const double* x_D, double y, const double* sn2_new_S, double* alpha_out, double* L_out,
+                        const char* who) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, stream_wait(ctx));
   const GpState& o = ctx->gp;
@@ -173,21 +172,57 @@ extern "C" int vbmc_gp_append(vbmc_ctx* ctx, const double* x_D, double y, double
   w.h_y.push_back(y);
   w.hyp = o.hyp;
   w.h_sl = o.h_sl;
-  w.homo = true;
-  std::vector<double> sW_host, sn2_host((size_t)S * N1);
-  for (int s = 0; s < S; ++s)
-    for (int n = 0; n < N1; ++n) sn2_host[(size_t)s * N1 + n] = o.h_sl[s];  // (constant noise: sn2 = sn2_div = sl)
+  w.homo = o.homo;
+  std::vector<double> sW_host;
+  w.h_sn2.resize((size_t)S * N1);
+  for (int s = 0; s < S; ++s) {
+    for (int n = 0; n < N; ++n)  // (constant noise: sn2 = sn2_div = sl)
+      w.h_sn2[(size_t)s * N1 + n] = sn2_new_S ? o.h_sn2[(size_t)s * N + n] : o.h_sl[s];
+    const double v = sn2_new_S ? sn2_new_S[s] : o.h_sl[s];
+    w.h_sn2[(size_t)s * N1 + N] = v;
+    w.homo = w.homo && v == o.h_sl[s];
+  }
+  // the new point's noise as the kernel reads it: the old state's first entry per sample (constant noise), or the
+  // new column of the state under construction
+  const double* d_sn2_new = sn2_new_S ? w.d_sn2 + N : o.d_sn2;
+  const size_t sn2_stride = sn2_new_S ? (size_t)N1 : (size_t)N;
   rc = stage_state(ctx, w, N1, D, S, P, o.mean_kind, sW_host);
-  if (!rc) rc = stage_tail(ctx, w.d_sn2, sn2_host.data(), (size_t)S * N1, d_flag, S);
+  if (!rc) rc = stage_tail(ctx, w.d_sn2, w.h_sn2.data(), (size_t)S * N1, d_flag, S);
   if (rc) {
-    (void)hipStreamSynchronize(ctx->stream);  // (copies from sW_host / sn2_host may be queued)
+    (void)hipStreamSynchronize(ctx->stream);  // (copies from sW_host / h_sn2 may be queued)
     return rc;
   }
   std::swap(ctx->gp, ctx->gp_next);
-  rc = launch_gp_post_append(ctx, ctx->gp_next, y, ws);
-  rc = finish_build(ctx, d_flag, S, rc, "gp_append");
+  rc = launch_gp_post_append(ctx, ctx->gp_next, y, d_sn2_new, sn2_stride, ws);
+  rc = finish_build(ctx, d_flag, S, rc, who);
   if (rc) return rc;
   return fetch(ctx, alpha_out, L_out);
+}
+
+extern "C" int vbmc_gp_append(vbmc_ctx* ctx, const double* x_D, double y, double* alpha_out, double* L_out) {
+  if (!ctx || !x_D) return VBMC_E_ARG;
+  NEED_DEVICE(ctx);
+  if (!ctx->gp.set || !ctx->gp.dev_built)
+    return vbmc_fail(ctx, VBMC_E_ARG, "gp_append: the context holds no posterior built by vbmc_gp_posterior");
+  if (!ctx->gp.homo)
+    return vbmc_fail(ctx, VBMC_E_UNSUP, "gp_append: the resident posterior has per-point noise: update it instead");
+  return append_point(ctx, x_D, y, nullptr, alpha_out, L_out, "gp_append");
+}
+
+extern "C" int vbmc_gp_append_noisy(vbmc_ctx* ctx, const double* x_D, double y, const double* sn2_new_S, double* alpha_out,
+                                    double* L_out) {
+  if (!ctx || !x_D || !sn2_new_S) return VBMC_E_ARG;
+  NEED_DEVICE(ctx);
+  if (!ctx->gp.set || !ctx->gp.dev_built)
+    return vbmc_fail(ctx, VBMC_E_ARG, "gp_append_noisy: the context holds no posterior built by vbmc_gp_posterior");
+  const GpState& o = ctx->gp;
+  if (o.h_sn2.size() != (size_t)o.S * o.N)
+    return vbmc_fail(ctx, VBMC_E_ARG, "gp_append_noisy: the resident posterior carries no noise table");
+  for (int s = 0; s < o.S; ++s)
+    if (!(sn2_new_S[s] >= o.h_sl[s]) || !(sn2_new_S[s] < INFINITY))
+      return vbmc_fail(ctx, VBMC_E_UNSUP, "gp_append_noisy: sample %d: the new point's noise is below sn2_div (the scale of the "
+                       "factor would change): update it instead", s);
+  return append_point(ctx, x_D, y, sn2_new_S, alpha_out, L_out, "gp_append_noisy");
 }
 
 extern "C" int vbmc_gp_fetch(vbmc_ctx* ctx, double* alpha_SxN, double* L_SxNxN) {

@@ -126,6 +126,7 @@ struct GpState {
   double* d_sl = nullptr;       // S : sn2_div * sn2_mult, the scale of A = K / sl + diag(sn2 / sn2_div)
   size_t cap_y = 0, cap_r = 0, cap_sn2 = 0, cap_sl = 0;
   std::vector<double> h_X, h_y, h_sl;  // host copies: X (N x D), y (N), sl (S)
+  std::vector<double> h_sn2;           // host copy of d_sn2 (S x N): vbmc_gp_append_noisy extends it by a column
 };
 
 // per-sample results of the GP expected log joint on the host (api_gp.hip glj_finalize)
@@ -648,8 +649,9 @@ struct GpAppendWs {
 };
 GpAppendWs gp_post_append_ws(int S, int N);
 // one point appended: `from` (N points, live) -> ctx->gp (N + 1 points, X / XT / hyp / sl / sn2 already in place);
-// ws: gp_post_append_ws(from.S, from.N), reserved
-int launch_gp_post_append(vbmc_ctx* ctx, const GpState& from, double y_new, const GpAppendWs& ws);
+// ws: gp_post_append_ws(from.S, from.N), reserved.  d_sn2_new[s * sn2_stride]: the new point's noise variance in sample s
+int launch_gp_post_append(vbmc_ctx* ctx, const GpState& from, double y_new, const double* d_sn2_new, size_t sn2_stride,
+                          const GpAppendWs& ws);
 void gp_post_free(vbmc_ctx* ctx);
 // vbmc_gp_lml's chunk plan, stated once: the candidates factorised side by side.  A candidate's factor state is L, L^-1
 // (N^2 each), the padded copy of L^-1 (ld^2), the inverted diagonal blocks (nb 64^2) and the gradient's tile partials

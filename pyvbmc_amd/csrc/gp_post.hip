@@ -12,7 +12,8 @@
 //   chol_trail_kernel  A_ab -= U_ja^T U_jb for the blocks j < a <= b              (the same tile product)
 // L^-1 then comes from launch_trinv (stage 2 only) and alpha from two triangular matrix-vector kernels over L^-1.
 //
-// One appended point x (constant noise): k = K(X, x) / sl, l = U^-T k, d = sqrt(sf^2 / sl + sn2 / sn2_div - l.l),
+// One appended point x (noise variance sn2 >= sn2_div, so sl stays): k = K(X, x) / sl, l = U^-T k,
+//   d = sqrt(sf^2 / sl + sn2 / sn2_div - l.l),
 //   U' = [[U, l], [0, d]],   U'^-1 = [[U^-1, -U^-1 l / d], [0, 1 / d]],
 // written with the new row stride N + 1 into the buffers of the state under construction (never in place).
 #include <cmath>
@@ -274,10 +275,11 @@ __global__ __launch_bounds__(256) void gp_append_k_kernel(const double* __restri
 }
 
 // append: d_s = sqrt(sf^2 / sl + sn2 / sn2_div - l.l); dd = [d | -d | 1 / d] (S each).  d^2 not positive and finite sets flag[s].
+// sn2_new[s * sn2_stride]: the new point's noise variance in sample s.
 __global__ __launch_bounds__(256) void gp_append_d_kernel(const double* __restrict__ lvec, int N, int D,
                                                           const double* __restrict__ hyp_all, int P, const double* __restrict__ sl,
-                                                          const double* __restrict__ sn2, int S, double* __restrict__ dd,
-                                                          int* __restrict__ flag) {
+                                                          const double* __restrict__ sn2_new, size_t sn2_stride, int S,
+                                                          double* __restrict__ dd, int* __restrict__ flag) {
   const int s = blockIdx.x, tid = threadIdx.x;
   __shared__ double sP[256];
   double acc = 0.0;
@@ -293,7 +295,7 @@ __global__ __launch_bounds__(256) void gp_append_d_kernel(const double* __restri
   }
   if (tid == 0) {
     const double* hyp = hyp_all + (size_t)s * P;
-    const double a = exp(2.0 * hyp[D]) * exp(-0.0) / sl[s] + sn2[(size_t)s * N] / sl[s];  // the diagonal entry gp_cov_kernel forms
+    const double a = exp(2.0 * hyp[D]) * exp(-0.0) / sl[s] + sn2_new[(size_t)s * sn2_stride] / sl[s];  // the diagonal entry gp_cov_kernel forms
     const double d2 = a - sP[0];
     double d = 1.0;
     if (d2 > 0.0 && d2 < INFINITY)
@@ -378,7 +380,8 @@ GpAppendWs gp_post_append_ws(int S, int N) {
   return w;
 }
 
-int launch_gp_post_append(vbmc_ctx* ctx, const GpState& o, double y_new, const GpAppendWs& ws) {
+int launch_gp_post_append(vbmc_ctx* ctx, const GpState& o, double y_new, const double* d_sn2_new, size_t sn2_stride,
+                          const GpAppendWs& ws) {
   GpState& g = ctx->gp;
   const int N = o.N, S = o.S, N1 = N + 1, nb = (N + PB - 1) / PB;
   const Scratch& sc = ws.sc;
@@ -390,7 +393,7 @@ int launch_gp_post_append(vbmc_ctx* ctx, const GpState& o, double y_new, const G
                      y_new, (const double*)o.d_hyp, o.P, o.mean_kind, (const double*)o.d_sl, kvec, rnew);
   hipLaunchKernelGGL(trmv_t_kernel, dim3(nb, S), dim3(256), 0, ctx->stream, (const double*)o.d_Linv, N, (const double*)kvec, lvec);
   hipLaunchKernelGGL(gp_append_d_kernel, dim3(S), dim3(256), 0, ctx->stream, (const double*)lvec, N, o.D, (const double*)o.d_hyp,
-                     o.P, (const double*)o.d_sl, (const double*)o.d_sn2, S, dd, d_flag);
+                     o.P, (const double*)o.d_sl, d_sn2_new, sn2_stride, S, dd, d_flag);
   hipLaunchKernelGGL(trmv_kernel, dim3(nb, S), dim3(256), 0, ctx->stream, (const double*)o.d_Linv, N, (const double*)lvec,
                      (const double*)(dd + S), uvec);
   const dim3 rg((N1 + 255) / 256, N1, S);

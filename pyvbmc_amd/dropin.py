@@ -310,3 +310,71 @@ def unpatch_whitening(mod):
             setattr(mod, n, ref)
     delattr(mod, _SAVED_WARP)
     return mod
+
+
+_SAVED_LOOP = "_pyvbmc_amd_saved_active_sample"
+_LOOP_DEFAULTS = ("rng", "seed", "n_starts")
+
+
+def patch_active_sample_loop(mod=None, **defaults):
+    """Rebind ``active_sample`` on ``mod`` (default: ``pyvbmc.vbmc.vbmc``, which binds the name by value, vbmc.py:26) to
+    ``pyvbmc_amd.active_sample.active_sample``, the driver of the device calls, with the reference's function behind it
+    for ``_lib.UnsupportedShape`` / ``_lib.NoDeviceError``: the driver refuses before its first side effect, so the
+    reference starts from untouched state.  ``timer``, ``train_gp`` and ``optimize_vp`` are the reference's own
+    (``pyvbmc.timer.main_timer``, ``gaussian_process_train.train_gp``, ``variational_optimization.optimize_vp`` -- the
+    last looked up at call time, so ``patch()`` applies to it), taken from ``mod`` where it carries them.  ``defaults``:
+    the driver's ``rng``, ``seed``, ``n_starts``.  Opt-in (neither ``patch()`` nor ``patch_active_sampling()`` calls it)
+    and idempotent; returns ``mod``."""
+    from .active_sample import active_sample as _loop
+
+    unknown = set(defaults) - set(_LOOP_DEFAULTS)
+    if unknown:
+        raise TypeError(f"patch_active_sample_loop: unknown defaults {sorted(unknown)} (rng, seed, n_starts)")
+    if mod is None:
+        import importlib
+
+        mod = importlib.import_module("pyvbmc.vbmc.vbmc")
+    if hasattr(mod, _SAVED_LOOP):
+        unpatch_active_sample_loop(mod)
+    ref = getattr(mod, "active_sample", None)
+    setattr(mod, _SAVED_LOOP, ref)
+
+    def _from_reference(name, module, attr):
+        if getattr(mod, name, None) is not None:
+            return getattr(mod, name)
+        try:
+            import importlib
+
+            return getattr(importlib.import_module(module), attr)
+        except ImportError:
+            return None
+
+    def active_sample(gp, sample_count, optim_state, function_logger, iteration_history, vp, options):
+        kw = dict(defaults)
+        kw["timer"] = _from_reference("timer", "pyvbmc.timer", "main_timer")
+        kw["train_gp"] = _from_reference("train_gp", "pyvbmc.vbmc.gaussian_process_train", "train_gp")
+        kw["optimize_vp"] = _from_reference("optimize_vp", "pyvbmc.vbmc.variational_optimization", "optimize_vp")
+        try:
+            return _loop(gp, sample_count, optim_state, function_logger, iteration_history, vp, options, **kw)
+        except (_lib.UnsupportedShape, _lib.NoDeviceError):
+            if not callable(ref):
+                raise
+            return ref(gp, sample_count, optim_state, function_logger, iteration_history, vp, options)
+
+    active_sample.__doc__ = _loop.__doc__
+    active_sample.__wrapped__ = _loop
+    mod.active_sample = active_sample
+    return mod
+
+
+def unpatch_active_sample_loop(mod):
+    """Put back what ``patch_active_sample_loop`` replaced."""
+    if not hasattr(mod, _SAVED_LOOP):
+        return mod
+    ref = getattr(mod, _SAVED_LOOP)
+    if ref is None:
+        delattr(mod, "active_sample")
+    else:
+        mod.active_sample = ref
+    delattr(mod, _SAVED_LOOP)
+    return mod

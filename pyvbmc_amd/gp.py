@@ -14,6 +14,9 @@ names so the hot-path functions accept either it or a real ``gpyreg.GP``:
 * ``update(..., device=True)``, ``append`` and ``device_posterior`` build the same records on the device instead
   (vbmc_gp_posterior / vbmc_gp_append: batched FP64 Cholesky, one-point append) and leave them installed there, so
   the ``upload_gp`` that follows ships nothing.  Opt-in: the default path and its bits are unchanged.
+* ``append_point`` / ``reupdate``: the one-point append and the mirror of the reference's ``reupdate_gp`` for any GP duck
+  type ``device_posterior`` accepts, under user-provided noise too (vbmc_gp_append_noisy); what the active-sampling loop
+  (active_sample.py) calls after every acquired point.
 * ``log_marginal_likelihood`` / ``GP.log_likelihood``: the objective of hyper-parameter fitting and its gradient for a
   batch of candidates on the device (vbmc_gp_lml), with a NumPy / SciPy host route of the same formulas.
 * ``hyper_log_prior``, ``sample_hyperparameters`` and ``GP.fit`` / ``set_bounds`` / ``set_priors``: hyper-parameter
@@ -366,6 +369,147 @@ def fetch_posteriors(gp, ctx=None):
             p.L = L[s]
     _adopt(gp, ctx, dev=dev)
     return posts
+
+
+def _host_records(gp, hyp):
+    """The posterior records of a GP duck type on the host: ``GP._posterior``'s arithmetic, with the noise rule of
+    ``_noise_var`` and the mean by its kind.  For the ducks that have no ``_posterior`` of their own."""
+    X = np.atleast_2d(np.asarray(gp.X, dtype=np.float64))
+    y = np.ravel(gp.y)
+    N, D = X.shape
+    kind = mean_kind_of(gp)
+    posts = np.empty(len(hyp), dtype=object)
+    for i, h in enumerate(hyp):
+        Kxx = SquaredExponential().compute(h[: D + 1], X)
+        sn2 = _noise_var(gp, h[D + 1 : D + 2])
+        sn2_div = np.min(sn2)
+        resid = y - _mean_and_grad(kind, h[D + 2 :], X)[0]
+        if sn2_div >= 1e-6:
+            L = sla.cholesky(Kxx / sn2_div + np.diag(sn2 / sn2_div), lower=False)
+            alpha = sla.cho_solve((L, False), resid) / sn2_div
+            L_chol = True
+        else:
+            L_chol = False
+            L = -np.linalg.inv(Kxx + np.diag(sn2))
+            alpha = -L @ resid
+        posts[i] = SimpleNamespace(hyp=np.array(h, dtype=np.float64), alpha=alpha.reshape(-1, 1),
+                                   sW=np.ones(N) / np.sqrt(sn2_div), L=L, sn2_mult=1.0, L_chol=L_chol)
+    return posts
+
+
+def _rebuild(gp, hyp, ctx, device, fetch):
+    """The posterior records of ``gp`` from its present ``X``, ``y``, ``s2`` at the samples ``hyp``: on the device where
+    that route applies, else on the host (the GP's own ``_posterior`` where it has one)."""
+    if device and ctx is not None and device_posterior(gp, hyp, ctx=ctx, fetch=fetch):
+        return
+    if hasattr(gp, "_posterior"):
+        posts = np.empty(len(hyp), dtype=object)
+        for i, h in enumerate(hyp):
+            posts[i] = gp._posterior(h)
+        gp.posteriors = posts
+    else:
+        gp.posteriors = _host_records(gp, hyp)
+
+
+def _device_ctx(gp, ctx, device):
+    """The context of the device route, or None when ``device`` is off or there is no device."""
+    if not device:
+        return None
+    if ctx is None:
+        ctx = getattr(gp, "_ctx", None)
+    if ctx is None:
+        if _lib.device_count() <= 0:
+            return None
+        ctx = gp.ctx if isinstance(gp, GP) else _lib.default_context()
+    return ctx if ctx.device >= 0 else None
+
+
+def _s2_column(gp):
+    s2 = getattr(gp, "s2", None)
+    return None if s2 is None or not np.size(s2) else np.asarray(s2, dtype=np.float64).reshape(-1, 1)
+
+
+def append_point(gp, x_new, y_new, s2_new=None, *, ctx=None, device=True, fetch=True):
+    """Add ONE training point to a GP duck type (this package's ``GP``, an attribute-only stand-in or a real
+    ``gpyreg.GP`` -- whatever ``device_posterior`` accepts): ``gp.X``, ``gp.y`` and, under user-provided noise, ``gp.s2``
+    grow by a row and the posterior records follow at the present hyper-parameter samples.  This is gpyreg's
+    ``update(xnew, ynew)`` after an acquired point (vbmc/active_sample.py:584).
+
+    With ``device`` set and the context holding this GP's posterior as the device built it (``device_posterior``,
+    ``GP.update(device=True)`` or an earlier append), the factor, its inverse and ``alpha`` are extended on the device in
+    O(S N^2): ``vbmc_gp_append`` without ``s2``, ``vbmc_gp_append_noisy`` with it (the new point's noise variance per
+    sample from the GP's noise rule).  Where the entry refuses (the new point's noise is below the sample's ``sn2_div``,
+    the resident state is another GP's) and without a device, the records are rebuilt from the extended data.
+    ``s2_new`` is required exactly when the GP carries ``s2``.  ``fetch`` as in ``device_posterior``.  Returns ``gp``."""
+    X0 = np.atleast_2d(np.asarray(gp.X, dtype=np.float64))
+    x = _lib.f64(np.ravel(x_new))
+    if x.size != X0.shape[1]:
+        raise ValueError("append: x_new must be one point of the GP's dimension")
+    s2_old = _s2_column(gp)
+    if (s2_old is None) != (s2_new is None):
+        raise ValueError("append: s2_new is given exactly when the GP carries user-provided noise (gp.s2)")
+    y = float(np.ravel(y_new)[0])
+    X1 = np.vstack([X0, x[None, :]])
+    y1 = np.vstack([np.asarray(gp.y, dtype=np.float64).reshape(-1, 1), [[y]]])
+    s2_1 = None if s2_new is None else np.vstack([s2_old, [[float(np.ravel(s2_new)[0])]]])
+    posts = gp.posteriors
+    hyp = np.stack([np.ravel(p.hyp) for p in posts])
+    ctx = _device_ctx(gp, ctx, device)
+    dev_key = getattr(ctx, "_gp_dev", None) if ctx is not None else None
+    if dev_key is not None and dev_key == _gp_fingerprint(gp, ctx)[0]:
+        S, N1, D = len(posts), X1.shape[0], X1.shape[1]
+        alpha = np.empty((S, N1))
+        L = np.empty((S, N1, N1)) if fetch else None
+        if s2_1 is None:
+            rc = ctx._lib.vbmc_gp_append(ctx._h, _lib.ptr(x), y, _lib.ptr(alpha), _lib.ptr(L))
+        else:
+            probe = SimpleNamespace(X=x[None, :], y=np.array([[y]]), s2=s2_1[-1:], noise=getattr(gp, "noise", None))
+            sn2_new = _lib.f64([_noise_var(probe, h[D + 1 : D + 2])[0] for h in hyp])
+            rc = ctx._lib.vbmc_gp_append_noisy(ctx._h, _lib.ptr(x), y, _lib.ptr(sn2_new), _lib.ptr(alpha), _lib.ptr(L))
+        if rc != _lib.E_UNSUP:
+            ctx.check(rc)
+            gp.X, gp.y = X1, y1
+            if s2_1 is not None:
+                gp.s2 = s2_1
+            gp.posteriors = _records(hyp, alpha, L, [np.ravel(p.sW)[0] for p in posts])
+            _adopt(gp, ctx, dev=True)
+            return gp
+    gp.X, gp.y, gp.s2 = X1, y1, s2_1
+    _rebuild(gp, hyp, ctx, device, fetch)
+    return gp
+
+
+def training_data(function_logger):
+    """``(X, y, s2)`` of the evaluated points of a function logger (reference gaussian_process_train.py
+    ``_get_training_data``, :739-772): ``s2 = S^2`` where the logger's ``noise_flag`` is set, else None."""
+    flag = function_logger.X_flag
+    X = np.array(function_logger.X[flag], dtype=np.float64)
+    y = np.array(function_logger.y[flag], dtype=np.float64).reshape(-1, 1)
+    S = getattr(function_logger, "S", None)
+    if S is None or not getattr(function_logger, "noise_flag", True):
+        return X, y, None
+    return X, y, (np.asarray(S[flag], dtype=np.float64) ** 2).reshape(-1, 1)
+
+
+def reupdate(function_logger, gp, *, ctx=None, device=True, fetch=True):
+    """Mirror of ``reupdate_gp`` (reference gaussian_process_train.py:817-842): the GP takes the logger's training data
+    and its posterior records are rebuilt at the present hyper-parameter samples (``device_posterior``, else the host).
+    Where the logger holds exactly the GP's data plus ONE new row evaluated once, the call is ``append_point`` instead
+    (O(S N^2), under per-point noise too).  Returns ``gp``."""
+    X, y, s2 = training_data(function_logger)
+    X0 = np.atleast_2d(np.asarray(gp.X, dtype=np.float64))
+    N = X0.shape[0]
+    s2_old = _s2_column(gp)
+    one_more = (X.shape[0] == N + 1 and (s2 is None) == (s2_old is None) and np.array_equal(X[:N], X0)
+                and np.array_equal(y[:N], np.asarray(gp.y, dtype=np.float64).reshape(-1, 1))
+                and (s2 is None or np.array_equal(s2[:N], s2_old))
+                and np.ravel(function_logger.n_evals[function_logger.X_flag])[N] == 1)
+    if one_more:
+        return append_point(gp, X[N], y[N, 0], None if s2 is None else s2[N, 0], ctx=ctx, device=device, fetch=fetch)
+    hyp = np.stack([np.ravel(p.hyp) for p in gp.posteriors])
+    gp.X, gp.y, gp.s2 = X, y, s2
+    _rebuild(gp, hyp, _device_ctx(gp, ctx, device), device, fetch)
+    return gp
 
 
 def _mean_and_grad(kind, hm, X):
@@ -775,39 +919,17 @@ class GP:
             posts[i] = self._posterior(h)
         self.posteriors = posts
 
-    def append(self, x_new, y_new, *, device=True, fetch=True):
-        """Add ONE training point: ``X``, ``y`` grow by a row and the posterior records follow.
+    def append(self, x_new, y_new, s2_new=None, *, device=True, fetch=True):
+        """Add ONE training point: ``X``, ``y`` (and ``s2``) grow by a row and the posterior records follow.
 
         This class's ``update(X_new, y_new)`` REPLACES the training data; gpyreg's ``update(xnew, ynew)`` -- what the
         reference calls after every acquired point (vbmc/active_sample.py:584) -- APPENDS to it.  ``append`` is that
-        call for this class.  With ``device=True`` and the context holding this GP's posterior as the device built it
-        (``update(device=True)``, ``device_posterior`` or an earlier ``append``) under constant noise, the factor, its
-        inverse and ``alpha`` are extended on the device in O(S N^2) (vbmc_gp_append); otherwise the call is
-        ``update`` on the extended data.  ``fetch`` as in ``device_posterior``."""
-        x = _lib.f64(np.ravel(x_new))
-        if x.size != self.X.shape[1]:
-            raise ValueError("append: x_new must be one point of the GP's dimension")
-        if self.s2 is not None:
-            raise NotImplementedError("append under user-provided noise: call update with the extended X, y, s2")
-        y = float(np.ravel(y_new)[0])
-        X1 = np.vstack([self.X, x[None, :]])
-        y1 = np.vstack([self.y, [[y]]])
-        ctx = self.ctx
-        posts = self.posteriors
-        hyp = np.stack([p.hyp for p in posts])
-        dev_key = getattr(ctx, "_gp_dev", None)
-        if device and dev_key is not None and dev_key == _gp_fingerprint(self, ctx)[0]:
-            S, N1 = len(posts), X1.shape[0]
-            alpha = np.empty((S, N1))
-            L = np.empty((S, N1, N1)) if fetch else None
-            rc = ctx._lib.vbmc_gp_append(ctx._h, _lib.ptr(x), y, _lib.ptr(alpha), _lib.ptr(L))
-            if rc != _lib.E_UNSUP:
-                ctx.check(rc)
-                self.X, self.y = X1, y1
-                self.posteriors = _records(hyp, alpha, L, [p.sW[0] for p in posts])
-                _adopt(self, ctx, dev=True)
-                return
-        self.update(X1, y1, None, hyp, device=device, fetch=fetch)
+        call for this class: ``append_point(self, ...)``.  With ``device=True`` and the context holding this GP's
+        posterior as the device built it (``update(device=True)``, ``device_posterior`` or an earlier ``append``), the
+        factor, its inverse and ``alpha`` are extended on the device in O(S N^2) (vbmc_gp_append; under user-provided
+        noise, with ``s2_new``, vbmc_gp_append_noisy); otherwise the call is ``update`` on the extended data.  ``fetch``
+        as in ``device_posterior``."""
+        append_point(self, x_new, y_new, s2_new, ctx=self.ctx if device else None, device=device, fetch=fetch)
 
     def log_likelihood(self, hyp=None, grad=False, *, device=True):
         """``log_marginal_likelihood`` of this GP: ``hyp`` (B, P), default the present records' samples."""
