@@ -132,7 +132,8 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on);
  *        9 = vbmc_search_fill's uploads and launches, 10 = vbmc_search_eval's acquisition, noise lookup and mask,
  *        11 = its sort and gather,
  *        12 = vbmc_gp_hyp_sample: all the rounds of the last call (a call that launched nothing leaves no record),
- *        13 = vbmc_search_cmaes: all the rounds of the last call, likewise. */
+ *        13 = vbmc_search_cmaes: all the rounds of the last call, likewise,
+ *        14 = vbmc_gp_hyp_optimize: all the rounds of the last call, likewise. */
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out);
 
 /* Host-side wall-clock breakdown (microseconds) of the most recent vbmc_neg_elcbo:
@@ -483,6 +484,43 @@ int vbmc_gp_hyp_sample(vbmc_ctx* ctx, int N, int D, int P, int mean_kind, const 
                        const double* ub_P, const double* prior_mu_P, const double* prior_sigma_P, const double* prior_df_P,
                        int n, int thin, int burn_in, uint64_t seed, double* hyp_CxnxP, double* logpost_Cxn,
                        double* logprior_Cxn, int64_t* stats_Cx4, int32_t* invalid_C);
+
+/* GP hyper-parameter optimisation: R quasi-Newton runs over phi(h) = -(lml(h) + log p(h)) inside [lb, ub], advanced in
+ * lockstep so that every evaluation round is one batch of R trial points for vbmc_gp_lml's factorisation, value and
+ * gradient kernels (csrc/gp_opt.hip).  lml, log p and the data and prior arguments are vbmc_gp_hyp_sample's; the
+ * derivative with respect to the noise parameter is that of constant additive noise.  The optimiser is this library's
+ * own limited-memory BFGS with a projected gradient and a backtracking search, stated in NumPy by tests/gp_opt_host.py
+ * and pyvbmc_amd/gp.py (it is not SciPy's L-BFGS-B), with g = grad phi:
+ *   x0 clipped into the box; phi(x0) not finite: the run is invalid.  Bound set B = {p : (x_p <= lb_p and g_p > 0) or
+ *   (x_p >= ub_p and g_p < 0) or lb_p = ub_p}, pg = g with the entries in B set to 0.  An iteration stops the run on
+ *   max |pg| <= tol_g (stop reason 1), then on the iteration count reaching max_iter (2); else d = -H pg by the two-loop
+ *   recursion over the stored pairs, oldest to newest, initial scaling s.y / y.y of the newest pair, entries in B set to
+ *   0; g.d >= 0 or no pairs: the history is dropped and d = -pg.  Trial points x_t = clip(x + t d, lb, ub), t = 1 with
+ *   pairs and min(1, 1 / sum |pg|) without, accepted when phi(x_t) is finite and phi(x_t) <= phi(x) + 1e-4 g.(x_t - x),
+ *   else t <- t / 2, at most 30 times (then stop reason 4); a trial that does not factorise is a rejection.  After an
+ *   accepted step the pair s = x_t - x, y = g_t - g is stored when s.y > 1e-10 |s| |y| (over the oldest when m are held),
+ *   and the run stops on phi_old - phi_new <= tol_f max(1, |phi_new|) (3).  Every trial is one value+gradient evaluation.
+ * A round is one advance launch (workgroup = run, one wave), then the factorisation and the value and gradient kernels on
+ * the staged state; the GP the context holds is not touched.  Runs beyond one chunk (vbmc_set_option "gp_lml_chunk") are
+ * processed chunk by chunk inside a round; the host reads back one count of unfinished runs every vbmc_set_option
+ * "gp_opt_rounds" rounds (default 4); at most 2 + 31 max_iter rounds are queued, and runs unfinished then are
+ * VBMC_E_HIP.  X, y, s2 go up once, the results come back in one copy.
+ * Outputs: hyp_RxP the final points, logpost_R = lml + log p there, grad_RxP its gradient there, stats_Rx4 = [iterations,
+ * evaluations, history resets, stop reason]; invalid_R[r] = 1 when phi(x0[r]) is not finite -- that run's outputs are
+ * zeros and the others are what they would be without it.  trace_cap > 0 (at most max_iter + 1): trace_iter
+ * [R][trace_cap][3 P + 3], row i = [x (P), phi, g (P), d (P), pairs held, 1 when d = -pg] of iteration i (the row of the
+ * point a run ends at has d = 0), and trace_eval [R][1 + 31 trace_cap][4], row e = [iteration, t, phi_trial, accepted] of
+ * evaluation e (row 0 the start's); rows not reached are zeros.  trace_cap = 0: both may be null.  A run's outputs
+ * depend on (data, x0[r], bounds, priors, max_iter, m, tol_g, tol_f) alone: not on R, the chunking, the rounds per read
+ * or the trace.
+ * VBMC_E_UNSUP, before any launch: D > 32, one candidate's factor state exceeds the cap, or
+ * exp(2 lb[D+1]) + min s2 < 1e-6.  VBMC_E_ARG: bad shapes, bounds that are not finite or lb > ub (lb = ub fixes the
+ * parameter), a prior with sigma <= 0 or df <= 0, max_iter < 0, m outside [1, 16], a negative tolerance. */
+int vbmc_gp_hyp_optimize(vbmc_ctx* ctx, int N, int D, int P, int mean_kind, const double* X_NxD, const double* y_N,
+                         const double* s2_N, int R, const double* x0_RxP, const double* lb_P, const double* ub_P,
+                         const double* prior_mu_P, const double* prior_sigma_P, const double* prior_df_P, int max_iter, int m,
+                         double tol_g, double tol_f, int trace_cap, double* hyp_RxP, double* logpost_R, double* grad_RxP,
+                         int64_t* stats_Rx4, int32_t* invalid_R, double* trace_iter, double* trace_eval);
 
 /* ---- a8: vbmc/variational_optimization.py:1238-1606 _gp_log_joint ------- */
 

@@ -26,6 +26,7 @@ T_ENTMC, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T
 T_SEARCH_FILL, T_SEARCH_EVAL, T_SEARCH_SORT = 9, 10, 11
 T_GP_HYP = 12
 T_SEARCH_CMAES = 13
+T_GP_OPT = 14
 
 
 class VbmcHipError(RuntimeError):
@@ -205,6 +206,11 @@ SIGNATURES = {
         C.c_int,
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
          C.c_int, C.c_uint64, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
+    ),
+    "vbmc_gp_hyp_optimize": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
+         C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, _dp],
     ),
     "vbmc_gp_log_joint": (
         C.c_int,

@@ -29,6 +29,8 @@ SOURCES = [
     "api_gp_lml.hip",
     "gp_hyp.hip",
     "api_gp_hyp.hip",
+    "gp_opt.hip",
+    "api_gp_opt.hip",
     "api_elbo.hip",
     "api_batch.hip",
     "adam.hip",

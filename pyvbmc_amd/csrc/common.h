@@ -148,9 +148,10 @@ struct ElboScratch {
 // The timed intervals of vbmc_last_kernel_ms (the numbers are ABI): entmc, glj, pdf, predict, elbo, predict's variance
 // product (timing level 2 only), the GP posterior's factorisation, the MCMC chains of vbmc_is_mcmc, one chunk of
 // vbmc_gp_lml (factorisation and gradient kernels), the three phases of the acquisition search (vbmc_search_fill's
-// launches; vbmc_search_eval's acquisition and mask; its sort and gather), all the rounds of one vbmc_gp_hyp_sample, all the rounds of one vbmc_search_cmaes
+// launches; vbmc_search_eval's acquisition and mask; its sort and gather), all the rounds of one vbmc_gp_hyp_sample, all the rounds of one vbmc_search_cmaes,
+// all the rounds of one vbmc_gp_hyp_optimize
 enum TimingPair { T_ENTMC = 0, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML, T_SEARCH_FILL,
-                  T_SEARCH_EVAL, T_SEARCH_SORT, T_GP_HYP, T_SEARCH_CMAES, T_COUNT };
+                  T_SEARCH_EVAL, T_SEARCH_SORT, T_GP_HYP, T_SEARCH_CMAES, T_GP_OPT, T_COUNT };
 
 struct vbmc_ctx {
   int device = 0;
@@ -262,6 +263,7 @@ struct vbmc_ctx {
   int opt_is_mcmc_threads = 512;  // workgroup size of vbmc_is_mcmc's chains: 256, 512 or 768 (acq_is_mcmc.hip)
   int opt_gp_lml_chunk = 0;       // vbmc_gp_lml: n > 0 = candidates per chunk (test hook); 0 = the largest under the byte cap
   int opt_gp_hyp_rounds = 4;      // vbmc_gp_hyp_sample: rounds queued between two reads of the unfinished-chain count (test hook)
+  int opt_gp_opt_rounds = 4;      // vbmc_gp_hyp_optimize: rounds queued between two reads of the unfinished-run count
   int opt_cmaes_rounds = 8;       // vbmc_search_cmaes: rounds queued between two reads of the count of runs not yet stopped
   void (*release_cb)(void*) = nullptr;  // vbmc_set_release_callback
   void* release_cb_user = nullptr;
@@ -699,6 +701,30 @@ size_t gp_hyp_state_elems();  // doubles of one chain's state (zeroed by the cal
 int launch_gp_hyp_advance(vbmc_ctx* ctx, const GpHypArgs& a, int b0, int S);
 // *d_count = chains of [0, C) that have not finished
 int launch_gp_hyp_count(vbmc_ctx* ctx, const double* d_state, int C, int* d_count);
+// gp_opt.hip: the lockstep quasi-Newton runs of vbmc_gp_hyp_optimize over phi = -(lml + log prior).  One advance launch
+// moves the runs [b0, b0 + S) of a chunk on by one evaluation: run r consumes lml[r] / dlml[r][:] / flag[r] of the round
+// before and writes its next trial point into slot r - b0 of the buffers launch_gp_post_build reads, and that slot's
+// d sn2 / d log sn into dsn2[r - b0].  All pointers device memory.
+struct GpOptArgs {
+  int N = 0, D = 0, P = 0, R = 0, max_iter = 0, m = 0, trace_cap = 0;
+  double tol_g = 0.0, tol_f = 0.0;
+  double s2_min = 0.0;          // min_n s2_n (0 without user noise)
+  const double* s2 = nullptr;   // [N] user-provided noise variances, or null
+  const double *x0 = nullptr, *lb = nullptr, *ub = nullptr;  // [R][P], [P], [P]
+  const double *pmu = nullptr, *psig = nullptr, *pdf = nullptr, *pconst = nullptr;  // the prior, as GpHypArgs states it
+  const double *lml = nullptr, *dlml = nullptr;  // [R], [R][P]: the round before's value and gradient
+  int* flag = nullptr;          // [R] its factorisation flags: read, then cleared for the next build
+  double* dsn2 = nullptr;       // [chunk]
+  double* state = nullptr;      // [R][gp_opt_state_elems(P, m)], zeroed by the caller: a zeroed state is a run at its start
+  double *hyp_out = nullptr, *logpost = nullptr, *grad = nullptr;  // [R][P], [R], [R][P]
+  long long* stats = nullptr;   // [R][4]: iterations, evaluations, history resets, stop reason
+  int* invalid = nullptr;       // [R]
+  double *trace_it = nullptr, *trace_ev = nullptr;  // [R][trace_cap][3 P + 3], [R][1 + 31 trace_cap][4] (trace_cap > 0)
+  double *g_hyp = nullptr, *g_sl = nullptr, *g_smeta = nullptr, *g_sn2 = nullptr;  // the staged GP's [S][P], [S], [S][3], [S][N]
+};
+size_t gp_opt_state_elems(int P, int m);
+int launch_gp_opt_advance(vbmc_ctx* ctx, const GpOptArgs& a, int b0, int S);
+int launch_gp_opt_count(vbmc_ctx* ctx, const GpOptArgs& a, int* d_count);  // *d_count = runs of [0, R) that have not finished
 // api_gp.hip: the device buffers of a GP state of N points, D dimensions, S samples, P hyper-parameters, kept across GP
 // updates and only grown (capacity n + n / 8 + 64: active sampling makes N creep up by one); with_post: also what a
 // device-built posterior keeps (y, residuals, noise variances, sl)

@@ -356,6 +356,7 @@ int vbmc_set_option(vbmc_ctx* ctx, const char* key, int value) {
   else if (!strcmp(key, "is_mcmc_threads")) ctx->opt_is_mcmc_threads = value <= 256 ? 256 : value >= 768 ? 768 : 512;  // workgroup size of vbmc_is_mcmc's chains
   else if (!strcmp(key, "gp_lml_chunk")) ctx->opt_gp_lml_chunk = value < 0 ? 0 : value;  // vbmc_gp_lml: candidates per chunk (test hook); 0 = by the byte cap
   else if (!strcmp(key, "gp_hyp_rounds")) ctx->opt_gp_hyp_rounds = value < 1 ? 4 : value > 4096 ? 4096 : value;  // vbmc_gp_hyp_sample: rounds queued per read of the unfinished-chain count (test hook); < 1 = the default
+  else if (!strcmp(key, "gp_opt_rounds")) ctx->opt_gp_opt_rounds = value < 1 ? 4 : value > 4096 ? 4096 : value;  // vbmc_gp_hyp_optimize: rounds queued per read of the unfinished-run count; < 1 = the default
   else if (!strcmp(key, "cmaes_rounds")) ctx->opt_cmaes_rounds = value < 1 ? 8 : value > 4096 ? 4096 : value;  // vbmc_search_cmaes: rounds queued per read of the count of runs not yet stopped; < 1 = the default
   else if (!strcmp(key, "randn_device")) ctx->opt_randn_dev = value < 0 ? 0 : value > 3 ? 3 : value;  // vbmc_set_eps_numpy: the NumPy stream on the device (device_randn.hip); 0 = strict parity (host generator, values bit-identical to np.random.randn); 2 = test hook: the device pass reports its margin exceeded; 3 = test hook: the window is always computed, never taken from the pass before
   else if (!strcmp(key, "adam_tail")) ctx->opt_adam_tail = value;  // the optimiser loop's two-launch iteration (adam.hip)

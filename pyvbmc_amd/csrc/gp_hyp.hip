@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "fastmath.h"
+#include "gp_cand.h"
 #include "mixture_dev.h"
 
 namespace {
@@ -199,21 +200,11 @@ __global__ __launch_bounds__(256) void gp_hyp_advance_kernel(GpHypArgs a, int b0
   }
   __syncthreads();  // xp (global memory, written by lane 0)
 
-  // ---- 2. the candidate: xp with a coordinate that is not finite (an invalid start) replaced by its lower bound, so the
-  // factorisation of this slot never reads one
-  double h = 0.0;
+  // ---- 2. the candidate (gp_cand.h, shared with gp_opt.hip): xp with a coordinate that is not finite (an invalid start)
+  // replaced by its lower bound, so the factorisation of this slot never reads one
   if (tid < P) {
-    h = xp[tid];
-    if (!(fabs(h) < INFINITY)) h = a.lb[tid];
-    a.g_hyp[(size_t)slot * P + tid] = h;
-    // its term of the log prior
-    const double sg = a.psig[tid];
-    double t = 0.0;
-    if (sg == sg) {
-      const double z = (h - a.pmu[tid]) / sg, nu = a.pdf[tid];
-      t = nu == INFINITY ? a.pconst[tid] - 0.5 * (z * z) : a.pconst[tid] - 0.5 * (nu + 1.0) * fm::log_fast(1.0 + z * z / nu);
-    }
-    s_t[tid] = t;
+    const double h = gp_cand_coord(xp, a.lb, tid, slot, P, a.g_hyp);
+    s_t[tid] = gp_prior_term(a.pmu, a.psig, a.pdf, a.pconst, tid, h);  // its term of the log prior
   }
   __syncthreads();
   if (tid == 0) {
@@ -222,17 +213,7 @@ __global__ __launch_bounds__(256) void gp_hyp_advance_kernel(GpHypArgs a, int b0
     if (!cs.done) cs.pprior = lp;
   }
   // ---- 3. its noise: sn2_n = exp(2 h[D + 1]) + s2_n, sl = sn2_div = min_n sn2_n (sn2_mult = 1)
-  double hn = xp[D + 1];
-  if (!(fabs(hn) < INFINITY)) hn = a.lb[D + 1];
-  const double e = exp(2.0 * hn);
-  for (int n = tid; n < N; n += 256) a.g_sn2[(size_t)slot * N + n] = a.s2 ? e + a.s2[n] : e;
-  if (tid == 0) {
-    const double sl = e + a.s2_min;
-    a.g_sl[slot] = sl;
-    a.g_smeta[3 * slot] = 1.0;  // (L_chol, sn2_mult, 1 / sn2_eff)
-    a.g_smeta[3 * slot + 1] = 1.0;
-    a.g_smeta[3 * slot + 2] = 1.0 / sl;
-  }
+  gp_cand_noise<256>(tid, slot, N, D, xp, a.lb, a.s2, a.s2_min, a.g_sn2, a.g_sl, a.g_smeta);
 }
 
 __global__ __launch_bounds__(256) void gp_hyp_count_kernel(const double* __restrict__ state, int C, int state_elems,

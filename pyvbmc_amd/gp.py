@@ -19,6 +19,9 @@ names so the hot-path functions accept either it or a real ``gpyreg.GP``:
   (active_sample.py) calls after every acquired point.
 * ``log_marginal_likelihood`` / ``GP.log_likelihood``: the objective of hyper-parameter fitting and its gradient for a
   batch of candidates on the device (vbmc_gp_lml), with a NumPy / SciPy host route of the same formulas.
+* ``optimize_hyperparameters``: R box-constrained limited-memory BFGS runs over lml + log prior in lockstep on the device
+  (vbmc_gp_hyp_optimize), one batch of R trial points per evaluation round, with a NumPy host route of the same
+  algorithm; ``GP.fit(optimizer="lockstep")`` uses it for the optimiser stage.
 * ``hyper_log_prior``, ``sample_hyperparameters`` and ``GP.fit`` / ``set_bounds`` / ``set_priors``: hyper-parameter
   fitting.  The sampler runs C slice chains over lml + log prior in lockstep on the device (vbmc_gp_hyp_sample), one
   batch of C candidates per evaluation round, with a NumPy host route on the same draws.  The sampler, the priors and
@@ -830,6 +833,182 @@ def sample_hyperparameters(gp, x0, *, lb, ub, widths, priors=None, n=1, thin=1, 
                 log_priors=np.stack([hyper_log_prior(o[0], pri) for o in out]), stats=np.stack([o[2] for o in out]))
 
 
+# -------------------------------------------------------------------------------------- hyper-parameter optimisation
+_OPT_ARMIJO, _OPT_CURV, _OPT_HALVINGS = 1e-4, 1e-10, 30
+STOP_TOL_G, STOP_MAX_ITER, STOP_TOL_F, STOP_SEARCH = 1, 2, 3, 4
+
+
+def _lbfgs_run(fun, x0, lb, ub, max_iter, m, tol_g, tol_f, trace=None):
+    """One run of the package's box-constrained limited-memory BFGS on the host, the statement vbmc_gp_hyp_optimize runs
+    on the device (csrc/gp_opt.hip's header has the algorithm).  ``fun(x) -> (phi, g)``, phi = +inf where the point has
+    no finite value and gradient.  Returns ``(x, phi, g, stats)`` with stats = [iterations, evaluations, history
+    resets, stop reason]; ``ValueError("Invalid value.")`` when phi(x0) is not finite.  ``trace``: a dict that receives
+    the lists ``iters`` and ``evals`` (rows as vbmc_gp_hyp_optimize's traces)."""
+    x = np.maximum(np.minimum(np.array(x0, dtype=np.float64).ravel(), ub), lb)
+    P = x.size
+    if not np.all(np.isfinite(x)):
+        raise ValueError("Invalid value.")
+    phi, g = fun(x)
+    n_ev, n_it, n_reset = 1, 0, 0
+    if not np.isfinite(phi):
+        raise ValueError("Invalid value.")
+    it_rows, ev_rows = [], [[0.0, 0.0, phi, 1.0]]
+    S, Y, rho, gamma = [], [], [], 1.0  # the pairs, oldest first
+    fixed = lb == ub
+
+    def row(d, reset):
+        it_rows.append(np.concatenate([x, [phi], g, d, [float(len(S)), float(reset)]]))
+
+    while True:
+        in_b = ((x <= lb) & (g > 0)) | ((x >= ub) & (g < 0)) | fixed
+        pg = np.where(in_b, 0.0, g)
+        if np.max(np.abs(pg)) <= tol_g:
+            reason = STOP_TOL_G
+            row(np.zeros(P), 0)
+            break
+        if n_it >= max_iter:
+            reason = STOP_MAX_ITER
+            row(np.zeros(P), 0)
+            break
+        steepest = not S
+        if S:
+            q, al = pg.copy(), [0.0] * len(S)
+            for j in range(len(S) - 1, -1, -1):
+                al[j] = rho[j] * float(S[j] @ q)
+                q = q - al[j] * Y[j]
+            q = q * gamma
+            for j in range(len(S)):
+                be = rho[j] * float(Y[j] @ q)
+                q = q + S[j] * (al[j] - be)
+            d = np.where(in_b, 0.0, -q)
+            if not float(g @ d) < 0.0:
+                steepest, S, Y, rho = True, [], [], []
+                n_reset += 1
+        if steepest:
+            d = -pg
+            t = min(1.0, 1.0 / float(np.sum(np.abs(pg))))
+        else:
+            t = 1.0
+        row(d, int(steepest))
+        accepted = False
+        for _ in range(_OPT_HALVINGS + 1):
+            xt = np.maximum(np.minimum(x + t * d, ub), lb)
+            phit, gt = fun(xt)
+            n_ev += 1
+            accepted = bool(np.isfinite(phit) and phit <= phi + _OPT_ARMIJO * float(g @ (xt - x)))
+            ev_rows.append([float(n_it), t, phit, float(accepted)])
+            if accepted:
+                break
+            t *= 0.5
+        if not accepted:
+            reason = STOP_SEARCH
+            break
+        s, yv = xt - x, gt - g
+        sy, ss, yy = float(s @ yv), float(s @ s), float(yv @ yv)
+        if sy > _OPT_CURV * (math.sqrt(ss) * math.sqrt(yy)):
+            if len(S) == m:
+                S, Y, rho = S[1:], Y[1:], rho[1:]
+            S, Y, rho, gamma = S + [s], Y + [yv], rho + [1.0 / sy], sy / yy
+        phi_old, x, g, phi = phi, xt, gt, phit
+        n_it += 1
+        if phi_old - phi <= tol_f * max(1.0, abs(phi)):
+            reason = STOP_TOL_F
+            row(np.zeros(P), 0)
+            break
+    if trace is not None:
+        trace["iters"], trace["evals"] = np.array(it_rows), np.array(ev_rows)
+    return x, phi, g, np.array([n_it, n_ev, n_reset, reason], dtype=np.int64)
+
+
+def optimize_hyperparameters(gp, x0, *, lb, ub, priors=None, max_iter=200, history=8, tol_g=1e-5, tol_f=1e-9, device=True,
+                             ctx=None, trace=False):
+    """Maximise ``lml + log prior`` over the hyper-parameters of ``gp`` inside ``[lb, ub]``: R quasi-Newton runs, one per
+    row of ``x0`` (R, P), each independent of the others.
+
+    ``gp`` is read as ``log_marginal_likelihood`` reads it; ``lb``, ``ub`` finite (``lb == ub`` fixes a parameter);
+    ``priors`` as ``hyper_log_prior`` takes them.  The optimiser is the package's own box-constrained limited-memory BFGS
+    (``history`` pairs, 1 to 16; projected gradient; backtracking Armijo search of at most 30 halvings; csrc/gp_opt.hip's
+    header states it), not SciPy's L-BFGS-B.  A run stops on max |projected gradient| <= ``tol_g`` (reason 1), on
+    ``max_iter`` iterations (2), on a decrease of at most ``tol_f`` max(1, |value|) after an accepted step (3), or on an
+    exhausted line search (4).
+    ``device=True``: the runs advance in lockstep on the device (vbmc_gp_hyp_optimize), every evaluation round one batch
+    of R trial points through vbmc_gp_lml's factorisation and gradient kernels; the posterior the context holds is
+    untouched.  Shapes the device refuses (D > 32, a noise bound that allows sn2_div < 1e-6, noise that is not
+    constant-additive) and ``device=False`` run the same algorithm in NumPy over the host lml, run by run.
+    Returns ``dict(hyp (R, P), log_post (R,), grad (R, P), stats (R, 4))``: the final points, ``lml + log prior`` and its
+    gradient there, and [iterations, evaluations, history resets, stop reason]; with ``trace=True`` also ``trace``, a dict
+    ``iters`` (R, max_iter + 1, 3 P + 3), rows [x, phi, g, d, pairs held, reset flag], and ``evals`` (R, 1 + 31 (max_iter
+    + 1), 4), rows [iteration, t, phi_trial, accepted]; rows not reached are zeros.  ``ValueError("Invalid value.")`` when
+    a start has no finite value."""
+    X = _lib.f64(np.atleast_2d(gp.X))
+    y = _lib.f64(np.ravel(gp.y))
+    N, D = X.shape
+    kind = mean_kind_of(gp)
+    P = D + 2 + (0, 1, 1 + 2 * D)[kind]
+    x0 = _lib.f64(np.atleast_2d(x0))
+    if x0.ndim != 2 or x0.shape[1] != P or x0.shape[0] < 1:
+        raise ValueError(f"optimize_hyperparameters: x0 must be (R, {P})")
+    R = x0.shape[0]
+    lb, ub = (_lib.f64(np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), (P,)))) for a in (lb, ub))
+    if not (np.all(np.isfinite(lb)) and np.all(np.isfinite(ub)) and np.all(lb <= ub)):
+        raise ValueError("optimize_hyperparameters: finite bounds with lb <= ub are required")
+    max_iter, m, tol_g, tol_f = int(max_iter), int(history), float(tol_g), float(tol_f)
+    if max_iter < 0 or not 1 <= m <= 16 or not tol_g >= 0 or not tol_f >= 0:
+        raise ValueError("optimize_hyperparameters: max_iter >= 0, 1 <= history <= 16, tol_g >= 0, tol_f >= 0")
+    mu, sigma, df = (_lib.f64(a) for a in _prior_arrays(priors, P))
+    pri = {"mu": mu, "sigma": sigma, "df": df}
+    cap = max_iter + 1
+    n_evr = 1 + 31 * cap
+    const_form, s2 = _const_noise_form(gp)
+    if device and const_form:
+        ctx = (getattr(gp, "ctx", None) or _lib.default_context()) if ctx is None else ctx
+        hyp, lpost, grad = np.zeros((R, P)), np.zeros(R), np.zeros((R, P))
+        stats, invalid = np.zeros((R, 4), dtype=np.int64), np.zeros(R, dtype=np.int32)
+        t_it = np.zeros((R, cap, 3 * P + 3)) if trace else None
+        t_ev = np.zeros((R, n_evr, 4)) if trace else None
+        rc = ctx._lib.vbmc_gp_hyp_optimize(
+            ctx._h, N, D, P, kind, _lib.ptr(X), _lib.ptr(y), _lib.ptr(s2), R, _lib.ptr(x0), _lib.ptr(lb), _lib.ptr(ub),
+            _lib.ptr(mu), _lib.ptr(sigma), _lib.ptr(df), max_iter, m, tol_g, tol_f, cap if trace else 0, _lib.ptr(hyp),
+            _lib.ptr(lpost), _lib.ptr(grad), stats.ctypes.data_as(C.POINTER(C.c_int64)),
+            invalid.ctypes.data_as(C.POINTER(C.c_int32)), _lib.ptr(t_it), _lib.ptr(t_ev))
+        if rc != _lib.E_UNSUP:
+            ctx.check(rc)
+            if np.any(invalid):
+                raise ValueError("Invalid value.")
+            out = dict(hyp=hyp, log_post=lpost, grad=grad, stats=stats)
+            if trace:
+                out["trace"] = dict(iters=t_it, evals=t_ev)
+            return out
+
+    noise = getattr(gp, "noise", None)
+    const_add = True if noise is None or not hasattr(noise, "compute") else bool(getattr(noise, "constant_add", False))
+
+    def fun(h):
+        with np.errstate(all="ignore"):
+            sn2 = _noise_var(gp, h[D + 1 : D + 2])
+            dsn2 = 2.0 * np.exp(2 * h[D + 1]) if const_add else 0.0
+            lml, dl = _host_lml(X, y, kind, h, sn2, np.min(sn2), dsn2, True)
+            lp, dp = hyper_log_prior(h, pri, grad=True)
+            phi, g = -(lml + lp), -(dl + dp)
+        if not (np.isfinite(phi) and np.all(np.isfinite(g))):
+            return np.inf, np.zeros(P)
+        return float(phi), g
+
+    hyp, lpost, grad = np.zeros((R, P)), np.zeros(R), np.zeros((R, P))
+    stats = np.zeros((R, 4), dtype=np.int64)
+    t_it, t_ev = np.zeros((R, cap, 3 * P + 3)), np.zeros((R, n_evr, 4))
+    for r in range(R):
+        tr = {}
+        x, phi, g, stats[r] = _lbfgs_run(fun, x0[r], lb, ub, max_iter, m, tol_g, tol_f, trace=tr)
+        hyp[r], lpost[r], grad[r] = x, -phi, -g
+        t_it[r, : len(tr["iters"])] = tr["iters"]
+        t_ev[r, : len(tr["evals"])] = tr["evals"]
+    out = dict(hyp=hyp, log_post=lpost, grad=grad, stats=stats)
+    if trace:
+        out["trace"] = dict(iters=t_it, evals=t_ev)
+    return out
+
+
 # hyper-parameter blocks by gpyreg's names, in the layout of hyp: (name, first index, length) for a GP of dimension D
 def _hyp_blocks(D, mean_n):
     blocks = [("covariance_log_lengthscale", 0, D), ("covariance_log_outputscale", D, 1), ("noise_log_scale", D + 1, 1)]
@@ -1024,7 +1203,7 @@ class GP:
                 out[nm] = ("student_t", (mu, sigma, df))
         return out
 
-    def fit(self, X=None, y=None, s2=None, hyp0=None, options=None, *, device=True, seed=None):
+    def fit(self, X=None, y=None, s2=None, hyp0=None, options=None, *, device=True, seed=None, optimizer="scipy"):
         """Fit the hyper-parameters to the training data (``X``, ``y``, ``s2`` REPLACE the GP's when given) inside the
         bounds of ``set_bounds`` (finite ones are required) under the priors of ``set_priors``:
 
@@ -1032,7 +1211,10 @@ class GP:
            into the bounds, plus ``init_N`` uniform draws in the box from ``np.random.default_rng(seed)``; all of them are
            scored in ONE ``log_marginal_likelihood`` batch, plus the prior;
         2. SciPy L-BFGS-B inside the bounds from the best ``opts_N`` of them on -(lml + log prior) with its gradient
-           (tolerance ``tol_opt``); the best point seen is the optimum;
+           (tolerance ``tol_opt``); the best point seen is the optimum.  ``optimizer="lockstep"``: the best ``opts_N``
+           candidates with a finite score go to ONE ``optimize_hyperparameters`` call instead (``tol_g = tol_opt``; on the
+           device every evaluation round is one batch of ``opts_N`` trial points), and the best result is the optimum;
+           ``n_iterations`` is the sum over the runs;
         3. ``n_samples`` > 0: that many slice chains from the optimum, one kept sample each after ``burn`` sweeps and
            ``thin`` more (``sample_hyperparameters``; ``widths`` as given, else (ub - lb) / 8);
         4. ``update(hyp=samples, device=device)``: with the device route the posterior stays installed.
@@ -1078,9 +1260,20 @@ class GP:
                 return 1e100, np.zeros(P)
             return -(lml[0] + lp), -(dl[0] + dp)
 
+        if optimizer not in ("scipy", "lockstep"):
+            raise ValueError(f"GP.fit: optimizer '{optimizer}' is not 'scipy' or 'lockstep'")
         order = np.argsort(-score, kind="stable")
         best_h, best_f, n_it = cand[order[0]].copy(), float(score[order[0]]), 0
-        for i in order[: max(int(opts["opts_N"]), 0)]:
+        if optimizer == "lockstep":
+            starts = [i for i in order[: max(int(opts["opts_N"]), 0)] if np.isfinite(score[i])]
+            if starts:
+                res = optimize_hyperparameters(self, cand[starts], lb=lb, ub=ub, priors=pri, tol_g=float(opts["tol_opt"]),
+                                               device=device, ctx=ctx)
+                n_it = int(np.sum(res["stats"][:, 0]))
+                k = int(np.argmax(res["log_post"]))
+                if np.isfinite(res["log_post"][k]) and res["log_post"][k] > best_f:
+                    best_h, best_f = res["hyp"][k].copy(), float(res["log_post"][k])
+        for i in order[: max(int(opts["opts_N"]), 0) if optimizer == "scipy" else 0]:
             if not np.isfinite(score[i]):
                 continue
             res = sopt.minimize(neg, cand[i], jac=True, method="L-BFGS-B", bounds=list(zip(lb, ub)), tol=float(opts["tol_opt"]))
