@@ -27,6 +27,7 @@ SOURCES = [
     "api_gp_post.hip",
     "gp_lml.hip",
     "api_gp_lml.hip",
+    "lockstep.hip",
     "gp_hyp.hip",
     "api_gp_hyp.hip",
     "gp_opt.hip",

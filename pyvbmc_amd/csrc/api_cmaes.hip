@@ -1,9 +1,9 @@
 // C-ABI entry point of the CMA-ES refinement of the acquisition search: vbmc_search_cmaes (vbmc/active_sample.py:355-423
 // with search_optimizer = "cmaes").  R runs of cmaes.hip's optimiser in lockstep: a round is one advance launch, then the
 // scoring of the R lambda rows it wrote (round 0: the R starts) by api_search.hip's search_score_rows -- the launches
-// vbmc_search_eval runs on the resident search set.  The host queues opt_cmaes_rounds rounds, then reads ONE int (the runs
-// not yet stopped) and goes on while it is not zero.  Plain stream order: no graph capture, no device-side launch, no
-// waiting between workgroups, no atomics on global memory.  The bounds, the starts, the noise table and the weights go up
+// vbmc_search_eval runs on the resident search set.  The host queues opt_cmaes_rounds rounds between two reads of the
+// count of runs not yet stopped (lockstep_rounds, common.h; DESIGN.md "lockstep drivers").  Plain stream order: no graph
+// capture, no device-side launch, no waiting between workgroups, no atomics on global memory.  The bounds, the starts, the noise table and the weights go up
 // once; all outputs come back in one copy.
 //
 // The candidates have a buffer of their own in this call's scratch: the resident search set of a preceding
@@ -154,40 +154,28 @@ int cmaes_queue(vbmc_ctx* ctx, int kind, double y_max, double tol_gp_var, double
   a.x_best = p.sc.ptr(p_xb); a.f_best = p.sc.ptr(p_fb); a.f0 = p.sc.ptr(p_f0);
   a.mean = p.sc.ptr(p_mean); a.sigma = p.sc.ptr(p_sig); a.C = p.sc.ptr(p_C);
   a.stats = p.sc.ptr(p_stats);
-  int* d_count = p.sc.ptr(p_count);
-  int* h_count = (int*)ctx->h_pinned;
 
   // ---- rounds: the start, at most ceil(max_fevals / lambda) generations, and the advance that consumes the last values
   const long long max_rounds = 2 + (a.max_fevals + lam - 1) / lam;
-  const int per_batch = ctx->opt_cmaes_rounds;
   long long rounds = 0;
   int left = R;
-  while (left > 0 && rounds < max_rounds) {
-    for (int q = 0; q < per_batch && rounds < max_rounds; ++q, ++rounds) {
-      if ((rc = launch_cmaes_advance(ctx, a))) return rc;
-      if ((rc = search_score_rows(ctx, s, a.rows, rounds == 0 ? (int64_t)R : M, y_max, tol_gp_var, u, p.sc.ptr(p_val)))) return rc;
-    }
-    if ((rc = launch_cmaes_count(ctx, a, d_count))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(h_count, d_count, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, stream_wait(ctx));
-    left = *h_count;
-  }
+  auto round = [&](long long q) {
+    const int rq = launch_cmaes_advance(ctx, a);
+    return rq ? rq : search_score_rows(ctx, s, a.rows, q == 0 ? (int64_t)R : M, y_max, tol_gp_var, u, p.sc.ptr(p_val));
+  };
+  if ((rc = lockstep_rounds(ctx, "search_cmaes", ctx->opt_cmaes_rounds, max_rounds, R, a.state, cmaes_done_word(ly),
+                            p.sc.ptr(p_count), round, &rounds, &left)))
+    return rc;
   if ((rc = timing_end(ctx, T_SEARCH_CMAES))) return rc;
   if (left > 0) return vbmc_fail(ctx, VBMC_E_HIP, "search_cmaes: %d runs not stopped after %lld rounds", left, rounds);
-
-  // ---- the results, one copy (the pinned copy keeps the pieces' spacing)
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, a.x_best, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, stream_wait(ctx));
-  const double* hp = ctx->h_pinned;
-  const size_t o0 = p_xb.off;
-  if (x_best_RxD) memcpy(x_best_RxD, hp, sizeof(double) * rd);
-  if (f_best_R) memcpy(f_best_R, hp + (p_fb.off - o0), sizeof(double) * Rs);
-  if (f0_R) memcpy(f0_R, hp + (p_f0.off - o0), sizeof(double) * Rs);
-  if (mean_RxD) memcpy(mean_RxD, hp + (p_mean.off - o0), sizeof(double) * rd);
-  if (sigma_R) memcpy(sigma_R, hp + (p_sig.off - o0), sizeof(double) * Rs);
-  if (C_RxDxD) memcpy(C_RxDxD, hp + (p_C.off - o0), sizeof(double) * rd * D);
-  if (stats_Rx4) memcpy(stats_Rx4, hp + (p_stats.off - o0), sizeof(int64_t) * 4 * Rs);
-  return VBMC_OK;
+  return fetch_tail(ctx, p.sc, p_xb.off,
+                    {{p_xb.off, x_best_RxD, sizeof(double) * rd},
+                     {p_fb.off, f_best_R, sizeof(double) * Rs},
+                     {p_f0.off, f0_R, sizeof(double) * Rs},
+                     {p_mean.off, mean_RxD, sizeof(double) * rd},
+                     {p_sig.off, sigma_R, sizeof(double) * Rs},
+                     {p_C.off, C_RxDxD, sizeof(double) * rd * D},
+                     {p_stats.off, stats_Rx4, sizeof(int64_t) * 4 * Rs}});
 }
 
 }  // namespace

@@ -380,18 +380,6 @@ __global__ __launch_bounds__(256) void cmaes_advance_kernel(CmaesArgs a) {
   if (tid == 0) h.phase = CMA_WAIT_GEN;
 }
 
-__global__ __launch_bounds__(256) void cmaes_count_kernel(const double* __restrict__ state, int R, size_t state_elems,
-                                                          size_t head, int* __restrict__ count) {
-  __shared__ int s_n;
-  if (threadIdx.x == 0) s_n = 0;
-  __syncthreads();
-  int n = 0;
-  for (int r = threadIdx.x; r < R; r += 256) n += ((const CmaHead*)(state + (size_t)r * state_elems + head))->phase == CMA_DONE ? 0 : 1;
-  if (n) atomicAdd(&s_n, n);  // (LDS, integers: the order does not matter)
-  __syncthreads();
-  if (threadIdx.x == 0) *count = s_n;
-}
-
 }  // namespace
 
 int launch_cmaes_advance(vbmc_ctx* ctx, const CmaesArgs& a) {
@@ -404,10 +392,6 @@ int launch_cmaes_advance(vbmc_ctx* ctx, const CmaesArgs& a) {
   return 0;
 }
 
-int launch_cmaes_count(vbmc_ctx* ctx, const CmaesArgs& a, int* d_count) {
-  const CmaState ly(a.D, a.lam, a.hist);
-  hipLaunchKernelGGL(cmaes_count_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)a.state, a.R, ly.total, ly.head,
-                     d_count);
-  HIP_TRY(ctx, hipGetLastError());
-  return 0;
+LockstepWord cmaes_done_word(const CmaState& ly) {
+  return {ly.total, sizeof(double) * ly.head + offsetof(CmaHead, phase), CMA_DONE};
 }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vbmc_hip.h"
+#include "gp_cand_host.h"
 #include "scratch.h"
 #include "transform.h"
 
@@ -636,12 +637,6 @@ int launch_pad_linv(vbmc_ctx* ctx);
 // gp_post.hip: the posterior of ctx->gp's X, y, hyp, noise built in ctx->gp's buffers (covariance, blocked upper
 // Cholesky, L^-1, alpha); d_flag[s] != 0 afterwards: sample s met a pivot that is not a positive finite number
 int launch_gp_post_build(vbmc_ctx* ctx, double* d_Dinv, int* d_flag);
-// the per-sample flags at the head of a build's or an append's workspace (ctx->d_post_ws): S ints and a spare double
-inline Piece<int> gp_post_flags(Scratch& sc, int S) {
-  const Piece<int> p = sc.add<int>((size_t)S);
-  sc.add(1);
-  return p;
-}
 // the workspace of an append to S samples of N points, listed once: flags | kvec, lvec, uvec [S][N] | dd 3 S | rnew S |
 // tvec [S][N + 1]
 struct GpAppendWs {
@@ -655,76 +650,102 @@ GpAppendWs gp_post_append_ws(int S, int N);
 int launch_gp_post_append(vbmc_ctx* ctx, const GpState& from, double y_new, const double* d_sn2_new, size_t sn2_stride,
                           const GpAppendWs& ws);
 void gp_post_free(vbmc_ctx* ctx);
-// vbmc_gp_lml's chunk plan, stated once: the candidates factorised side by side.  A candidate's factor state is L, L^-1
-// (N^2 each), the padded copy of L^-1 (ld^2), the inverted diagonal blocks (nb 64^2) and the gradient's tile partials
-// (nb (nb + 1) / 2 tile pairs of D + 2 sums); the chunk is the largest whose state stays under cap_bytes, at most B, or
-// `forced` (> 0) where that is smaller.  0: not even one candidate fits.
-constexpr size_t GP_LML_CAP_BYTES = (size_t)1 << 30;
-inline size_t gp_lml_part_elems(int N, int D) {
-  const size_t nb = ((size_t)N + 63) / 64;
-  return nb * (nb + 1) / 2 * ((size_t)D + 2);
-}
-inline int gp_lml_plan(int N, int D, int B, size_t cap_bytes, int forced) {
-  const size_t nn = (size_t)N * N, ld = (size_t)(((size_t)N + 63) / 64 * 64), nb = ld / 64;
-  const size_t per = sizeof(double) * (2 * nn + ld * ld + nb * 64 * 64 + gp_lml_part_elems(N, D));
-  size_t chunk = cap_bytes / per;
-  if (chunk > (size_t)B) chunk = (size_t)B;
-  if (forced > 0 && (size_t)forced < chunk) chunk = (size_t)forced;
-  return (int)chunk;
-}
 // gp_lml.hip: value and gradient of the log marginal likelihood of ctx->gp's S candidates from the factor state
 // launch_gp_post_build left there.  d_sums [S][2], d_part [S][gp_lml_part_elems], d_mg [S][mean parameters]: workspace;
 // d_lml [S], d_dlml [S][P] (want_grad): results, device memory
 int launch_gp_lml(vbmc_ctx* ctx, int want_grad, const double* d_dsn2, double* d_sums, double* d_part, double* d_mg,
                   double* d_lml, double* d_dlml);
+// api_gp_lml.hip: the launching side of gp_cand_host.h, shared by vbmc_gp_lml and the lockstep entries.
+// gp_stage_data: the fields of the staged state w and the uploads that do not change from chunk to chunk (X, X^T, y).
+int gp_stage_data(vbmc_ctx* ctx, GpState& w, int N, int D, int P, int mean_kind, const double* X, const double* y);
+// gp_cand_begin: the device, the stream drained, ctx->gp_next grown for `chunk` candidates
+int gp_cand_begin(vbmc_ctx* ctx, int N, int D, int P, int chunk);
+// gp_lml_chunk: S candidates, staged in ctx->gp_next, through the factorisation and the value (and gradient) kernels;
+// their flags, lml and dlml go to slots [slot0, slot0 + S) of ws.  ctx->gp_next is swapped in as ctx->gp for the launches
+// and swapped back on every path.
+int gp_lml_chunk(vbmc_ctx* ctx, const Scratch& sc, const GpLmlWs& ws, int S, int slot0);
+// gp_cand_stage: a lockstep entry's uploads, once per call -- X, X^T, y and the packed `in` block to d_in -- ws's cleared
+// range and the entry's own pieces [own_off, sc.total) zeroed (count, a zeroed state = every run at its start, zeros
+// where an invalid run writes nothing), and a's lml, flag and g_* wired.  A failure has waited for the stream.
+int gp_cand_stage(vbmc_ctx* ctx, const char* who, const Scratch& sc, const GpLmlWs& ws, double* d_in,
+                  const std::vector<double>& in, size_t own_off, int mean_kind, const double* X, const double* y, GpCandArgs& a);
+// One round of a lockstep entry: per chunk of the runs, advance(b0, S) -> rc moves the runs [b0, b0 + S) on by one
+// evaluation and leaves their candidates in the staged GP, then gp_lml_chunk evaluates them.
+template <class Advance>
+int gp_cand_round(vbmc_ctx* ctx, const Scratch& sc, const GpLmlWs& ws, int runs, int chunk, Advance advance) {
+  int rc = 0;
+  for (int b0 = 0; b0 < runs && !rc; b0 += chunk) {
+    const int S = runs - b0 < chunk ? runs - b0 : chunk;
+    if (!(rc = advance(b0, S))) rc = gp_lml_chunk(ctx, sc, ws, S, b0);
+  }
+  return rc;
+}
+// lockstep.hip.  Where a run's "finished" word sits: each state's owner states it next to its state's size.
+struct LockstepWord {
+  size_t state_elems = 0, offset_bytes = 0;  // doubles of one run's state; the 32-bit word's offset in it
+  int done_value = 0;
+};
+// *d_count = the runs of [0, n_runs) whose word is not done_value
+int launch_lockstep_count(vbmc_ctx* ctx, const double* d_state, int n_runs, size_t state_elems, size_t word_offset_bytes,
+                          int done_value, int* d_count);
+// The rounds of a lockstep entry (DESIGN.md "lockstep drivers"): round_fn(rounds) -> rc queues one round; after per_batch
+// of them (never past max_rounds) the count is launched, ONE int comes back through ctx->h_pinned and the host goes on
+// while it is not zero.  Returns the first rc; the failure epilogue and the "unfinished" message are the caller's.
+template <class RoundFn>
+int lockstep_rounds(vbmc_ctx* ctx, const char* what, int per_batch, long long max_rounds, int n_runs, const double* d_state,
+                    const LockstepWord& word, int* d_count, RoundFn round_fn, long long* rounds, int* left) {
+  int rc = 0;
+  *rounds = 0;
+  *left = n_runs;
+  while (*left > 0 && *rounds < max_rounds) {
+    for (int q = 0; q < per_batch && *rounds < max_rounds; ++q, ++*rounds)
+      if ((rc = round_fn(*rounds))) return rc;
+    if ((rc = launch_lockstep_count(ctx, d_state, n_runs, word.state_elems, word.offset_bytes, word.done_value, d_count)))
+      return rc;
+    hipError_t e = hipMemcpyAsync(ctx->h_pinned, d_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = stream_wait(ctx);
+    if (e != hipSuccess) return vbmc_fail(ctx, VBMC_E_HIP, "%s: %s", what, hipGetErrorString(e));
+    *left = *(const int*)ctx->h_pinned;
+  }
+  return 0;
+}
+// A call's results in one copy: the tail [from, sc.total) of its scratch to ctx->h_pinned (the caller's ensure_pinned; the
+// pinned copy keeps the pieces' spacing), one wait, then each piece to its host array; a null dst is skipped.
+struct FetchPiece {
+  size_t off;  // the piece's offset in the scratch, doubles
+  void* dst;
+  size_t bytes;
+};
+int fetch_tail(vbmc_ctx* ctx, const Scratch& sc, size_t from, std::initializer_list<FetchPiece> pieces);
 // gp_hyp.hip: the lockstep slice chains of vbmc_gp_hyp_sample over lml + log prior.  One advance launch moves the chains
 // [b0, b0 + S) of a chunk on by one evaluation: chain c consumes lml[c] / flag[c] of the round before and writes its next
 // candidate into slot c - b0 of the buffers launch_gp_post_build reads.  All pointers device memory.
-struct GpHypArgs {
-  int N = 0, D = 0, P = 0, C = 0, n = 0, thin = 0, burn_in = 0;
+struct GpHypArgs : GpCandArgs {
+  int C = 0, n = 0, thin = 0, burn_in = 0;
   uint64_t seed = 0;
-  double s2_min = 0.0;          // min_n s2_n (0 without user noise)
-  const double* s2 = nullptr;   // [N] user-provided noise variances, or null
-  const double *x0 = nullptr, *widths = nullptr, *lb = nullptr, *ub = nullptr;  // [C][P], [P] each
-  // the prior per parameter: location, scale (NaN: none), degrees of freedom (+inf: Gaussian), the constant part of t_p
-  const double *pmu = nullptr, *psig = nullptr, *pdf = nullptr, *pconst = nullptr;
-  const double* lml = nullptr;  // [C] the value the round before produced
-  int* flag = nullptr;          // [C] its factorisation flags: read, then cleared for the next build
+  const double* widths = nullptr;      // [P]
   double *x = nullptr, *xp = nullptr;  // [C][P] the chain's point; the point under evaluation
-  double* state = nullptr;      // [C][gp_hyp_state_elems()]
   double *hyp_out = nullptr, *logpost = nullptr, *logprior = nullptr;  // [C][n][P], [C][n], [C][n]
-  long long* stats = nullptr;   // [C][4]
-  int* invalid = nullptr;       // [C]
-  double *g_hyp = nullptr, *g_sl = nullptr, *g_smeta = nullptr, *g_sn2 = nullptr;  // the staged GP's [S][P], [S], [S][3], [S][N]
 };
-size_t gp_hyp_state_elems();  // doubles of one chain's state (zeroed by the caller: a zeroed state is a chain at its start)
+size_t gp_hyp_state_elems();  // doubles of one chain's state
+LockstepWord gp_hyp_done_word();
 int launch_gp_hyp_advance(vbmc_ctx* ctx, const GpHypArgs& a, int b0, int S);
-// *d_count = chains of [0, C) that have not finished
-int launch_gp_hyp_count(vbmc_ctx* ctx, const double* d_state, int C, int* d_count);
 // gp_opt.hip: the lockstep quasi-Newton runs of vbmc_gp_hyp_optimize over phi = -(lml + log prior).  One advance launch
 // moves the runs [b0, b0 + S) of a chunk on by one evaluation: run r consumes lml[r] / dlml[r][:] / flag[r] of the round
 // before and writes its next trial point into slot r - b0 of the buffers launch_gp_post_build reads, and that slot's
 // d sn2 / d log sn into dsn2[r - b0].  All pointers device memory.
-struct GpOptArgs {
-  int N = 0, D = 0, P = 0, R = 0, max_iter = 0, m = 0, trace_cap = 0;
+struct GpOptArgs : GpCandArgs {
+  int R = 0, max_iter = 0, m = 0, trace_cap = 0;
   double tol_g = 0.0, tol_f = 0.0;
-  double s2_min = 0.0;          // min_n s2_n (0 without user noise)
-  const double* s2 = nullptr;   // [N] user-provided noise variances, or null
-  const double *x0 = nullptr, *lb = nullptr, *ub = nullptr;  // [R][P], [P], [P]
-  const double *pmu = nullptr, *psig = nullptr, *pdf = nullptr, *pconst = nullptr;  // the prior, as GpHypArgs states it
-  const double *lml = nullptr, *dlml = nullptr;  // [R], [R][P]: the round before's value and gradient
-  int* flag = nullptr;          // [R] its factorisation flags: read, then cleared for the next build
-  double* dsn2 = nullptr;       // [chunk]
-  double* state = nullptr;      // [R][gp_opt_state_elems(P, m)], zeroed by the caller: a zeroed state is a run at its start
+  const double* dlml = nullptr;  // [R][P]: the round before's gradient
+  double* dsn2 = nullptr;        // [chunk]
   double *hyp_out = nullptr, *logpost = nullptr, *grad = nullptr;  // [R][P], [R], [R][P]
-  long long* stats = nullptr;   // [R][4]: iterations, evaluations, history resets, stop reason
-  int* invalid = nullptr;       // [R]
+  // stats [R][4]: iterations, evaluations, history resets, stop reason
   double *trace_it = nullptr, *trace_ev = nullptr;  // [R][trace_cap][3 P + 3], [R][1 + 31 trace_cap][4] (trace_cap > 0)
-  double *g_hyp = nullptr, *g_sl = nullptr, *g_smeta = nullptr, *g_sn2 = nullptr;  // the staged GP's [S][P], [S], [S][3], [S][N]
 };
 size_t gp_opt_state_elems(int P, int m);
+LockstepWord gp_opt_done_word(int P, int m);
 int launch_gp_opt_advance(vbmc_ctx* ctx, const GpOptArgs& a, int b0, int S);
-int launch_gp_opt_count(vbmc_ctx* ctx, const GpOptArgs& a, int* d_count);  // *d_count = runs of [0, R) that have not finished
 // api_gp.hip: the device buffers of a GP state of N points, D dimensions, S samples, P hyper-parameters, kept across GP
 // updates and only grown (capacity n + n / 8 + 64: active sampling makes N creep up by one); with_post: also what a
 // device-built posterior keeps (y, residuals, noise variances, sl)
@@ -872,7 +893,7 @@ struct CmaesArgs {
   long long* stats = nullptr;   // [R][4]: generations, evaluations, stop reason, generation of the best
 };
 int launch_cmaes_advance(vbmc_ctx* ctx, const CmaesArgs& a);
-int launch_cmaes_count(vbmc_ctx* ctx, const CmaesArgs& a, int* d_count);  // *d_count = runs not yet stopped
+LockstepWord cmaes_done_word(const CmaState& ly);  // a run has stopped
 // acq_is_mcmc.hip: the S slice-sampling chains of active_importance_sampling's step 2, one workgroup each, on ctx->stream
 // (all pointers device memory; d_invalid [S] zeroed by the caller), and the dynamic LDS a workgroup of `threads` needs
 size_t is_mcmc_lds_bytes(int N, int threads);

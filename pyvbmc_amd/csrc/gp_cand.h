@@ -8,7 +8,7 @@
 #include "fastmath.h"
 
 // t_p of parameter p at h: 0 without a prior (sigma NaN), else with z = (h - mu_p) / sigma_p
-//   c_p - 1/2 z^2 (df = +inf) or c_p - (df + 1) / 2 log(1 + z^2 / df);  c_p is the host's (api_gp_hyp.hip).
+//   c_p - 1/2 z^2 (df = +inf) or c_p - (df + 1) / 2 log(1 + z^2 / df);  c_p is the host's (gp_cand_host.h).
 // dt (optional): its derivative, -z / sigma or -(df + 1) z / (sigma (df + z^2)).
 __device__ __forceinline__ double gp_prior_term(const double* pmu, const double* psig, const double* pdf, const double* pconst,
                                                 int p, double h, double* dt = nullptr) {

@@ -14,7 +14,7 @@
 // of acq_is_mcmc.hip's chain_advance.
 //
 // The prior: log p(h) = sum_p t_p, p ascending; t_p = 0 without a prior (sigma NaN), else with z = (h_p - mu_p) / sigma_p
-//   t_p = c_p - 1/2 z^2 (df = +inf) or c_p - (df + 1) / 2 log(1 + z^2 / df);  c_p is the host's (api_gp_hyp.hip).
+//   t_p = c_p - 1/2 z^2 (df = +inf) or c_p - (df + 1) / 2 log(1 + z^2 / df);  c_p is the host's (gp_cand_host.h).
 //
 // A finished (or invalid) chain's workgroup still writes its last candidate, so every slot of a chunk stays a valid
 // input of the factorisation; its state and outputs no longer change.  No atomics on global memory, no waiting on other
@@ -216,31 +216,14 @@ __global__ __launch_bounds__(256) void gp_hyp_advance_kernel(GpHypArgs a, int b0
   gp_cand_noise<256>(tid, slot, N, D, xp, a.lb, a.s2, a.s2_min, a.g_sn2, a.g_sl, a.g_smeta);
 }
 
-__global__ __launch_bounds__(256) void gp_hyp_count_kernel(const double* __restrict__ state, int C, int state_elems,
-                                                           int* __restrict__ count) {
-  __shared__ int s_n;
-  if (threadIdx.x == 0) s_n = 0;
-  __syncthreads();
-  int n = 0;
-  for (int c = threadIdx.x; c < C; c += 256) n += ((const HypChain*)(state + (size_t)c * state_elems))->done ? 0 : 1;
-  if (n) atomicAdd(&s_n, n);  // (LDS, integers: the order does not matter)
-  __syncthreads();
-  if (threadIdx.x == 0) *count = s_n;
-}
-
 }  // namespace
 
 size_t gp_hyp_state_elems() { return sizeof(HypChain) / sizeof(double); }
+LockstepWord gp_hyp_done_word() { return {gp_hyp_state_elems(), offsetof(HypChain, done), 1}; }  // (done: 0 or 1)
 
 int launch_gp_hyp_advance(vbmc_ctx* ctx, const GpHypArgs& a, int b0, int S) {
   if (a.P > HY_PMAX) return vbmc_fail(ctx, VBMC_E_ARG, "gp_hyp: P=%d > %d", a.P, HY_PMAX);
   hipLaunchKernelGGL(gp_hyp_advance_kernel, dim3(S), dim3(256), 0, ctx->stream, a, b0, S, (int)gp_hyp_state_elems());
-  HIP_TRY(ctx, hipGetLastError());
-  return 0;
-}
-
-int launch_gp_hyp_count(vbmc_ctx* ctx, const double* d_state, int C, int* d_count) {
-  hipLaunchKernelGGL(gp_hyp_count_kernel, dim3(1), dim3(256), 0, ctx->stream, d_state, C, (int)gp_hyp_state_elems(), d_count);
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }

@@ -320,34 +320,16 @@ __global__ __launch_bounds__(64) void gp_opt_advance_kernel(GpOptArgs a, int b0,
   if (lane == 0) a.dsn2[slot] = 2.0 * e;
 }
 
-__global__ __launch_bounds__(256) void gp_opt_count_kernel(const double* __restrict__ state, int R, int state_elems,
-                                                           int* __restrict__ count) {
-  __shared__ int s_n;
-  if (threadIdx.x == 0) s_n = 0;
-  __syncthreads();
-  int n = 0;
-  for (int r = threadIdx.x; r < R; r += 256) n += ((const OptRun*)(state + (size_t)r * state_elems))->done ? 0 : 1;
-  if (n) atomicAdd(&s_n, n);  // (LDS, integers: the order does not matter)
-  __syncthreads();
-  if (threadIdx.x == 0) *count = s_n;
-}
-
 }  // namespace
 
 size_t gp_opt_state_elems(int P, int m) { return sizeof(OptRun) / sizeof(double) + (4 + 2 * (size_t)m) * P + m; }
+LockstepWord gp_opt_done_word(int P, int m) { return {gp_opt_state_elems(P, m), offsetof(OptRun, done), 1}; }  // (done: 0 or 1)
 
 int launch_gp_opt_advance(vbmc_ctx* ctx, const GpOptArgs& a, int b0, int S) {
   if (a.P > OP_PMAX || a.m < 1 || a.m > OP_MMAX)
     return vbmc_fail(ctx, VBMC_E_ARG, "gp_opt: P=%d > %d or m=%d outside [1, %d]", a.P, OP_PMAX, a.m, OP_MMAX);
   hipLaunchKernelGGL(gp_opt_advance_kernel, dim3(S), dim3(64), 0, ctx->stream, a, b0, S,
                      (int)gp_opt_state_elems(a.P, a.m));
-  HIP_TRY(ctx, hipGetLastError());
-  return 0;
-}
-
-int launch_gp_opt_count(vbmc_ctx* ctx, const GpOptArgs& a, int* d_count) {
-  hipLaunchKernelGGL(gp_opt_count_kernel, dim3(1), dim3(256), 0, ctx->stream, (const double*)a.state, a.R,
-                     (int)gp_opt_state_elems(a.P, a.m), d_count);
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }

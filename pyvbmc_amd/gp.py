@@ -596,9 +596,7 @@ def log_marginal_likelihood(gp, hyp, *, grad=False, device=True, ctx=None):
     with np.errstate(all="ignore"):
         sn2 = _lib.f64(np.stack([_noise_var(gp, h[D + 1 : D + 2]) for h in hyp]))
         sn2_div = _lib.f64(np.min(sn2, axis=1))
-        noise = getattr(gp, "noise", None)
-        const_add = True if noise is None or not hasattr(noise, "compute") else bool(getattr(noise, "constant_add", False))
-        dsn2 = _lib.f64(2.0 * np.exp(2 * hyp[:, D + 1]) if const_add else np.zeros(B))
+        dsn2 = _lib.f64(2.0 * np.exp(2 * hyp[:, D + 1]) if _const_noise_form(gp)[0] else np.zeros(B))
     lml = np.empty(B)
     dlml = np.empty((B, P)) if grad else None
     host_rows = np.ones(B, dtype=bool)
@@ -771,6 +769,28 @@ def _const_noise_form(gp):
     return True, s2 if getattr(noise, "user_provided_add", False) else None
 
 
+def _hyper_problem(who, runs, gp, x0, lb, ub, priors, ctx, device):
+    """The prologue ``sample_hyperparameters`` and ``optimize_hyperparameters`` share (``who``, ``runs``: the caller's name and its letter
+    for the number of starts, for its error texts): the GP's data, the starts and the box as float64 arrays of the right shapes, the prior arrays, the noise
+    form and the context of the device route (None: the host route runs)."""
+    X = _lib.f64(np.atleast_2d(gp.X))
+    y = _lib.f64(np.ravel(gp.y))
+    D = X.shape[1]
+    kind = mean_kind_of(gp)
+    P = D + 2 + (0, 1, 1 + 2 * D)[kind]
+    x0 = _lib.f64(np.atleast_2d(x0))
+    if x0.ndim != 2 or x0.shape[1] != P or x0.shape[0] < 1:
+        raise ValueError(f"{who}: x0 must be ({runs}, {P})")
+    lb, ub = (_lib.f64(np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), (P,)))) for a in (lb, ub))
+    if not (np.all(np.isfinite(lb)) and np.all(np.isfinite(ub)) and np.all(lb <= ub)):
+        raise ValueError(f"{who}: finite bounds with lb <= ub are required")
+    mu, sigma, df = (_lib.f64(a) for a in _prior_arrays(priors, P))
+    const_add, s2 = _const_noise_form(gp)
+    ctx = None if not (device and const_add) else (getattr(gp, "ctx", None) or _lib.default_context()) if ctx is None else ctx
+    return SimpleNamespace(X=X, y=y, N=X.shape[0], D=D, kind=kind, P=P, x0=x0, lb=lb, ub=ub, mu=mu, sigma=sigma, df=df,
+                           pri={"mu": mu, "sigma": sigma, "df": df}, const_add=const_add, s2=s2, ctx=ctx)
+
+
 def sample_hyperparameters(gp, x0, *, lb, ub, widths, priors=None, n=1, thin=1, burn_in=0, seed=None, device=True, ctx=None):
     """Slice-sample the hyper-parameters of ``gp`` from ``lml + log prior``: C chains, one per row of ``x0`` (C, P).
 
@@ -784,39 +804,27 @@ def sample_hyperparameters(gp, x0, *, lb, ub, widths, priors=None, n=1, thin=1, 
     run the same chains in NumPy over the host lml, with the same draws.
     Returns ``dict(samples (C, n, P), log_post (C, n), log_priors (C, n), stats (C, 4))``, stats = [evaluations, draws,
     step-out caps hit, shrink caps hit].  ``ValueError("Invalid value.")`` when a chain's start has no finite density."""
-    X = _lib.f64(np.atleast_2d(gp.X))
-    y = _lib.f64(np.ravel(gp.y))
-    N, D = X.shape
-    kind = mean_kind_of(gp)
-    P = D + 2 + (0, 1, 1 + 2 * D)[kind]
-    x0 = _lib.f64(np.atleast_2d(x0))
-    if x0.ndim != 2 or x0.shape[1] != P or x0.shape[0] < 1:
-        raise ValueError(f"sample_hyperparameters: x0 must be (C, {P})")
+    q = _hyper_problem("sample_hyperparameters", "C", gp, x0, lb, ub, priors, ctx, device)
+    X, y, N, D, kind, P, x0, lb, ub, pri = q.X, q.y, q.N, q.D, q.kind, q.P, q.x0, q.lb, q.ub, q.pri
     Cn = x0.shape[0]
-    lb, ub, widths = (_lib.f64(np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), (P,)))) for a in (lb, ub, widths))
-    if not (np.all(np.isfinite(lb)) and np.all(np.isfinite(ub)) and np.all(lb <= ub)):
-        raise ValueError("sample_hyperparameters: finite bounds with lb <= ub are required")
+    widths = _lib.f64(np.array(np.broadcast_to(np.asarray(widths, dtype=np.float64), (P,))))
     if not (np.all(widths > 0) and np.all(np.isfinite(widths))):
         raise ValueError("sample_hyperparameters: widths must be positive")
     n, thin, burn_in = int(n), int(thin), int(burn_in)
     if n < 1 or thin < 1 or burn_in < 0:
         raise ValueError("sample_hyperparameters: n >= 1, thin >= 1, burn_in >= 0")
-    mu, sigma, df = (_lib.f64(a) for a in _prior_arrays(priors, P))
-    pri = {"mu": mu, "sigma": sigma, "df": df}
     seed = int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0]) if seed is None else int(seed)
     seed &= 0xFFFFFFFFFFFFFFFF
-    const_form, s2 = _const_noise_form(gp)
-    if device and const_form:
-        ctx = (getattr(gp, "ctx", None) or _lib.default_context()) if ctx is None else ctx
+    if q.ctx is not None:
         samples, lpost, lprior = np.zeros((Cn, n, P)), np.zeros((Cn, n)), np.zeros((Cn, n))
         stats, invalid = np.zeros((Cn, 4), dtype=np.int64), np.zeros(Cn, dtype=np.int32)
-        rc = ctx._lib.vbmc_gp_hyp_sample(
-            ctx._h, N, D, P, kind, _lib.ptr(X), _lib.ptr(y), _lib.ptr(s2), Cn, _lib.ptr(x0), _lib.ptr(widths), _lib.ptr(lb),
-            _lib.ptr(ub), _lib.ptr(mu), _lib.ptr(sigma), _lib.ptr(df), n, thin, burn_in, C.c_uint64(seed), _lib.ptr(samples),
-            _lib.ptr(lpost), _lib.ptr(lprior), stats.ctypes.data_as(C.POINTER(C.c_int64)),
+        rc = q.ctx._lib.vbmc_gp_hyp_sample(
+            q.ctx._h, N, D, P, kind, _lib.ptr(X), _lib.ptr(y), _lib.ptr(q.s2), Cn, _lib.ptr(x0), _lib.ptr(widths),
+            _lib.ptr(lb), _lib.ptr(ub), _lib.ptr(q.mu), _lib.ptr(q.sigma), _lib.ptr(q.df), n, thin, burn_in, C.c_uint64(seed),
+            _lib.ptr(samples), _lib.ptr(lpost), _lib.ptr(lprior), stats.ctypes.data_as(C.POINTER(C.c_int64)),
             invalid.ctypes.data_as(C.POINTER(C.c_int32)))
         if rc != _lib.E_UNSUP:
-            ctx.check(rc)
+            q.ctx.check(rc)
             if np.any(invalid):
                 raise ValueError("Invalid value.")
             return dict(samples=samples, log_post=lpost, log_priors=lprior, stats=stats)
@@ -940,39 +948,26 @@ def optimize_hyperparameters(gp, x0, *, lb, ub, priors=None, max_iter=200, histo
     ``iters`` (R, max_iter + 1, 3 P + 3), rows [x, phi, g, d, pairs held, reset flag], and ``evals`` (R, 1 + 31 (max_iter
     + 1), 4), rows [iteration, t, phi_trial, accepted]; rows not reached are zeros.  ``ValueError("Invalid value.")`` when
     a start has no finite value."""
-    X = _lib.f64(np.atleast_2d(gp.X))
-    y = _lib.f64(np.ravel(gp.y))
-    N, D = X.shape
-    kind = mean_kind_of(gp)
-    P = D + 2 + (0, 1, 1 + 2 * D)[kind]
-    x0 = _lib.f64(np.atleast_2d(x0))
-    if x0.ndim != 2 or x0.shape[1] != P or x0.shape[0] < 1:
-        raise ValueError(f"optimize_hyperparameters: x0 must be (R, {P})")
+    q = _hyper_problem("optimize_hyperparameters", "R", gp, x0, lb, ub, priors, ctx, device)
+    X, y, N, D, kind, P, x0, lb, ub, pri = q.X, q.y, q.N, q.D, q.kind, q.P, q.x0, q.lb, q.ub, q.pri
     R = x0.shape[0]
-    lb, ub = (_lib.f64(np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), (P,)))) for a in (lb, ub))
-    if not (np.all(np.isfinite(lb)) and np.all(np.isfinite(ub)) and np.all(lb <= ub)):
-        raise ValueError("optimize_hyperparameters: finite bounds with lb <= ub are required")
     max_iter, m, tol_g, tol_f = int(max_iter), int(history), float(tol_g), float(tol_f)
     if max_iter < 0 or not 1 <= m <= 16 or not tol_g >= 0 or not tol_f >= 0:
         raise ValueError("optimize_hyperparameters: max_iter >= 0, 1 <= history <= 16, tol_g >= 0, tol_f >= 0")
-    mu, sigma, df = (_lib.f64(a) for a in _prior_arrays(priors, P))
-    pri = {"mu": mu, "sigma": sigma, "df": df}
     cap = max_iter + 1
     n_evr = 1 + 31 * cap
-    const_form, s2 = _const_noise_form(gp)
-    if device and const_form:
-        ctx = (getattr(gp, "ctx", None) or _lib.default_context()) if ctx is None else ctx
+    if q.ctx is not None:
         hyp, lpost, grad = np.zeros((R, P)), np.zeros(R), np.zeros((R, P))
         stats, invalid = np.zeros((R, 4), dtype=np.int64), np.zeros(R, dtype=np.int32)
         t_it = np.zeros((R, cap, 3 * P + 3)) if trace else None
         t_ev = np.zeros((R, n_evr, 4)) if trace else None
-        rc = ctx._lib.vbmc_gp_hyp_optimize(
-            ctx._h, N, D, P, kind, _lib.ptr(X), _lib.ptr(y), _lib.ptr(s2), R, _lib.ptr(x0), _lib.ptr(lb), _lib.ptr(ub),
-            _lib.ptr(mu), _lib.ptr(sigma), _lib.ptr(df), max_iter, m, tol_g, tol_f, cap if trace else 0, _lib.ptr(hyp),
+        rc = q.ctx._lib.vbmc_gp_hyp_optimize(
+            q.ctx._h, N, D, P, kind, _lib.ptr(X), _lib.ptr(y), _lib.ptr(q.s2), R, _lib.ptr(x0), _lib.ptr(lb), _lib.ptr(ub),
+            _lib.ptr(q.mu), _lib.ptr(q.sigma), _lib.ptr(q.df), max_iter, m, tol_g, tol_f, cap if trace else 0, _lib.ptr(hyp),
             _lib.ptr(lpost), _lib.ptr(grad), stats.ctypes.data_as(C.POINTER(C.c_int64)),
             invalid.ctypes.data_as(C.POINTER(C.c_int32)), _lib.ptr(t_it), _lib.ptr(t_ev))
         if rc != _lib.E_UNSUP:
-            ctx.check(rc)
+            q.ctx.check(rc)
             if np.any(invalid):
                 raise ValueError("Invalid value.")
             out = dict(hyp=hyp, log_post=lpost, grad=grad, stats=stats)
@@ -980,13 +975,10 @@ def optimize_hyperparameters(gp, x0, *, lb, ub, priors=None, max_iter=200, histo
                 out["trace"] = dict(iters=t_it, evals=t_ev)
             return out
 
-    noise = getattr(gp, "noise", None)
-    const_add = True if noise is None or not hasattr(noise, "compute") else bool(getattr(noise, "constant_add", False))
-
     def fun(h):
         with np.errstate(all="ignore"):
             sn2 = _noise_var(gp, h[D + 1 : D + 2])
-            dsn2 = 2.0 * np.exp(2 * h[D + 1]) if const_add else 0.0
+            dsn2 = 2.0 * np.exp(2 * h[D + 1]) if q.const_add else 0.0
             lml, dl = _host_lml(X, y, kind, h, sn2, np.min(sn2), dsn2, True)
             lp, dp = hyper_log_prior(h, pri, grad=True)
             phi, g = -(lml + lp), -(dl + dp)

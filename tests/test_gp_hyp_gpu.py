@@ -112,6 +112,25 @@ def test_independent_of_batch_chunks_and_rounds(ctx):
     assert one[0] == 0 and seven[0] == 0 and same(base, one) and same(base, seven)
 
 
+def test_more_chains_than_the_count_kernel_has_threads(ctx):
+    """C = 257: the count of unfinished chains (one workgroup of 256 threads, csrc/lockstep.hip) takes a second trip of
+    its strided loop.  A count that saw the first 256 chains alone would let the host stop while chain 256 still runs,
+    and its outputs would be the zeros they start as."""
+    cs = hs.case(65)
+    kw = dict(n=1, thin=1, burn_in=0)
+    rng = np.random.default_rng(257)
+    jit = cs.x0[np.arange(254) % 3] + 0.05 * rng.standard_normal((254, cs.P))
+    x0 = np.vstack([cs.x0, np.minimum(np.maximum(jit, cs.lb), cs.ub)])
+    assert x0.shape == (257, cs.P)
+    three = raw(ctx, cs, cs.x0, **kw)
+    rc, smp, lpost, lpri, stats, inv = out = raw(ctx, cs, x0, **kw)
+    assert three[0] == 0 and rc == 0 and not np.any(inv)
+    assert np.all(stats[:, 0] > 0)
+    assert same(three, tuple(a[:3] if i else a for i, a in enumerate(out)))
+    assert np.all(smp[256, 0] >= cs.lb) and np.all(smp[256, 0] <= cs.ub)
+    within_host_bound(cs, smp[256, 0], lpost[256, 0], "chain 256 of 257")
+
+
 # ------------------------------------------------------------------------------------------- 3. the installed GP
 def test_installed_gp_untouched(ctx):
     import gp_post_host as gph

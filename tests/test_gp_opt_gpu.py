@@ -234,6 +234,22 @@ def test_independent_of_batch_chunks_rounds_and_trace(ctx):
     assert plain[0] == 0 and same(base, plain)
 
 
+def test_more_runs_than_the_count_kernel_has_threads(ctx):
+    """R = 257: the count of unfinished runs (one workgroup of 256 threads, csrc/lockstep.hip) takes a second trip of its
+    strided loop.  Run 256 starts where run 0 does and the runs draw nothing, so it ends where run 0 does; a count that
+    saw the first 256 runs alone could let the host stop before it has, with the zeros its outputs start as."""
+    cs = goh.case(63)
+    rng = np.random.default_rng(257)
+    jit = cs.x0[np.arange(253) % 3] + 0.05 * rng.standard_normal((253, cs.P))
+    x0 = np.vstack([cs.x0, np.minimum(np.maximum(jit, cs.lb), cs.ub), cs.x0[:1]])
+    assert x0.shape == (257, cs.P)
+    rc, hyp, lpost, grad, stats, inv, _, _ = raw(ctx, cs, x0, trace=False, max_iter=3)
+    assert rc == 0
+    assert np.array_equal(hyp[256], hyp[0]) and lpost[256] == lpost[0] and np.array_equal(grad[256], grad[0])
+    assert np.array_equal(stats[256], stats[0])
+    assert np.all(stats[:, 3] != 0), np.flatnonzero(stats[:, 3] == 0)
+
+
 # ------------------------------------------------------------------------------------------- 4. the installed GP
 def test_installed_gp_untouched(ctx):
     import gp_post_host as gph

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Outputs of the entry points that list their device scratch through csrc/scratch.h and are not in tools/gp_dense_dump.py
 -- the sampler and its consumers (kl_div, moments, mtv, mode), the transformer, pdf_orig, kde_1d, the importance-sampling
-preparation and its MCMC step, neg_elcbo_batch, the device-built GP posterior and its append, GP hyper-parameter sampling,
-the acquisition search's evaluation of a resident set and its CMA-ES refinement -- for a fixed list of small
+preparation and its MCMC step, neg_elcbo_batch, the device-built GP posterior and its append, GP hyper-parameter sampling and
+optimisation, the batched log marginal likelihood, the acquisition search's evaluation of a resident set and its CMA-ES refinement -- for a fixed list of small
 cases, written to an .npz: run once per library (VBMC_HIP_LIB names the one to load, as in tools/ab_libs.sh) and compare.
     VBMC_HIP_LIB=$PWD/variants/libvbmc_parent.so python tools/entry_dump.py parent.npz
     python tools/entry_dump.py new.npz
@@ -217,6 +217,35 @@ def main(out):
                                    st.ctypes.data_as(C.POINTER(C.c_int64)), inv.ctypes.data_as(C.POINTER(C.c_int32))))
     for k, v in zip(("samples", "log_post", "log_priors", "stats", "invalid"), (smp, lpo, lpr, st, inv)):
         res[f"gp_hyp_sample/{k}"] = v
+    # ---- vbmc_gp_hyp_optimize on the same data: 3 starts, 6 iterations of 3 pairs, traced; once more in chunks of 2
+    i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+    mi, mh, cap = 6, 3, 7
+    for chunk in (0, 2):
+        ctx.set_option("gp_lml_chunk", chunk)
+        ho, lpo, go = np.zeros((Cn, P)), np.zeros(Cn), np.zeros((Cn, P))
+        st, inv = np.zeros((Cn, 4), dtype=np.int64), np.zeros(Cn, dtype=np.int32)
+        tit, tev = np.zeros((Cn, cap, 3 * P + 3)), np.zeros((Cn, 1 + 31 * cap, 4))
+        ctx.check(L.vbmc_gp_hyp_optimize(h, N, D, P, _lib.MEAN_CONST, p(X), p(y), None, Cn, p(x0), p(lb), p(ub), p(pmu), p(psg),
+                                         p(pdf), mi, mh, 1e-5, 1e-9, cap, p(ho), p(lpo), p(go), st.ctypes.data_as(i64p),
+                                         inv.ctypes.data_as(i32p), p(tit), p(tev)))
+        for k, v in zip(("hyp", "log_post", "grad", "stats", "invalid", "trace_iter", "trace_eval"),
+                        (ho, lpo, go, st, inv, tit, tev)):
+            res[f"gp_hyp_optimize/c{chunk}/{k}"] = v
+    # ---- vbmc_gp_lml on the same data: B = 3 (the starts; the third row's sf^2 overflows, a candidate that does not
+    # factorise), value alone and with the gradient, then in chunks of 2
+    hb = f64(x0)
+    hb[2, D] = 400.0
+    e = np.exp(2.0 * hb[:, D + 1])
+    sn2b, divb, dsb = f64(np.repeat(e[:, None], N, axis=1)), f64(e), f64(2.0 * e)
+    for tag, chunk, gr in (("v", 0, 0), ("g", 0, 1), ("g_c2", 2, 1)):
+        ctx.set_option("gp_lml_chunk", chunk)
+        lm, dl, stt = np.empty(Cn), np.zeros((Cn, P)), np.zeros(Cn, dtype=np.int32)
+        ctx.check(L.vbmc_gp_lml(h, N, D, Cn, P, _lib.MEAN_CONST, p(X), p(y), p(sn2b), p(divb), p(dsb), p(hb), gr, p(lm),
+                                p(dl) if gr else None, stt.ctypes.data_as(i32p)))
+        lm[np.isneginf(lm)] = -12345.0  # (a fixed stand-in, as for the search's NaN: np.array_equal could not compare NaN)
+        dl[np.isnan(dl)] = -12345.0
+        res[f"gp_lml/{tag}/lml"], res[f"gp_lml/{tag}/dlml"], res[f"gp_lml/{tag}/status"] = lm, dl, stt
+    ctx.set_option("gp_lml_chunk", 0)
     # ---- vbmc_search_put / vbmc_search_eval on 300 resident points, every kind; then vbmc_search_cmaes, whose scoring
     # is the same code (a library from before that entry point: the search arrays alone)
     r3 = np.random.default_rng(2025)
