@@ -133,7 +133,8 @@ int vbmc_set_timing(vbmc_ctx* ctx, int on);
  *        11 = its sort and gather,
  *        12 = vbmc_gp_hyp_sample: all the rounds of the last call (a call that launched nothing leaves no record),
  *        13 = vbmc_search_cmaes: all the rounds of the last call, likewise,
- *        14 = vbmc_gp_hyp_optimize: all the rounds of the last call, likewise. */
+ *        14 = vbmc_gp_hyp_optimize: all the rounds of the last call, likewise,
+ *        15 = vbmc_sieve_fill's launch, 16 = vbmc_sieve_eval's scoring launches, 17 = its rank and gather. */
 int vbmc_last_kernel_ms(vbmc_ctx* ctx, int which, double* ms_out);
 
 /* Host-side wall-clock breakdown (microseconds) of the most recent vbmc_neg_elcbo:
@@ -836,6 +837,57 @@ int vbmc_search_cmaes(vbmc_ctx* ctx, int kind, double y_max, double tol_gp_var, 
                       const double* sigma0_R, const double* lb_D, const double* ub_D, uint32_t integer_bits,
                       const vbmc_cmaes_opts* opts, double* x_best_RxD, double* f_best_R, double* f0_R, double* mean_RxD,
                       double* sigma_R, double* C_RxDxD, int64_t* stats_Rx4);
+
+/* ---- the sieve of optimize_vp: candidates drawn, scored, ranked ----------- *
+ *
+ * vbmc/variational_optimization.py:660-810 (_sieve) builds init_N candidate posteriors with _vb_init (:813-988), scores
+ * each with a value-only, lower-bound-entropy _neg_elcbo (:775-787) and sorts them (:789-792).  The context keeps one
+ * resident set of candidate thetas (B x n_theta: the raw parameters get_parameters returns for a candidate,
+ * variational_posterior.py:642-676, the eta tail max-shifted as _neg_elcbo leaves it, :1082-1085); between the calls
+ * below the candidates exist only in device memory.
+ *
+ * vbmc_sieve_fill replaces _vb_init's loop (:882-986) and the get_parameters of :776.  The set is n1 candidates of type
+ * 1 (the old parameters mu0 / sigma0 / lambd0 / w0 of K components; K_new - K components spawned next to old ones,
+ * :898-914), n2 of type 2 (start mu2 / sigma2, :862-875: the caller orders y_star and makes the single sigma0 draw) and
+ * n3 of type 3 (means gathered from X_star, sigma from their variance, :926-943; v3 = mean_d var(X_star[:, d], ddof=1) is
+ * used instead when K == 1), in this order; lambd_s_D is the normalised std(X_star) form of lambd (:920-921, :946-947)
+ * that types 2 and 3 take with optimize_lambd.  Candidate 0 of types 1 and 2 is left without jitter (:895-896, :917-918).
+ * The draws: Z_BxS / I_BxKn are the host's (NumPy's stream; slot layout and index columns: csrc/sieve.hip), or, with
+ * Z_BxS NULL, every draw is made on the device from Philox under `seed`, counter (candidate, slot) (streams 10-12 of
+ * csrc/sample.hip's list).  thetas_out_BxN (nullable) receives the set.
+ * Covered, VBMC_E_UNSUP otherwise, before anything is queued: D <= 32, K_new <= 128, optimize_sigma on, K_new >= K,
+ * K_new > K only with optimize_mu, B <= 2^20, N_star within the generator's LDS (Philox type 3: about 3 700 points at
+ * K_new D = 4 096).
+ *
+ * vbmc_sieve_put makes the rows of a host matrix the resident set (a caller's own candidates).
+ *
+ * vbmc_sieve_eval replaces the loop :775-787 and the sort :789-792: the scoring launches of vbmc_neg_elcbo_batch on the
+ * resident set (the ctx mixture supplies D, K = K_new and the blocks that are not optimised; opts as there), then the
+ * stable ascending order of F, NaN last (np.argsort(kind="stable")).  A candidate with a value that is not finite
+ * scores NaN -- it is dropped by the order, not an error.  Outputs, each nullable: F, G, H in set order, the order, and
+ * the thetas in rank order; one download. */
+typedef struct vbmc_sieve_fill_args {
+  int D, K, K_new, optimize_mask;
+  int64_t n1, n2, n3;
+  const double* mu0_KxD;
+  const double* sigma0_K;
+  const double* lambd0_D;
+  const double* w0_K;
+  const double* mu2_KnxD;  /* n2 > 0 */
+  const double* sigma2_Kn; /* n2 > 0 */
+  const double* lambd_s_D; /* n2 + n3 > 0 and optimize_lambd */
+  int64_t N_star;
+  const double* X_star_NxD; /* n3 > 0 and optimize_mu */
+  double v3;
+  const double* Z_BxS; /* host draws, or NULL: Philox under seed */
+  int n_slot;          /* S = (K_new - K)(D + 2) + 3 K_new + D K_new + D */
+  const int32_t* I_BxKn;
+  uint64_t seed;
+} vbmc_sieve_fill_args;
+int vbmc_sieve_fill(vbmc_ctx* ctx, const vbmc_sieve_fill_args* args, double* thetas_out_BxN);
+int vbmc_sieve_put(vbmc_ctx* ctx, int64_t B, int n_theta, const double* thetas_BxN);
+int vbmc_sieve_eval(vbmc_ctx* ctx, const vbmc_elbo_opts* opts, double* F_B, double* G_B, double* H_B, int64_t* order_B,
+                    double* thetas_sorted_BxN);
 
 /* ---- sampling and its Monte-Carlo consumers -------------- */
 

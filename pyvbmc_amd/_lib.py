@@ -27,6 +27,7 @@ T_SEARCH_FILL, T_SEARCH_EVAL, T_SEARCH_SORT = 9, 10, 11
 T_GP_HYP = 12
 T_SEARCH_CMAES = 13
 T_GP_OPT = 14
+T_SIEVE_FILL, T_SIEVE_SCORE, T_SIEVE_RANK = 15, 16, 17
 
 
 class VbmcHipError(RuntimeError):
@@ -115,6 +116,34 @@ class SearchSource(C.Structure):
         ("rows", C.c_int64),
         ("data", _dp),
         ("df", C.c_double),
+        ("seed", C.c_uint64),
+    ]
+
+
+class SieveFillArgs(C.Structure):
+    """vbmc_sieve_fill_args: the base mixture, the per-type constants and the draws of one sieve (vbmc_sieve_fill)."""
+
+    _fields_ = [
+        ("D", C.c_int),
+        ("K", C.c_int),
+        ("K_new", C.c_int),
+        ("optimize_mask", C.c_int),
+        ("n1", C.c_int64),
+        ("n2", C.c_int64),
+        ("n3", C.c_int64),
+        ("mu0_KxD", _dp),
+        ("sigma0_K", _dp),
+        ("lambd0_D", _dp),
+        ("w0_K", _dp),
+        ("mu2_KnxD", _dp),
+        ("sigma2_Kn", _dp),
+        ("lambd_s_D", _dp),
+        ("N_star", C.c_int64),
+        ("X_star_NxD", _dp),
+        ("v3", C.c_double),
+        ("Z_BxS", _dp),
+        ("n_slot", C.c_int),
+        ("I_BxKn", C.POINTER(C.c_int32)),
         ("seed", C.c_uint64),
     ]
 
@@ -253,6 +282,9 @@ SIGNATURES = {
     "vbmc_search_cmaes": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, _dp, _dp, _dp, C.c_int, _dp,
                                     _dp, C.c_int, _dp, _dp, _dp, _dp, C.c_uint32, C.POINTER(CmaesOpts), _dp, _dp, _dp, _dp,
                                     _dp, _dp, C.POINTER(C.c_int64)]),
+    "vbmc_sieve_fill": (C.c_int, [_vp, C.POINTER(SieveFillArgs), _dp]),
+    "vbmc_sieve_put": (C.c_int, [_vp, C.c_int64, C.c_int, _dp]),
+    "vbmc_sieve_eval": (C.c_int, [_vp, C.POINTER(ElboOpts), _dp, _dp, _dp, C.POINTER(C.c_int64), _dp]),
     "vbmc_mixture_sample": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, C.POINTER(C.c_int32)]),
     "vbmc_mixture_sample_t": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, C.c_double, _dp, C.POINTER(C.c_int32)]),
     "vbmc_kl_div_mc": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, _dp, _dp, _dp, _dp]),

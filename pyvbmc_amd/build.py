@@ -42,6 +42,8 @@ SOURCES = [
     "acq_is_mcmc.hip",
     "search.hip",
     "api_search.hip",
+    "sieve.hip",
+    "api_sieve.hip",
     "cmaes.hip",
     "api_cmaes.hip",
     "sample.hip",

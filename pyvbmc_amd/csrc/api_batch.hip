@@ -245,58 +245,70 @@ __global__ __launch_bounds__(256) void batch_finalize_kernel(BatchFin f) {
 
 }  // namespace
 
-extern "C" int vbmc_neg_elcbo_batch(vbmc_ctx* ctx, const double* thetas_BxN, int B, int n_theta,
-                                    const vbmc_elbo_opts* opts, double* F_B, double* G_B,
-                                    double* H_B) {
-  if (!ctx || !thetas_BxN || !opts || !F_B || B < 0) return VBMC_E_ARG;
-  NEED_DEVICE(ctx);
-  if (!ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo_batch: mixture (D,K) not set");
-  if (!ctx->gp.set) return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo_batch: GP not set");
-  if (ctx->gp.D != ctx->D) return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo_batch: GP/mixture D mismatch");
+// ---- the scoring part, on thetas that are already in device memory: what vbmc_neg_elcbo_batch runs on its uploaded rows
+// and vbmc_sieve_eval (api_sieve.hip) on the resident candidate set.  A call's order: check (the arguments, before anything
+// is queued), list (the pieces behind the caller's own), reserve + ensure_pinned(batch_score_pinned) by the caller, queue
+// (the base attributes, the bounds and the flags go up, the four launches; F | G | H are then s.p_out, the flags s.p_flags).
+
+int batch_score_check(vbmc_ctx* ctx, const char* who, int B, int n_theta, const vbmc_elbo_opts* opts) {
+  if (!ctx->mix_set) return vbmc_fail(ctx, VBMC_E_ARG, "%s: mixture (D,K) not set", who);
+  if (!ctx->gp.set) return vbmc_fail(ctx, VBMC_E_ARG, "%s: GP not set", who);
+  if (ctx->gp.D != ctx->D) return vbmc_fail(ctx, VBMC_E_ARG, "%s: GP/mixture D mismatch", who);
   if (opts->ns_per_comp != 0 || opts->compute_grad)
-    return vbmc_fail(ctx, VBMC_E_UNSUP,
-                     "neg_elcbo_batch covers the sieve call only: Ns = 0 (entlb), no gradient");
-  if (B == 0) return VBMC_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int D = ctx->D, K = ctx->K, S = ctx->gp.S;
-  const int mask = opts->optimize_mask;
-  const ThetaMap tm(D, K, mask);
-  if (n_theta != tm.n_theta()) return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo_batch: theta length %d does not match", n_theta);
+    return vbmc_fail(ctx, VBMC_E_UNSUP, "%s covers the sieve call only: Ns = 0 (entlb), no gradient", who);
+  const ThetaMap tm(ctx->D, ctx->K, opts->optimize_mask);
+  if (n_theta != tm.n_theta()) return vbmc_fail(ctx, VBMC_E_ARG, "%s: theta length %d does not match", who, n_theta);
   const bool has_bnd = opts->bnd_lb && opts->bnd_ub;
   if (has_bnd && tm.n_bnd() != opts->n_bnd)
-    return vbmc_fail(ctx, VBMC_E_ARG, "neg_elcbo_batch: bounds length %d != %d", opts->n_bnd, tm.n_bnd());
-  const int n_bnd = has_bnd ? opts->n_bnd : 0;
-  MixLayout ml;
-  ml.plan(D, K);
-  const size_t stride = (size_t)ml.total;
-  const int n_aux = (int)adam_dev::aux_len(D, K);
+    return vbmc_fail(ctx, VBMC_E_ARG, "%s: bounds length %d != %d", who, opts->n_bnd, tm.n_bnd());
+  if (ctx->K > 1 && sizeof(double) * ((size_t)ctx->K * ctx->D + 2 * (size_t)ctx->K) > 150 * 1024)
+    return vbmc_fail(ctx, VBMC_E_UNSUP, "%s: K=%d D=%d too large", who, ctx->K, ctx->D);
+  return 0;
+}
 
-  // ---- device memory: thetas | attributes | packs | sums | H | F G H | base attributes | bounds | flags ----
-  const size_t n_res = (size_t)B * S * K * (1 + 2 * D);
-  Scratch sc;
-  const auto p_th = sc.add((size_t)B * n_theta), p_aux = sc.add((size_t)B * n_aux), p_packs = sc.add(stride * B);
-  const auto p_res = sc.add(n_res), p_H = sc.add((size_t)B), p_out = sc.add(3 * (size_t)B);  // (out: F | G | H)
-  const auto p_base = sc.add((size_t)n_aux), p_bnd = sc.add(2 * (size_t)n_bnd);
-  const auto p_flags = sc.add<int>(8);  // [0] non-finite status of the pack, [1] first bad candidate (room for 8)
-  int rc = reserve(ctx, sc);
-  if (rc) return rc;
-  rc = ensure_pinned(ctx, 3 * (size_t)B + n_aux + 2 * (size_t)n_bnd + 2);
-  if (rc) return rc;
-  double *d_th = sc.ptr(p_th), *d_aux = sc.ptr(p_aux), *d_packs = sc.ptr(p_packs), *d_res = sc.ptr(p_res), *d_H = sc.ptr(p_H);
-  double *d_out = sc.ptr(p_out), *d_base = sc.ptr(p_base), *d_bnd = sc.ptr(p_bnd);
-  int* d_flags = sc.ptr(p_flags);
+// device memory behind the thetas: attributes | packs | sums | H | F G H | base attributes | bounds | flags
+void batch_score_list(const vbmc_ctx* ctx, int B, int n_theta, const vbmc_elbo_opts* opts, Scratch& sc, BatchScore& s) {
+  const int D = ctx->D, K = ctx->K, S = ctx->gp.S;
+  s.B = B;
+  s.n_theta = n_theta;
+  s.mask = opts->optimize_mask;
+  s.n_bnd = (opts->bnd_lb && opts->bnd_ub) ? opts->n_bnd : 0;
+  s.ml.plan(D, K);
+  s.stride = (size_t)s.ml.total;
+  s.n_aux = (int)adam_dev::aux_len(D, K);
+  s.p_aux = sc.add((size_t)B * s.n_aux);
+  s.p_packs = sc.add(s.stride * B);
+  s.p_res = sc.add((size_t)B * S * K * (1 + 2 * D));
+  s.p_H = sc.add((size_t)B);
+  s.p_out = sc.add(3 * (size_t)B);  // (out: F | G | H)
+  s.p_base = sc.add((size_t)s.n_aux);
+  s.p_bnd = sc.add(2 * (size_t)s.n_bnd);
+  s.p_flags = sc.add<int>(8);  // [0] non-finite status of the pack, [1] first bad candidate (room for 8)
+}
+
+size_t batch_score_pinned(const BatchScore& s) { return (size_t)s.n_aux + 2 * (size_t)s.n_bnd; }
+
+int batch_score_queue(vbmc_ctx* ctx, const char* who, const Scratch& sc, BatchScore& s, const vbmc_elbo_opts* opts, double* d_th,
+                      double* hp) {
+  const int D = ctx->D, K = ctx->K, S = ctx->gp.S, B = s.B, n_theta = s.n_theta, n_aux = s.n_aux, n_bnd = s.n_bnd;
+  const int mask = s.mask;
+  const MixLayout& ml = s.ml;
+  const size_t stride = s.stride;
+  double *d_aux = sc.ptr(s.p_aux), *d_packs = sc.ptr(s.p_packs), *d_res = sc.ptr(s.p_res), *d_H = sc.ptr(s.p_H);
+  double *d_out = sc.ptr(s.p_out), *d_base = sc.ptr(s.p_base), *d_bnd = sc.ptr(s.p_bnd);
+  int* d_flags = sc.ptr(s.p_flags);
   hipStream_t sm = ctx->stream;
+  int rc = 0;
   // the small host-side inputs through the pinned buffer: the ctx mixture's attributes, the bounds
-  double* hp = ctx->h_pinned + 3 * (size_t)B;
   ctx_pack_aux(ctx, hp);
-  if (has_bnd) {
+  if (n_bnd) {
     memcpy(hp + n_aux, opts->bnd_lb, sizeof(double) * n_bnd);
     memcpy(hp + n_aux + n_bnd, opts->bnd_ub, sizeof(double) * n_bnd);
   }
   HIP_TRY(ctx, hipMemcpyAsync(d_base, hp, sizeof(double) * (n_aux + 2 * (size_t)n_bnd), hipMemcpyHostToDevice, sm));
-  HIP_TRY(ctx, hipMemcpyAsync(d_th, thetas_BxN, sizeof(double) * (size_t)B * n_theta, hipMemcpyHostToDevice, sm));
-  const int flags0[2] = {0, 0x7fffffff};
-  HIP_TRY(ctx, hipMemcpyAsync(d_flags, flags0, sizeof(flags0), hipMemcpyHostToDevice, sm));
+  s.flags0[0] = 0;
+  s.flags0[1] = 0x7fffffff;
+  HIP_TRY(ctx, hipMemcpyAsync(d_flags, s.flags0, sizeof(s.flags0), hipMemcpyHostToDevice, sm));
 
   adam_dev::AdamDev a;
   memset(&a, 0, sizeof(a));
@@ -311,7 +323,6 @@ extern "C" int vbmc_neg_elcbo_batch(vbmc_ctx* ctx, const double* thetas_BxN, int
   hipLaunchKernelGGL(batch_pack_kernel, dim3(B), dim3(256), 0, sm, a, d_th, d_aux, (const double*)d_base, d_packs, stride, n_aux,
                      d_flags + 1);
   HIP_TRY(ctx, hipGetLastError());
-
   if (D <= 32 && (int64_t)B * K < ((int64_t)1 << 31)) {
     const GpState& g = ctx->gp;
     if (D <= 4) launch_glj_value_batch<4>(sm, d_packs, ml, stride, B, g, d_res);
@@ -334,7 +345,6 @@ extern "C" int vbmc_neg_elcbo_batch(vbmc_ctx* ctx, const double* thetas_BxN, int
   }
   if (K > 1) {
     const size_t lds_e = sizeof(double) * ((size_t)K * D + 2 * (size_t)K);
-    if (lds_e > 150 * 1024) return vbmc_fail(ctx, VBMC_E_UNSUP, "neg_elcbo_batch: K=%d D=%d too large", K, D);
     if (lds_e > 64 * 1024)
       HIP_TRY(ctx, hipFuncSetAttribute((const void*)entlb_value_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_e));
     hipLaunchKernelGGL(entlb_value_batch_kernel, dim3(B), dim3(256), lds_e, sm,
@@ -350,6 +360,34 @@ extern "C" int vbmc_neg_elcbo_batch(vbmc_ctx* ctx, const double* thetas_BxN, int
   f.F = d_out; f.G = d_out + B; f.H = d_out + 2 * (size_t)B;
   hipLaunchKernelGGL(batch_finalize_kernel, dim3(B), dim3(256), sizeof(double) * ((size_t)S * D + 1), sm, f);
   HIP_TRY(ctx, hipGetLastError());
+  (void)who;
+  return 0;
+}
+
+extern "C" int vbmc_neg_elcbo_batch(vbmc_ctx* ctx, const double* thetas_BxN, int B, int n_theta,
+                                    const vbmc_elbo_opts* opts, double* F_B, double* G_B,
+                                    double* H_B) {
+  if (!ctx || !thetas_BxN || !opts || !F_B || B < 0) return VBMC_E_ARG;
+  NEED_DEVICE(ctx);
+  int rc = batch_score_check(ctx, "neg_elcbo_batch", B, n_theta, opts);
+  if (rc) return rc;
+  if (B == 0) return VBMC_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  Scratch sc;
+  BatchScore s;
+  const auto p_th = sc.add((size_t)B * n_theta);
+  batch_score_list(ctx, B, n_theta, opts, sc, s);
+  rc = reserve(ctx, sc);
+  if (rc) return rc;
+  rc = ensure_pinned(ctx, 3 * (size_t)B + batch_score_pinned(s));
+  if (rc) return rc;
+  double* d_th = sc.ptr(p_th);
+  hipStream_t sm = ctx->stream;
+  HIP_TRY(ctx, hipMemcpyAsync(d_th, thetas_BxN, sizeof(double) * (size_t)B * n_theta, hipMemcpyHostToDevice, sm));
+  rc = batch_score_queue(ctx, "neg_elcbo_batch", sc, s, opts, d_th, ctx->h_pinned + 3 * (size_t)B);
+  if (rc) return rc;
+  const double* d_out = sc.ptr(s.p_out);
+  const int* d_flags = sc.ptr(s.p_flags);
   int flags[2] = {0, 0};
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_pinned, d_out, sizeof(double) * 3 * (size_t)B, hipMemcpyDeviceToHost, sm));
   HIP_TRY(ctx, hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, sm));

@@ -150,9 +150,10 @@ struct ElboScratch {
 // product (timing level 2 only), the GP posterior's factorisation, the MCMC chains of vbmc_is_mcmc, one chunk of
 // vbmc_gp_lml (factorisation and gradient kernels), the three phases of the acquisition search (vbmc_search_fill's
 // launches; vbmc_search_eval's acquisition and mask; its sort and gather), all the rounds of one vbmc_gp_hyp_sample, all the rounds of one vbmc_search_cmaes,
-// all the rounds of one vbmc_gp_hyp_optimize
+// all the rounds of one vbmc_gp_hyp_optimize, the three phases of the sieve (vbmc_sieve_fill's launch; vbmc_sieve_eval's scoring
+// launches; its rank and gather)
 enum TimingPair { T_ENTMC = 0, T_GLJ, T_PDF, T_PREDICT, T_ELBO, T_PREDICT_VAR, T_GP_POST, T_IS_MCMC, T_GP_LML, T_SEARCH_FILL,
-                  T_SEARCH_EVAL, T_SEARCH_SORT, T_GP_HYP, T_SEARCH_CMAES, T_GP_OPT, T_COUNT };
+                  T_SEARCH_EVAL, T_SEARCH_SORT, T_GP_HYP, T_SEARCH_CMAES, T_GP_OPT, T_SIEVE_FILL, T_SIEVE_SCORE, T_SIEVE_RANK, T_COUNT };
 
 struct vbmc_ctx {
   int device = 0;
@@ -313,6 +314,7 @@ struct vbmc_ctx {
   int opt_randn_dev = 1;      // vbmc_set_eps_numpy: the reference's stream generated on the device (0: on the host cores + PCIe)
   void* xf = nullptr;         // parameter-transformer descriptors, two slots (transform.hip)
   void* search = nullptr;     // the resident search set of the acquisition search (api_search.hip)
+  void* sieve = nullptr;      // the resident candidate set of the sieve (api_sieve.hip)
 };
 // the device's CU count, which sizes one round of workgroups (256 where the runtime reports none)
 inline int ctx_cus(const vbmc_ctx* ctx) { return ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256; }
@@ -322,6 +324,7 @@ void acq_is_free(vbmc_ctx* ctx);
 void randn_dev_free(vbmc_ctx* ctx);
 void xf_free(vbmc_ctx* ctx);  // transform.hip
 void search_free(vbmc_ctx* ctx);  // api_search.hip
+void sieve_free(vbmc_ctx* ctx);   // api_sieve.hip
 // device_randn.hip: the next n values of NumPy's legacy randn stream into d_out (device memory), state advanced as
 // vbmc_mt19937_randn does; VBMC_W_NOT_FUSED = not this path's size (the caller uses the host generator)
 int randn_device(vbmc_ctx* ctx, uint32_t* key, int* pos, int* has_gauss, double* gauss, double* d_out, int64_t n);
@@ -869,6 +872,44 @@ int search_score_rows(vbmc_ctx* ctx, const SearchScore& s, const double* d_X, in
                       double u, double* d_acq);
 int search_set_rows_cap();                       // the search set's row cap (2^20)
 int search_fail_wait(vbmc_ctx* ctx, int rc);     // a failed call waits for the copies it queued from its own host memory
+// api_batch.hip: the sieve's scoring launches (pack, GP sums, lower-bound entropy, finalisation) on B thetas that are in
+// device memory already, for vbmc_neg_elcbo_batch (its uploaded rows) and vbmc_sieve_eval (the resident set).  A call's
+// order: check (before anything is queued), list (the pieces into sc, behind the caller's own), the caller's reserve and
+// ensure_pinned (batch_score_pinned doubles at hp), queue.  F | G | H are then the piece p_out, the flags p_flags
+// ([0] the pack's non-finite status, [1] the first non-finite candidate or 0x7fffffff); s must outlive the stream wait.
+struct BatchScore {
+  int B = 0, n_theta = 0, n_bnd = 0, n_aux = 0, mask = 0;
+  size_t stride = 0;
+  MixLayout ml;
+  Piece<> p_aux, p_packs, p_res, p_H, p_out, p_base, p_bnd;
+  Piece<int> p_flags;
+  int flags0[2] = {0, 0};  // host source of the flags' upload
+};
+int batch_score_check(vbmc_ctx* ctx, const char* who, int B, int n_theta, const vbmc_elbo_opts* opts);
+void batch_score_list(const vbmc_ctx* ctx, int B, int n_theta, const vbmc_elbo_opts* opts, Scratch& sc, BatchScore& s);
+size_t batch_score_pinned(const BatchScore& s);
+int batch_score_queue(vbmc_ctx* ctx, const char* who, const Scratch& sc, BatchScore& s, const vbmc_elbo_opts* opts, double* d_th,
+                      double* hp);
+// sieve.hip: the candidate generator of the sieve (api_sieve.hip), one workgroup per candidate, on ctx->stream.  All
+// pointers device memory; a null Z = the draws come from Philox under `seed` (streams 10, 11, 12: csrc/sieve.hip).
+struct SieveFillDev {
+  int D = 0, K = 0, Kn = 0, mask = 0, n_theta = 0, Ns = 0, n_slot = 0;
+  long long n1 = 0, n2 = 0, n3 = 0;
+  unsigned long long seed = 0;
+  const double* base = nullptr;   // mu0 [K][D] | sigma0 [K] | lambd0 [D] | w0 [K]
+  const double* t2 = nullptr;     // type 2's start: mu [Kn][D] | sigma [Kn]
+  const double* lam_s = nullptr;  // [D]: types 2 and 3 with optimised lambd
+  const double* Xs = nullptr;     // [Ns][D]
+  double v3 = 0.0;                // type 3 with K == 1: mean_d var(X_star[:, d], ddof = 1)
+  const double* Z = nullptr;      // [B][n_slot]
+  const int* I = nullptr;         // [B][Kn]
+  double* thetas = nullptr;       // [B][n_theta]
+};
+// dynamic LDS of a workgroup; n_keys: N_star where type 3's selection is ranked on the device (Philox draws), else 0
+size_t sieve_fill_lds_bytes(int D, int Kn, int n_keys);
+int launch_sieve_fill(vbmc_ctx* ctx, const SieveFillDev& a);
+// F, G, H [b] = NaN where row b of thetas holds a value that is not finite
+int launch_sieve_nan_rows(vbmc_ctx* ctx, const double* d_thetas, int64_t B, int n_theta, double* d_F, double* d_G, double* d_H);
 // cmaes.hip: the lockstep CMA-ES runs of vbmc_search_cmaes.  One advance launch moves every run on by one generation:
 // run r consumes val[r lam .. r lam + lam) (round 1: val[r], the start's value) and writes its next lam candidates,
 // rounded, into rows[r lam ..] (round 0: the start into rows[r]).  All pointers device memory; the constants are the

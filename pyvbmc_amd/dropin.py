@@ -36,6 +36,10 @@ mirror's own slice sampler and stream).  ``patch_active_sampling(mod, search=Tru
 (active_sample.py:647-837) to ``pyvbmc_amd.active_search.get_search_points`` -- with ``VBMC_HIP_RNG=philox`` the search
 points are then drawn on the device -- again with the reference's function behind it; the reference's ``active_sample``
 keeps its own evaluate / argsort lines (:334-349): only callers of ``pyvbmc_amd.search`` get the fused stage.
+
+``patch_sieve(vo)`` is another explicit step: it replaces ``_sieve`` by ``pyvbmc_amd.sieve.sieve`` -- the candidates
+drawn, scored and ranked on the device -- with the binding it finds (``make_sieve``'s wrapper after ``patch``, else the
+reference's function) behind it for shapes the mirror refuses; ``patch`` and ``make_sieve`` are unchanged by it.
 """
 import numpy as np
 
@@ -310,6 +314,54 @@ def unpatch_whitening(mod):
             setattr(mod, n, ref)
     delattr(mod, _SAVED_WARP)
     return mod
+
+
+_SAVED_SIEVE = "_pyvbmc_amd_saved_sieve"
+
+
+def patch_sieve(vo=None):
+    """Rebind ``_sieve`` on ``vo`` (default: ``pyvbmc.vbmc.variational_optimization``; ``optimize_vp`` looks the name up
+    at call time, :146) to ``pyvbmc_amd.sieve.sieve``: the candidates drawn, scored and ranked on the device.  The binding
+    it replaces -- ``make_sieve``'s wrapper if ``patch()`` ran before, else the reference's function -- stays behind it
+    for ``_lib.UnsupportedShape`` / ``_lib.NoDeviceError``: the mirror refuses before its first draw and before it touches
+    ``vp``, so the previous binding starts from untouched state.  The draws follow ``VBMC_HIP_RNG``.  Opt-in (``patch()``
+    does not call it; call it after ``patch()``, which saves and restores ``_sieve`` itself) and idempotent; returns ``vo``."""
+    from .sieve import sieve as _sieve_mirror
+
+    if vo is None:
+        import importlib
+
+        vo = importlib.import_module("pyvbmc.vbmc.variational_optimization")
+    if hasattr(vo, _SAVED_SIEVE):
+        unpatch_sieve(vo)
+    prev = getattr(vo, "_sieve", None)
+    setattr(vo, _SAVED_SIEVE, prev)
+
+    def _sieve(options, optim_state, vp, gp, init_N=None, best_N=1, K=None):
+        try:
+            return _sieve_mirror(options, optim_state, vp, gp, init_N, best_N, K)
+        except (_lib.UnsupportedShape, _lib.NoDeviceError):
+            if not callable(prev):
+                raise
+            return prev(options, optim_state, vp, gp, init_N, best_N, K)
+
+    _sieve.__doc__ = _sieve_mirror.__doc__
+    _sieve.__wrapped__ = _sieve_mirror
+    vo._sieve = _sieve
+    return vo
+
+
+def unpatch_sieve(vo):
+    """Put back what ``patch_sieve`` replaced."""
+    if not hasattr(vo, _SAVED_SIEVE):
+        return vo
+    prev = getattr(vo, _SAVED_SIEVE)
+    if prev is None:
+        delattr(vo, "_sieve")
+    else:
+        vo._sieve = prev
+    delattr(vo, _SAVED_SIEVE)
+    return vo
 
 
 _SAVED_LOOP = "_pyvbmc_amd_saved_active_sample"
