@@ -889,6 +889,50 @@ int vbmc_sieve_put(vbmc_ctx* ctx, int64_t B, int n_theta, const double* thetas_B
 int vbmc_sieve_eval(vbmc_ctx* ctx, const vbmc_elbo_opts* opts, double* F_B, double* G_B, double* H_B, int64_t* order_B,
                     double* thetas_sorted_BxN);
 
+/* ---- the last stage of optimize_vp: full ELCBO and the pruning trials ------ *
+ *
+ * After the optimiser, vbmc/variational_optimization.py evaluates the full ELCBO with variance and per-component terms
+ * (_eval_full_elcbo, :428-499: _neg_elcbo with compute_var and separate_K) and evaluates it again for every pruning
+ * trial, on the posterior with one component removed (:322-378).  Removing a component leaves mu, sigma, lambd of the
+ * others as they are and rescales their weights, so a trial's G, varG and var_ss are a re-weighting of the I_sk (S x K)
+ * and J_sjk (S x K x K) of the first evaluation (:1578-1596); only the Monte-Carlo entropy is new.
+ *
+ * The context owns one RECORD: S, K0, I_sk and J_sjk at stride K0 in device memory of its own (later scratch use does
+ * not touch it), the current mixture, and the alive list -- the columns of the record the current mixture's components
+ * stand for, 0..K0-1 at first.
+ *
+ * vbmc_elcbo_full replaces one _eval_full_elcbo (:474-485 with :1080-1183): theta -> mixture (vbmc_theta_to_mixture),
+ * the GP sums and, with compute_var, the variance launches of vbmc_gp_log_joint, the value-only entropy launches
+ * (ns_per_comp > 0: Monte Carlo as vbmc_entmc, draws by eps_mode / seed; 0: the lower bound as vbmc_entlb), then the
+ * re-weighting kernel; one stream wait.  out = nelbo, G, H, varF, varG, varH, var_ss (:1179-1183, :1578-1596; varH = 0
+ * as there).  I_SxK, J_SxKxK nullable.  compute_var = 0 (skip_elbo_variance): no J in the record, variances 0.
+ * theta's eta tail is max-shifted in place (:1082-1085).
+ *
+ * vbmc_elcbo_prune_trial evaluates the record's mixture without the component at position `drop` of the alive list
+ * (:335-350): delete, get_parameters (variational_posterior.py:642-676), set_parameters (:720-756) -- the softmax of
+ * the remaining log weights with max shift, the lambd / sigma renormalisation; the result becomes the context's mixture
+ * (host copy included).  Entropy launches at K' = K_alive - 1, G / varG / var_ss from the re-weighting kernel over the
+ * record.  No GP kernel is launched; seven doubles come down after one wait.  drop = -1 removes nothing: the record's
+ * mixture as it is, evaluated from the record (after vbmc_elcbo_put: the values of the installed arrays).
+ *
+ * vbmc_elcbo_prune_accept makes the last trial's alive list and mixture the record's (:365-376).
+ *
+ * vbmc_elcbo_put installs a record from host arrays with the context's current mixture (K0 components) as its mixture;
+ * J_SxK0xK0 NULL = a record without variance.
+ *
+ * vbmc_elcbo_record_info: info = S, K0, K_alive, launches of the GP expected log joint (its sums, its variance) queued
+ * on this context since the record was made, stream waits of this context since then; alive_K0 (nullable) receives the
+ * K_alive alive columns.
+ *
+ * The re-weighting kernel (csrc/elcbo_full.hip) restates the host loop of vbmc_gp_log_joint (csrc/api_gp.hip, :1578-1596):
+ * upper triangle j <= k, both clamps at np.spacing(1).  D <= 32, K <= 128, else VBMC_E_UNSUP. */
+int vbmc_elcbo_full(vbmc_ctx* ctx, double* theta, int n_theta, int optimize_mask, int64_t ns_per_comp, int eps_mode,
+                    uint64_t seed, int compute_var, double out[7], double* I_SxK, double* J_SxKxK);
+int vbmc_elcbo_prune_trial(vbmc_ctx* ctx, int drop, int64_t ns_per_comp, int eps_mode, uint64_t seed, double out[7]);
+int vbmc_elcbo_prune_accept(vbmc_ctx* ctx);
+int vbmc_elcbo_put(vbmc_ctx* ctx, int S, int K0, const double* I_SxK0, const double* J_SxK0xK0);
+int vbmc_elcbo_record_info(const vbmc_ctx* ctx, int64_t info[5], int32_t* alive_K0);
+
 /* ---- sampling and its Monte-Carlo consumers -------------- */
 
 /* VariationalPosterior.sample in transformed space, Gaussian components

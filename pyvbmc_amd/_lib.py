@@ -285,6 +285,11 @@ SIGNATURES = {
     "vbmc_sieve_fill": (C.c_int, [_vp, C.POINTER(SieveFillArgs), _dp]),
     "vbmc_sieve_put": (C.c_int, [_vp, C.c_int64, C.c_int, _dp]),
     "vbmc_sieve_eval": (C.c_int, [_vp, C.POINTER(ElboOpts), _dp, _dp, _dp, C.POINTER(C.c_int64), _dp]),
+    "vbmc_elcbo_full": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _dp]),
+    "vbmc_elcbo_prune_trial": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, C.c_uint64, _dp]),
+    "vbmc_elcbo_prune_accept": (C.c_int, [_vp]),
+    "vbmc_elcbo_put": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp]),
+    "vbmc_elcbo_record_info": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),  # info[5]
     "vbmc_mixture_sample": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, C.POINTER(C.c_int32)]),
     "vbmc_mixture_sample_t": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, C.c_double, _dp, C.POINTER(C.c_int32)]),
     "vbmc_kl_div_mc": (C.c_int, [_vp, C.c_int64, C.c_uint64, C.c_int, _dp, _dp, _dp, _dp, _dp]),
@@ -500,6 +505,16 @@ class Context:
             raise ValueError("mixture attribute shapes do not match (D, K)")
         self.check(self._lib.vbmc_set_mixture(self._h, D, K, ptr(mu_kd), ptr(s), ptr(l), ptr(ww), ptr(e)))
         self.D, self.K = D, K
+
+    def mixture_changed(self, D, K):
+        """An entry point installed a mixture of its own (``vbmc_elcbo_full``, ``vbmc_elcbo_prune_trial``, a direct
+        ``set_mixture``): the Python-side records of what the device holds -- ``upload_vp``'s last arguments, the repeat
+        record of the fused ``_neg_elcbo`` -- are dropped and ``D``, ``K`` follow the library's."""
+        self.__dict__["_vp_args"] = None
+        self.D, self.K = int(D), int(K)
+        vo = sys.modules.get(__package__ + ".variational_optimization")
+        if vo is not None:
+            vo.clear_fast_path()
 
     def set_eps(self, eps_half, row_begin=0, row_count=None):
         eps_half = f64(eps_half)

@@ -44,6 +44,8 @@ SOURCES = [
     "api_search.hip",
     "sieve.hip",
     "api_sieve.hip",
+    "elcbo_full.hip",
+    "api_elcbo_full.hip",
     "cmaes.hip",
     "api_cmaes.hip",
     "sample.hip",

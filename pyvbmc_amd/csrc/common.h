@@ -315,6 +315,9 @@ struct vbmc_ctx {
   void* xf = nullptr;         // parameter-transformer descriptors, two slots (transform.hip)
   void* search = nullptr;     // the resident search set of the acquisition search (api_search.hip)
   void* sieve = nullptr;      // the resident candidate set of the sieve (api_sieve.hip)
+  void* elcbo = nullptr;      // the full-ELCBO record of optimize_vp's last stage (api_elcbo_full.hip)
+  uint64_t stream_waits = 0;  // stream_wait() calls so far (vbmc_elcbo_record_info reports them since the record)
+  uint64_t gp_launches = 0;   // launches of the GP expected log joint queued so far: its sums (prep.hip), its variance (gp.hip)
 };
 // the device's CU count, which sizes one round of workgroups (256 where the runtime reports none)
 inline int ctx_cus(const vbmc_ctx* ctx) { return ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256; }
@@ -325,6 +328,7 @@ void randn_dev_free(vbmc_ctx* ctx);
 void xf_free(vbmc_ctx* ctx);  // transform.hip
 void search_free(vbmc_ctx* ctx);  // api_search.hip
 void sieve_free(vbmc_ctx* ctx);   // api_sieve.hip
+void elcbo_free(vbmc_ctx* ctx);   // api_elcbo_full.hip
 // device_randn.hip: the next n values of NumPy's legacy randn stream into d_out (device memory), state advanced as
 // vbmc_mt19937_randn does; VBMC_W_NOT_FUSED = not this path's size (the caller uses the host generator)
 int randn_device(vbmc_ctx* ctx, uint32_t* key, int* pos, int* has_gauss, double* gauss, double* d_out, int64_t n);
@@ -552,6 +556,7 @@ GenSlice make_gen_slice(double* eps, int K, int D, int64_t rows, int64_t n_half,
 // wait for everything queued on the ctx stream (also: the pinned mixture pack is free again)
 inline hipError_t stream_wait(vbmc_ctx* ctx) {
   if (ctx->spec.armed) spec_disarm(ctx);  // (launches waiting for a theta would make this wait last their time-out)
+  ++ctx->stream_waits;
   const hipError_t e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) ctx->pack_in_flight = false;
   return e;
@@ -910,6 +915,14 @@ size_t sieve_fill_lds_bytes(int D, int Kn, int n_keys);
 int launch_sieve_fill(vbmc_ctx* ctx, const SieveFillDev& a);
 // F, G, H [b] = NaN where row b of thetas holds a value that is not finite
 int launch_sieve_nan_rows(vbmc_ctx* ctx, const double* d_thetas, int64_t B, int n_theta, double* d_F, double* d_G, double* d_H);
+// elcbo_full.hip: the kernels of optimize_vp's last stage (api_elcbo_full.hip), on ctx->stream; all pointers device memory.
+// I_sk [S][K] from the GP sums d_res [S][K][1 + 2 D] of launch_gp_log_joint (api_gp.hip glj_finalize's I_k: the sum, the
+// mean function's constant and quadratic parts) for the context's mixture and GP
+int launch_elcbo_isk(vbmc_ctx* ctx, const double* d_res, double* d_I);
+// The re-weighting: G_s and varG_s over the alive columns alive[0 .. Ka) of I [S][K0] and J [S][K0][K0] (null: no
+// variance) with the weights w[0 .. Ka) into part [2][S], then out = G, varG, var_ss over s (api_gp.hip:246-288)
+int launch_elcbo_reweight(vbmc_ctx* ctx, int S, int K0, int Ka, const double* d_I, const double* d_J, const double* d_w,
+                          const int* d_alive, double* d_part, double* d_out);
 // cmaes.hip: the lockstep CMA-ES runs of vbmc_search_cmaes.  One advance launch moves every run on by one generation:
 // run r consumes val[r lam .. r lam + lam) (round 1: val[r], the start's value) and writes its next lam candidates,
 // rounded, into rows[r lam ..] (round 0: the start into rows[r]).  All pointers device memory; the constants are the

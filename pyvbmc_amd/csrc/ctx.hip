@@ -283,6 +283,7 @@ void vbmc_ctx_destroy(vbmc_ctx* ctx) {
   xf_free(ctx);
   search_free(ctx);
   sieve_free(ctx);
+  elcbo_free(ctx);
   gp_post_free(ctx);
   double* bufs[] = {ctx->d_mix, ctx->d_mix_fg, ctx->d_acq_fg, ctx->d_stage, ctx->d_eps, ctx->d_scratch, ctx->d_out, ctx->d_ptick, ctx->gp.d_X, ctx->gp.d_XT,
                     ctx->gp.d_alpha, ctx->gp.d_L, ctx->gp.d_Linv, ctx->gp.d_LinvP, ctx->gp.d_sW, ctx->gp.d_hyp,

@@ -990,6 +990,7 @@ int launch_gp_log_joint(vbmc_ctx* ctx, int want_grad, double* d_res, double* d_Z
 int launch_gp_var(vbmc_ctx* ctx, const double* d_Z, double* d_V, double* d_Q) {
   const GpState& g = ctx->gp;
   const int K = ctx->K, N = g.N, S = g.S;
+  ctx->gp_launches += 2;
   // V = Z L^-1 (upper-triangular skip) or Z L on the FP64 matrix cores, then the K x K Gram
   // matrix; every GP sample in the same two launches
   hipLaunchKernelGGL(predict_var_mfma_kernel, dim3((N + TS - 1) / TS, (K + TS - 1) / TS, S), dim3(256), 0,

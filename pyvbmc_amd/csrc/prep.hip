@@ -195,6 +195,7 @@ int launch_prep_on(vbmc_ctx* ctx, hipStream_t stream, const PrepArgs& a_in) {
   }
   if (lds > 64 * 1024)
     HIP_TRY(ctx, hipFuncSetAttribute((const void*)elbo_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (gblocks > 0) ++ctx->gp_launches;
   hipLaunchKernelGGL(elbo_prep_kernel, dim3(grid, a.batch), dim3(256), lds, stream, a);
   HIP_TRY(ctx, hipGetLastError());
   return 0;

@@ -364,6 +364,58 @@ def unpatch_sieve(vo):
     return vo
 
 
+_SAVED_OPTIMIZE_VP = "_pyvbmc_amd_saved_optimize_vp"
+
+
+def patch_optimize_vp(vo=None):
+    """Rebind ``optimize_vp`` on ``vo`` (default: ``pyvbmc.vbmc.variational_optimization``) to
+    ``pyvbmc_amd.optimize_vp.optimize_vp``: the sieve, Adam, the full ELCBO and the pruning trials on the device.  The
+    binding it replaces stays behind it for ``_lib.UnsupportedShape`` / ``_lib.NoDeviceError``: the mirror refuses what it
+    can see (D, K, N, the optimise flags, the options, a communicator, no device) before its first draw and before it
+    touches ``vp``, so the previous binding starts from untouched state.  One refusal is made later, by the sieve's
+    generator (``pyvbmc_amd/optimize_vp.py``, "Refusals"): the previous binding is still called, but
+    ``vp.optimize_weights`` may then already be off (warm-up).  The draws follow
+    ``VBMC_HIP_RNG``.  A module that bound the name by value (``from ... import optimize_vp``) keeps what it bound: rebind
+    it there as well, or pass ``pyvbmc_amd.optimize_vp`` to the caller (``active_sample(..., optimize_vp=...)``).  Opt-in
+    (``patch()`` does not call it) and idempotent; returns ``vo``."""
+    from .optimize_vp import optimize_vp as _mirror
+
+    if vo is None:
+        import importlib
+
+        vo = importlib.import_module("pyvbmc.vbmc.variational_optimization")
+    if hasattr(vo, _SAVED_OPTIMIZE_VP):
+        unpatch_optimize_vp(vo)
+    prev = getattr(vo, "optimize_vp", None)
+    setattr(vo, _SAVED_OPTIMIZE_VP, prev)
+
+    def optimize_vp(options, optim_state, vp, gp, fast_opts_N, slow_opts_N, K=None):
+        try:
+            return _mirror(options, optim_state, vp, gp, fast_opts_N, slow_opts_N, K)
+        except (_lib.UnsupportedShape, _lib.NoDeviceError):
+            if not callable(prev):
+                raise
+            return prev(options, optim_state, vp, gp, fast_opts_N, slow_opts_N, K)
+
+    optimize_vp.__doc__ = _mirror.__doc__
+    optimize_vp.__wrapped__ = _mirror
+    vo.optimize_vp = optimize_vp
+    return vo
+
+
+def unpatch_optimize_vp(vo):
+    """Put back what ``patch_optimize_vp`` replaced."""
+    if not hasattr(vo, _SAVED_OPTIMIZE_VP):
+        return vo
+    prev = getattr(vo, _SAVED_OPTIMIZE_VP)
+    if prev is None:
+        delattr(vo, "optimize_vp")
+    else:
+        vo.optimize_vp = prev
+    delattr(vo, _SAVED_OPTIMIZE_VP)
+    return vo
+
+
 _SAVED_LOOP = "_pyvbmc_amd_saved_active_sample"
 _LOOP_DEFAULTS = ("rng", "seed", "n_starts")
 
