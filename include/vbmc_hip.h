@@ -523,6 +523,49 @@ int vbmc_gp_hyp_optimize(vbmc_ctx* ctx, int N, int D, int P, int mean_kind, cons
                          double tol_g, double tol_f, int trace_cap, double* hyp_RxP, double* logpost_R, double* grad_RxP,
                          int64_t* stats_Rx4, int32_t* invalid_R, double* trace_iter, double* trace_eval);
 
+/* The GP hyper-parameter fit as ONE call: design, scoring and ranking of the candidates, vbmc_gp_hyp_optimize's runs from
+ * the best of them, vbmc_gp_hyp_sample's chains from the optimum and vbmc_gp_posterior's build at the samples, on one
+ * stream with the hand-overs done by kernels (csrc/gp_fit.hip).  X, y, s2 and the arrays below go up once in one block;
+ * the host reads the two lockstep drivers' counts of unfinished runs and nothing else; the results come back in one copy.
+ * pyvbmc_amd/gp.py states the stages in NumPy (GP.fit(optimizer="fused", device=False)).  lml, log p, the data and the
+ * prior arguments are vbmc_gp_hyp_sample's.
+ *   1 design    B = H + init_N candidates: the H rows of hyp0 clipped into [lb, ub], then init_N drawn rows, coordinate p
+ *               of drawn row j = clip(dlb_p + (dub_p - dlb_p) u, dlb_p, dub_p) with u the 53-bit uniform of words 0, 1 of
+ *               Philox block (p, 0, j, 10) under `seed`, no contraction.  [dlb, dub] inside [lb, ub] is the design box.
+ *   2 score     every candidate factorised (value only, in vbmc_gp_lml's chunks); score = lml + sum_p t_p, exactly what
+ *               vbmc_gp_hyp_optimize computes at a start; a candidate that is not finite or not positive definite, or a
+ *               score that is not finite, gives -inf, never an error.  Ranked by score descending, ties to the lower
+ *               index; the first R = min(opts_N, B) are the optimiser's starts (starts_R), one without a finite score an
+ *               invalid run.
+ *   3 optimise  (opts_N > 0) vbmc_gp_hyp_optimize's rounds from those starts (max_iter, m, tol_g, tol_f as there, no
+ *               trace).  The optimum: the best candidate and its score, replaced by the first run of greatest finite log
+ *               posterior where that is strictly greater.
+ *   4 sample    (n_samples > 0) vbmc_gp_hyp_sample's rounds: n_samples chains from the optimum under the same `seed`
+ *               (stream 6; the design's is stream 10), one kept sample each after burn_in + thin sweeps.
+ *   5 install   S = n_samples samples (n_samples = 0: S = 1, the optimum) are built as vbmc_gp_posterior builds them, read
+ *               from device memory, and left installed in the context exactly as that entry leaves its state; alpha_SxN,
+ *               L_SxNxN are downloaded only where given.
+ * Outputs (nullable except best_P, best_logpost, hyp_SxP, noise_S, status): cand_BxP, score_B; starts_R; the optimiser's
+ * opt_hyp_RxP, opt_logpost_R, opt_stats_Rx4, opt_invalid_R; best_P and best_logpost, the optimum; hyp_SxP the installed
+ * samples, with logpost_S, logprior_S, stats_Sx4 of the chains (n_samples = 0: logpost_S[0] = best_logpost);
+ * noise_S[s] = exp(2 hyp[s][D+1]) as the device formed it (sn2 = noise + s2, sn2_div = noise + min s2: the inputs that
+ * make vbmc_gp_posterior reproduce the installed state bit for bit); *status: bit 0 = no candidate has a finite score.
+ * Contracts: every refusal happens before any launch, every VBMC_E_ARG before every VBMC_E_UNSUP, through the check the
+ * two lockstep entries share: theirs, plus VBMC_E_ARG for dlb / dub outside [lb, ub] or dlb > dub (init_N > 0),
+ * H + init_N < 1, negative counts.  "No candidate has a finite score" comes with VBMC_OK and the status bit; then, and on
+ * any error, the installed GP is what it was.  The results depend on (data, hyp0, boxes, priors, options, seed) alone:
+ * not on the chunking (vbmc_set_option "gp_lml_chunk") or on the rounds per read ("gp_opt_rounds", "gp_hyp_rounds").
+ * vbmc_last_kernel_ms 12 and 14 report the chains' and the optimiser's rounds of the last call. */
+int vbmc_gp_fit(vbmc_ctx* ctx, int N, int D, int P, int mean_kind, const double* X_NxD, const double* y_N,
+                const double* s2_N, int H, const double* hyp0_HxP, int init_N, const double* dlb_P, const double* dub_P,
+                const double* lb_P, const double* ub_P, const double* prior_mu_P, const double* prior_sigma_P,
+                const double* prior_df_P, int opts_N, int max_iter, int m, double tol_g, double tol_f, int n_samples,
+                const double* widths_P, int thin, int burn_in, uint64_t seed, double* cand_BxP, double* score_B,
+                int32_t* starts_R, double* opt_hyp_RxP, double* opt_logpost_R, int64_t* opt_stats_Rx4,
+                int32_t* opt_invalid_R, double* best_P, double* best_logpost, double* hyp_SxP, double* logpost_S,
+                double* logprior_S, int64_t* stats_Sx4, double* noise_S, int32_t* status, double* alpha_SxN,
+                double* L_SxNxN);
+
 /* ---- a8: vbmc/variational_optimization.py:1238-1606 _gp_log_joint ------- */
 
 /* G, dG (enabled blocks; sigma/lambda/w blocks only under jacobian_flag,

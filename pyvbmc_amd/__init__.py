@@ -24,6 +24,8 @@ from .dropin import patch_sieve, unpatch_sieve  # noqa: F401
 from . import sieve  # noqa: F401
 from .dropin import patch_optimize_vp, unpatch_optimize_vp  # noqa: F401
 from .optimize_vp import optimize_vp  # noqa: F401
+from .dropin import patch_train_gp, unpatch_train_gp  # noqa: F401
+from .gaussian_process_train import train_gp  # noqa: F401
 from .entropy import entlb_vbmc, entmc_vbmc  # noqa: F401
 from .gp import GP, append_point, log_marginal_likelihood, reupdate  # noqa: F401
 from .variational_posterior import VariationalPosterior  # noqa: F401
@@ -34,4 +36,4 @@ __all__ = ["VariationalPosterior", "entmc_vbmc", "entlb_vbmc", "patch", "unpatch
            "unpatch_active_sampling", "GP", "log_marginal_likelihood", "get_search_points", "search", "refine",
            "whitening", "patch_whitening", "unpatch_whitening", "active_sample", "append_point", "reupdate",
            "patch_active_sample_loop", "unpatch_active_sample_loop", "sieve", "patch_sieve", "unpatch_sieve",
-           "optimize_vp", "patch_optimize_vp", "unpatch_optimize_vp"]
+           "optimize_vp", "patch_optimize_vp", "unpatch_optimize_vp", "train_gp", "patch_train_gp", "unpatch_train_gp"]

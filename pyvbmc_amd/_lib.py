@@ -241,6 +241,13 @@ SIGNATURES = {
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
          C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, _dp],
     ),
+    "vbmc_gp_fit": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+         C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _dp, C.c_int, C.c_int, C.c_uint64, _dp, _dp,
+         C.POINTER(C.c_int32), _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, _dp, _dp, _dp, _dp,
+         C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int32), _dp, _dp],
+    ),
     "vbmc_gp_log_joint": (
         C.c_int,
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp],

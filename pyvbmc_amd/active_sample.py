@@ -54,7 +54,10 @@ def _device_runs(pt, D):
 
 
 def _reference_callables(train_gp, optimize_vp, need_train, need_vp):
-    """The full update's callables: the ones passed in, else the reference's, imported on first need."""
+    """The full update's callables: the ones passed in, else the reference's, imported on first need.  (The default stays
+    the reference's ``train_gp``; the package's own -- one device call per fit that leaves the posterior installed -- is
+    ``pyvbmc_amd.gaussian_process_train.train_gp``: pass it as ``active_sample(..., train_gp=...)``, or bind it under the
+    drop-in with ``pyvbmc_amd.patch_train_gp()``.)"""
     if need_train and train_gp is None:
         try:
             from pyvbmc.vbmc.gaussian_process_train import train_gp

@@ -32,6 +32,8 @@ SOURCES = [
     "api_gp_hyp.hip",
     "gp_opt.hip",
     "api_gp_opt.hip",
+    "gp_fit.hip",
+    "api_gp_fit.hip",
     "api_elbo.hip",
     "api_batch.hip",
     "adam.hip",

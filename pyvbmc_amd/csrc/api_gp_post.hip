@@ -9,11 +9,10 @@
 
 #include "common.h"
 
-namespace {
-
-// host-side fields of the state under construction and the uploads that do not depend on the factorisation:
-// X, X^T, the predict centre, smeta, hyp, sW, y, sl.  h_X, h_y, hyp, h_sl of `w` are set by the caller.
-int stage_state(vbmc_ctx* ctx, GpState& w, int N, int D, int S, int P, int mean_kind, std::vector<double>& sW_host) {
+// The host-side fields of a device-built state that follow from h_X, h_sl and the shapes: L_chol, sn2_eff, sn2_mult, the
+// predict centre and smeta (h_small), X^T, and sW for the upload.  Stated once for the build entries here and for
+// vbmc_gp_fit, which installs the state it built from device-resident samples (api_gp_fit.hip).
+void gp_post_host_fields(GpState& w, int N, int D, int S, int P, int mean_kind, std::vector<double>& sW_host) {
   w.set = false;
   w.dev_built = false;
   w.N = N; w.D = D; w.S = S; w.P = P; w.mean_kind = mean_kind;
@@ -41,6 +40,17 @@ int stage_state(vbmc_ctx* ctx, GpState& w, int N, int D, int S, int P, int mean_
   w.h_XT.resize((size_t)N * D);
   for (int n = 0; n < N; ++n)
     for (int d = 0; d < D; ++d) w.h_XT[(size_t)d * N + n] = X[(size_t)n * D + d];
+}
+
+namespace {
+
+// host-side fields of the state under construction (gp_post_host_fields) and the uploads that do not depend on the
+// factorisation: X, X^T, the predict centre, smeta, hyp, sW, y, sl.  h_X, h_y, hyp, h_sl of `w` are set by the caller.
+int stage_state(vbmc_ctx* ctx, GpState& w, int N, int D, int S, int P, int mean_kind, std::vector<double>& sW_host) {
+  gp_post_host_fields(w, N, D, S, P, mean_kind, sW_host);
+  const double* X = w.h_X.data();
+  const double* xc = w.h_small.data();
+  const double* smeta = xc + D;
   hipStream_t st = ctx->stream;
   HIP_TRY(ctx, hipMemcpyAsync(w.d_smeta, smeta, sizeof(double) * 3 * S, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(w.d_xc, xc, sizeof(double) * D, hipMemcpyHostToDevice, st));

@@ -11,6 +11,7 @@
 
 #include "../../include/vbmc_hip.h"
 #include "gp_cand_host.h"
+#include "gp_fit_host.h"
 #include "scratch.h"
 #include "transform.h"
 
@@ -658,6 +659,17 @@ GpAppendWs gp_post_append_ws(int S, int N);
 int launch_gp_post_append(vbmc_ctx* ctx, const GpState& from, double y_new, const double* d_sn2_new, size_t sn2_stride,
                           const GpAppendWs& ws);
 void gp_post_free(vbmc_ctx* ctx);
+// api_gp_post.hip: the host-side fields of a device-built state w that follow from w.h_X, w.h_sl and the shapes (L_chol,
+// sn2_eff, sn2_mult, h_small = predict centre | smeta, h_XT) and sW as uploaded
+void gp_post_host_fields(GpState& w, int N, int D, int S, int P, int mean_kind, std::vector<double>& sW_host);
+// gp_fit.hip: the hand-over kernels of vbmc_gp_fit (gp_fit_host.h has their arguments).  design: the B candidate rows;
+// stage: candidates [b0, b0 + S) into the staged GP's slots; rank: scores from ws.lml and the prior, the order, the
+// optimiser's starts; select: the optimum and the chains' starts; handover: the S samples into the staged GP.
+int launch_gp_fit_design(vbmc_ctx* ctx, const GpFitArgs& f);
+int launch_gp_fit_stage(vbmc_ctx* ctx, const GpFitArgs& f, int b0, int S);
+int launch_gp_fit_rank(vbmc_ctx* ctx, const GpFitArgs& f);
+int launch_gp_fit_select(vbmc_ctx* ctx, const GpFitArgs& f);
+int launch_gp_fit_handover(vbmc_ctx* ctx, const GpFitArgs& f);
 // gp_lml.hip: value and gradient of the log marginal likelihood of ctx->gp's S candidates from the factor state
 // launch_gp_post_build left there.  d_sums [S][2], d_part [S][gp_lml_part_elems], d_mg [S][mean parameters]: workspace;
 // d_lml [S], d_dlml [S][P] (want_grad): results, device memory

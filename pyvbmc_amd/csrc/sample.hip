@@ -23,6 +23,8 @@
 //                                      run's own key
 //     c = (n_lo, n_hi, p,    9)        box draw n of warp_input's plausible / search box (warp.hip): words 0, 1 and 2, 3
 //                                      as the 53-bit uniforms of dimensions 2 p, 2 p + 1
+//     c = (p,    0,    j,    10)       coordinate p of drawn candidate j of the GP fit's design (gp_fit.hip): words 0, 1 as
+//                                      one 53-bit uniform, under that call's seed
 // oracle/sample_ref.py restates both.  Component choice: inverse CDF of the weights
 // (np.random.choice(p=w), :316-319); with balance_flag the first sum_k floor(w_k N) samples
 // are split exactly according to the weights and the remaining ones are drawn from the

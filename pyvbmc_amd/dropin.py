@@ -416,6 +416,66 @@ def unpatch_optimize_vp(vo):
     return vo
 
 
+_SAVED_TRAIN_GP = "_pyvbmc_amd_saved_train_gp"
+_TRAIN_GP_MODULES = ("pyvbmc.vbmc.gaussian_process_train", "pyvbmc.vbmc.vbmc", "pyvbmc.vbmc.active_sample")
+
+
+def patch_train_gp(mods=None, **defaults):
+    """Rebind ``train_gp`` to ``pyvbmc_amd.gaussian_process_train.train_gp`` -- the hyper-parameter fit as one device call
+    that leaves the posterior installed -- on every module of ``mods`` that carries the name (default: the reference's
+    ``gaussian_process_train`` and the two modules that bind the name by value, ``vbmc.py`` and ``active_sample.py``).
+    Each module's previous binding stays behind the mirror for ``_lib.UnsupportedShape`` / ``_lib.NoDeviceError``: the
+    mirror refuses (samplers other than slice sampling, noise forms and covariance functions the package's ``GP`` does not
+    take) before it touches ``hyp_dict`` or NumPy's global stream, so the previous binding starts from untouched state.
+    ``defaults``: the mirror's ``device``, ``seed``, ``ctx``.  The GP it returns is this package's ``GP``, which the
+    package's other mirrors and patches accept.  Opt-in (``patch()`` does not call it) and idempotent; returns the list
+    of modules it rebound."""
+    from .gaussian_process_train import train_gp as _mirror
+
+    unknown = set(defaults) - {"device", "seed", "ctx"}
+    if unknown:
+        raise TypeError(f"patch_train_gp: unknown defaults {sorted(unknown)} (device, seed, ctx)")
+    if mods is None:
+        import importlib
+
+        mods = [importlib.import_module(m) for m in _TRAIN_GP_MODULES]
+    done = []
+    for mod in mods:
+        if hasattr(mod, _SAVED_TRAIN_GP):
+            unpatch_train_gp([mod])
+        prev = getattr(mod, "train_gp", None)
+        if prev is None:
+            continue
+        setattr(mod, _SAVED_TRAIN_GP, prev)
+
+        def train_gp(hyp_dict, optim_state, function_logger, iteration_history, options, plb_tran, pub_tran, _prev=prev):
+            try:
+                return _mirror(hyp_dict, optim_state, function_logger, iteration_history, options, plb_tran, pub_tran, **defaults)
+            except (_lib.UnsupportedShape, _lib.NoDeviceError):
+                if not callable(_prev):
+                    raise
+                return _prev(hyp_dict, optim_state, function_logger, iteration_history, options, plb_tran, pub_tran)
+
+        train_gp.__doc__ = _mirror.__doc__
+        train_gp.__wrapped__ = _mirror
+        mod.train_gp = train_gp
+        done.append(mod)
+    return done
+
+
+def unpatch_train_gp(mods=None):
+    """Put back what ``patch_train_gp`` replaced."""
+    if mods is None:
+        import importlib
+
+        mods = [importlib.import_module(m) for m in _TRAIN_GP_MODULES]
+    for mod in mods:
+        if hasattr(mod, _SAVED_TRAIN_GP):
+            mod.train_gp = getattr(mod, _SAVED_TRAIN_GP)
+            delattr(mod, _SAVED_TRAIN_GP)
+    return mods
+
+
 _SAVED_LOOP = "_pyvbmc_amd_saved_active_sample"
 _LOOP_DEFAULTS = ("rng", "seed", "n_starts")
 

@@ -27,6 +27,11 @@ names so the hot-path functions accept either it or a real ``gpyreg.GP``:
   batch of C candidates per evaluation round, with a NumPy host route on the same draws.  The sampler, the priors and
   ``fit``'s stages are this package's own: gpyreg's are not in the reference tree, and neither its stream nor its
   default bounds are reproduced.
+* ``GP.fit(optimizer="fused")``: those stages as ONE device call (vbmc_gp_fit) -- the candidates drawn, scored and ranked,
+  the lockstep optimiser, the optimum selected, the lockstep chains and the posterior build, with kernels doing the
+  hand-overs and the posterior left installed; ``fit_design`` / ``fit_rank`` / ``fit_select`` and the ``device=False`` route
+  state it in NumPy.  ``get_bounds_info`` of the covariance, mean and noise classes is the package's own rule for bounds
+  from the data.  pyvbmc_amd/gaussian_process_train.py builds the reference's ``train_gp`` on it.
 """
 import math
 import ctypes as C
@@ -39,11 +44,37 @@ import scipy.linalg as sla
 from . import _lib
 
 
+# ``get_bounds_info(X, y) -> dict(LB, UB, PLB, PUB, x0)`` of the covariance, mean and noise classes below: hard bounds,
+# plausible bounds and a starting point per hyper-parameter of the block, from the data's ranges.  gpyreg has methods of
+# this name, but gpyreg is not part of the reference tree: the numbers here are THIS PACKAGE'S OWN RULE,
+# not gpyreg's defaults.  w_d = max X_d - min X_d, h = max y - min y; a zero range counts as 1.
+def _range(v, axis=None):
+    r = np.max(v, axis=axis) - np.min(v, axis=axis)
+    return np.where(r > 0, r, 1.0)
+
+
+def _spread(v, axis=None):
+    """std, and 1 where the range is zero (the std of a constant column is rounding noise, not a scale)"""
+    return np.where(np.max(v, axis=axis) - np.min(v, axis=axis) > 0, np.std(v, axis=axis), 1.0)
+
+
+def _log_scale_info(width, spread, lo=1e-6):
+    """log-scale block: LB log(lo w), UB log(10 w), PLB log(1e-3 w), PUB log w, x0 log spread"""
+    return dict(LB=np.log(lo * width), UB=np.log(10 * width), PLB=np.log(1e-3 * width), PUB=np.log(width), x0=np.log(spread))
+
+
 class SquaredExponential:
     """SE-ARD: k(a,b) = sf^2 exp(-1/2 sum_d ((a_d-b_d)/ell_d)^2); hyp = [log ell (D), log sf]."""
 
     def hyperparameter_count(self, D):
         return D + 1
+
+    def get_bounds_info(self, X, y):
+        """log length scales from w_d and std(X_d), log output scale from h and std(y) (the package's own rule)."""
+        X, y = np.atleast_2d(X), np.ravel(y)
+        ell = _log_scale_info(_range(X, 0), _spread(X, 0))
+        sf = _log_scale_info(np.atleast_1d(_range(y)), np.atleast_1d(_spread(y)))
+        return {k: np.concatenate([ell[k], sf[k]]) for k in ell}
 
     def compute(self, hyp, X, X_star=None):
         X = np.atleast_2d(X)
@@ -65,6 +96,17 @@ class ZeroMean:
     def compute(self, hyp, X):
         return np.zeros(X.shape[0])
 
+    def get_bounds_info(self, X, y):
+        return {k: np.zeros(0) for k in ("LB", "UB", "PLB", "PUB", "x0")}
+
+
+def _mean_const_info(y):
+    """constant of a mean: LB min y - h/2, UB max y + h/2, PLB / PUB the 0.1 / 0.9 quantiles of y, x0 median y"""
+    y = np.ravel(y)
+    h = float(_range(y))
+    return dict(LB=np.array([np.min(y) - 0.5 * h]), UB=np.array([np.max(y) + 0.5 * h]), PLB=np.array([np.quantile(y, 0.1)]),
+                PUB=np.array([np.quantile(y, 0.9)]), x0=np.array([np.median(y)]))
+
 
 class ConstantMean:
     kind = _lib.MEAN_CONST
@@ -74,6 +116,9 @@ class ConstantMean:
 
     def compute(self, hyp, X):
         return np.full(X.shape[0], hyp[0])
+
+    def get_bounds_info(self, X, y):
+        return _mean_const_info(y)
 
 
 class NegativeQuadratic:
@@ -89,6 +134,16 @@ class NegativeQuadratic:
         D = X.shape[1]
         return hyp[0] - 0.5 * np.sum(((X - hyp[1 : 1 + D]) / np.exp(hyp[1 + D : 1 + 2 * D])) ** 2, 1)
 
+    def get_bounds_info(self, X, y):
+        """the constant as ``ConstantMean``; location: LB / UB min X - w/2 ... max X + w/2, PLB / PUB min X ... max X, x0
+        median X; log scale: LB log(1e-3 w), UB log(10 w), PLB log(1e-2 w), PUB log w, x0 log std(X)."""
+        X = np.atleast_2d(X)
+        w, lo, hi = _range(X, 0), np.min(X, axis=0), np.max(X, axis=0)
+        c = _mean_const_info(y)
+        loc = dict(LB=lo - 0.5 * w, UB=hi + 0.5 * w, PLB=lo, PUB=hi, x0=np.median(X, axis=0))
+        om = dict(LB=np.log(1e-3 * w), UB=np.log(10 * w), PLB=np.log(1e-2 * w), PUB=np.log(w), x0=np.log(_spread(X, 0)))
+        return {k: np.concatenate([c[k], loc[k], om[k]]) for k in c}
+
 
 class GaussianNoise:
     def __init__(self, constant_add=False, user_provided_add=False, scale_user_provided=False,
@@ -100,6 +155,13 @@ class GaussianNoise:
 
     def hyperparameter_count(self):
         return 1
+
+    def get_bounds_info(self, X, y):
+        """log noise scale: LB log 1e-3, UB log max(h, 1), PLB log 1e-3, PUB log max(std(y), 1e-2), x0 log 1e-3."""
+        y = np.ravel(y)
+        lo = math.log(1e-3)
+        return dict(LB=np.array([lo]), UB=np.array([math.log(max(float(_range(y)), 1.0))]), PLB=np.array([lo]),
+                    PUB=np.array([math.log(max(float(np.std(y)), 1e-2))]), x0=np.array([lo]))
 
     def compute(self, hyp, X, y=None, s2=None):
         sn2 = np.full((X.shape[0], 1), np.exp(2 * hyp[0]) if self.constant_add else np.spacing(1.0))
@@ -672,11 +734,12 @@ _PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E377
 _SLICE_OUT_CAP, _SLICE_SHRINK_CAP, _SLICE_STREAM = 32, 64, 6
 
 
-def _philox_bits53(i, chain, seed):
-    """The upper 53 bits of words 0, 1 of Philox4x32-10 block (i_lo, i_hi, chain, 6) under key ``seed`` (csrc/philox.h):
-    draw i of chain ``chain`` of the slice samplers (stream 6 of csrc/sample.hip's list)."""
+def _philox_bits53(i, chain, seed, stream=_SLICE_STREAM):
+    """The upper 53 bits of words 0, 1 of Philox4x32-10 block (i_lo, i_hi, chain, stream) under key ``seed``
+    (csrc/philox.h).  Stream 6 (the default): draw i of chain ``chain`` of the slice samplers; stream 10: coordinate i of
+    drawn candidate ``chain`` of the fit's design (csrc/sample.hip lists the streams)."""
     m = 0xFFFFFFFF
-    c0, c1, c2, c3 = i & m, (i >> 32) & m, chain & m, _SLICE_STREAM
+    c0, c1, c2, c3 = i & m, (i >> 32) & m, chain & m, stream
     k0, k1 = seed & m, (seed >> 32) & m
     for _ in range(10):
         p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
@@ -1001,6 +1064,43 @@ def optimize_hyperparameters(gp, x0, *, lb, ub, priors=None, max_iter=200, histo
     return out
 
 
+# ------------------------------------------------------------------------------------- the fused fit's own stages
+_FIT_STREAM = 10
+
+
+def fit_design(init_N, dlb, dub, seed):
+    """The drawn candidates of ``GP.fit(optimizer="fused")`` (init_N, P), the statement of csrc/gp_fit.hip's design kernel:
+    coordinate p of row j is ``clip(dlb_p + (dub_p - dlb_p) u, dlb_p, dub_p)`` with u = bits * 2^-53, bits the upper 53
+    bits of words 0, 1 of Philox block (p, 0, j, stream 10) under ``seed``.  One product and one sum, each rounded, so
+    the device's rows are these bits."""
+    dlb, dub = np.asarray(dlb, dtype=np.float64), np.asarray(dub, dtype=np.float64)
+    P = dlb.size
+    out = np.empty((max(int(init_N), 0), P))
+    for j in range(out.shape[0]):
+        u = np.array([_philox_bits53(p, j, seed, _FIT_STREAM) for p in range(P)], dtype=np.float64) * 2.0**-53
+        out[j] = np.maximum(np.minimum(dlb + (dub - dlb) * u, dub), dlb)
+    return out
+
+
+def fit_rank(score):
+    """``(score with NaN and +inf as -inf, order)``: the candidates by score descending, ties to the lower index -- the
+    stable ``argsort(-score)`` of ``GP.fit``, what csrc/gp_fit.hip's counting rank produces."""
+    score = np.array(score, dtype=np.float64)
+    score[~np.isfinite(score)] = -np.inf
+    return score, np.argsort(-score, kind="stable")
+
+
+def fit_select(best_f, run_log_post, run_invalid):
+    """The optimum of the fused fit by ``GP.fit``'s lockstep-branch rule: ``(k, f)`` with k the first run of greatest
+    finite log posterior among the valid ones where that is strictly greater than the best candidate's score
+    ``best_f``, else ``(-1, best_f)``: the best candidate stays."""
+    k, bl = -1, -np.inf
+    for r, (lp, inv) in enumerate(zip(np.ravel(run_log_post), np.ravel(run_invalid))):
+        if not inv and np.isfinite(lp) and lp > bl:
+            k, bl = r, float(lp)
+    return (k, bl) if k >= 0 and bl > best_f else (-1, float(best_f))
+
+
 # hyper-parameter blocks by gpyreg's names, in the layout of hyp: (name, first index, length) for a GP of dimension D
 def _hyp_blocks(D, mean_n):
     blocks = [("covariance_log_lengthscale", 0, D), ("covariance_log_outputscale", D, 1), ("noise_log_scale", D + 1, 1)]
@@ -1216,7 +1316,11 @@ class GP:
         optimize_result, sample_result)``: ``optimize_result`` a dict ``hyp``, ``log_post``, ``candidates``,
         ``candidate_log_post``, ``n_iterations``; ``sample_result`` (None without sampling) a dict ``samples`` (S, P),
         ``log_priors`` (S,), ``log_post`` (S,), ``stats`` (S, 4).  gpyreg's own design of starting points, its default
-        bounds and its random stream are not reproduced."""
+        bounds and its random stream are not reproduced.
+
+        ``optimizer="fused"`` (opt-in; the two routes above and their results are unchanged): the same stages as one
+        device call with a counter-based design in its own box and the chains under the same ``seed`` -- ``_fit_fused``
+        states them; it also reads the option keys ``design_lb`` / ``design_ub``."""
         import scipy.optimize as sopt
 
         opts = {"init_N": 0, "opts_N": 1, "n_samples": 0, "thin": 1, "burn": 0, "widths": None, "tol_opt": 1e-5}
@@ -1236,6 +1340,8 @@ class GP:
         hyp0 = np.atleast_2d(np.asarray(hyp0, dtype=np.float64))
         if hyp0.shape[1] != P:
             raise ValueError(f"GP.fit: hyp0 has {hyp0.shape[1]} columns, the GP takes {P}")
+        if optimizer == "fused":
+            return self._fit_fused(hyp0, opts, options or {}, lb, ub, device, seed)
         rng = np.random.default_rng(seed)
         cand = np.clip(hyp0, lb, ub)
         if int(opts["init_N"]) > 0:
@@ -1253,7 +1359,7 @@ class GP:
             return -(lml[0] + lp), -(dl[0] + dp)
 
         if optimizer not in ("scipy", "lockstep"):
-            raise ValueError(f"GP.fit: optimizer '{optimizer}' is not 'scipy' or 'lockstep'")
+            raise ValueError(f"GP.fit: optimizer '{optimizer}' is not 'scipy', 'lockstep' or 'fused'")
         order = np.argsort(-score, kind="stable")
         best_h, best_f, n_it = cand[order[0]].copy(), float(score[order[0]]), 0
         if optimizer == "lockstep":
@@ -1286,6 +1392,114 @@ class GP:
             hyp = r["samples"][:, 0, :]
             smp_res = dict(samples=hyp, log_priors=r["log_priors"][:, 0], log_post=r["log_post"][:, 0], stats=r["stats"])
         self.update(hyp=hyp, device=device)
+        return hyp, opt_res, smp_res
+
+    def _fit_fused(self, hyp0, opts, options, lb, ub, device, seed):
+        """``fit(optimizer="fused")``: the stages of ``fit`` as ONE device call (vbmc_gp_fit, csrc/api_gp_fit.hip) with
+        the hand-overs done by kernels, or -- ``device=False``, and the shapes the device refuses (D > 32, a noise bound
+        that allows sn2_div < 1e-6, noise that is not constant-additive) -- the same stages in NumPy, which is the
+        statement of the algorithm:
+
+        1. candidates: ``hyp0`` clipped into the bounds, then ``init_N`` rows of ``fit_design`` in the design box
+           ``design_lb`` / ``design_ub`` (option keys; default the hard box) -- counter-based draws under ``seed``, the
+           same bits on both routes;
+        2. score = lml + log prior, NaN / not positive definite = -inf; ``fit_rank`` orders them; the first ``opts_N`` are
+           the optimiser's starts (``optimize_result["starts"]``), one without a finite score an invalid run;
+        3. ``optimize_hyperparameters`` from the starts; ``fit_select`` forms the optimum;
+        4. ``n_samples`` chains of ``sample_hyperparameters`` from the optimum under the same ``seed``, one kept sample
+           each after ``burn`` sweeps and ``thin`` more;
+        5. the posterior at the samples (the optimum without sampling), left installed on the device route.
+
+        Returns ``fit``'s triple; ``optimize_result`` also has ``starts`` and ``runs`` (the optimiser's ``hyp``,
+        ``log_post``, ``stats``, ``invalid`` per start)."""
+        P, pri = lb.size, self.hyper_priors
+        dlb = lb.copy() if options.get("design_lb") is None else np.array(np.broadcast_to(np.asarray(options["design_lb"], dtype=np.float64), (P,)))
+        dub = ub.copy() if options.get("design_ub") is None else np.array(np.broadcast_to(np.asarray(options["design_ub"], dtype=np.float64), (P,)))
+        if not (np.all(dlb >= lb) and np.all(dub <= ub) and np.all(dlb <= dub)):
+            raise ValueError("GP.fit: the design box must lie inside the bounds, with design_lb <= design_ub")
+        init_N, opts_N, S = (max(int(opts[k]), 0) for k in ("init_N", "opts_N", "n_samples"))
+        thin, burn, tol = int(opts["thin"]), int(opts["burn"]), float(opts["tol_opt"])
+        H = hyp0.shape[0]
+        B = H + init_N
+        if B < 1:
+            raise ValueError("GP.fit: no candidate (hyp0 is empty and init_N = 0)")
+        widths = (ub - lb) / 8 if opts["widths"] is None else np.asarray(opts["widths"], dtype=np.float64)
+        widths = _lib.f64(np.array(np.broadcast_to(widths, (P,))))
+        if S > 0 and not (np.all(widths > 0) and np.all(np.isfinite(widths)) and thin >= 1 and burn >= 0):
+            raise ValueError("GP.fit: widths must be positive, thin >= 1, burn >= 0")
+        seed = int(np.random.SeedSequence().generate_state(2, np.uint32).view(np.uint64)[0]) if seed is None else int(seed)
+        seed &= 0xFFFFFFFFFFFFFFFF
+        q = _hyper_problem("GP.fit", "H", self, lb[None, :], lb, ub, pri, self.ctx if device else None, device)
+        X, y, N, D = q.X, q.y, q.N, q.D
+        R, Sn = min(opts_N, B), max(S, 1)
+        max_iter, m, tol_f = 200, 8, 1e-9  # optimize_hyperparameters' defaults, as fit(optimizer="lockstep") runs it
+        if q.ctx is not None:
+            h0, dl, du = _lib.f64(hyp0), _lib.f64(dlb), _lib.f64(dub)
+            cand, score, starts = np.zeros((B, P)), np.zeros(B), np.zeros(R, dtype=np.int32)
+            o_hyp, o_lp = np.zeros((R, P)), np.zeros(R)
+            o_stats, o_inv = np.zeros((R, 4), dtype=np.int64), np.zeros(R, dtype=np.int32)
+            best, best_lp = np.zeros(P), np.zeros(1)
+            hyp, lpost, lprior = np.zeros((Sn, P)), np.zeros(Sn), np.zeros(Sn)
+            stats, noise, status = np.zeros((Sn, 4), dtype=np.int64), np.zeros(Sn), np.zeros(1, dtype=np.int32)
+            alpha, L = np.empty((Sn, N)), np.empty((Sn, N, N))
+            i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+            rc = q.ctx._lib.vbmc_gp_fit(
+                q.ctx._h, N, D, P, q.kind, _lib.ptr(X), _lib.ptr(y), _lib.ptr(q.s2), H, _lib.ptr(h0) if H else None, init_N,
+                _lib.ptr(dl), _lib.ptr(du), _lib.ptr(q.lb), _lib.ptr(q.ub), _lib.ptr(q.mu), _lib.ptr(q.sigma),
+                _lib.ptr(q.df), opts_N, max_iter, m, tol, tol_f, S, _lib.ptr(widths), thin, burn, C.c_uint64(seed),
+                _lib.ptr(cand), _lib.ptr(score), starts.ctypes.data_as(i32), _lib.ptr(o_hyp), _lib.ptr(o_lp),
+                o_stats.ctypes.data_as(i64), o_inv.ctypes.data_as(i32), _lib.ptr(best), _lib.ptr(best_lp), _lib.ptr(hyp),
+                _lib.ptr(lpost), _lib.ptr(lprior), stats.ctypes.data_as(i64), _lib.ptr(noise), status.ctypes.data_as(i32),
+                _lib.ptr(alpha), _lib.ptr(L))
+            if rc != _lib.E_UNSUP:
+                q.ctx.check(rc)
+                if status[0] & 1:
+                    raise ValueError("GP.fit: no candidate has a finite log posterior")
+                runs = dict(hyp=o_hyp, log_post=o_lp, stats=o_stats, invalid=o_inv)
+                opt_res = dict(hyp=best, log_post=float(best_lp[0]), candidates=cand, candidate_log_post=score,
+                               n_iterations=int(np.sum(o_stats[:, 0])), starts=starts.astype(np.int64), runs=runs)
+                smp_res = dict(samples=hyp, log_priors=lprior, log_post=lpost, stats=stats) if S > 0 else None
+                sn2_div = noise + (0.0 if q.s2 is None else float(np.min(q.s2)))
+                self.posteriors = _records(hyp, alpha, L, 1.0 / np.sqrt(sn2_div * 1.0))
+                _adopt(self, q.ctx, dev=True)
+                return hyp, opt_res, smp_res
+
+        # ---- the host route: the statement of the stages
+        cand = np.vstack([np.clip(hyp0, lb, ub), fit_design(init_N, dlb, dub, seed)])
+        finite_rows = np.all(np.isfinite(cand), axis=1)
+        score = np.full(B, -np.inf)
+        if np.any(finite_rows):
+            rows = cand[finite_rows]
+            with np.errstate(all="ignore"):
+                score[finite_rows] = log_marginal_likelihood(self, rows, device=False) + hyper_log_prior(rows, pri)
+        score, order = fit_rank(score)
+        if not np.any(np.isfinite(score)):
+            raise ValueError("GP.fit: no candidate has a finite log posterior")
+        starts = order[:R].astype(np.int64)
+        o_hyp, o_lp = np.zeros((R, P)), np.zeros(R)
+        o_stats, o_inv = np.zeros((R, 4), dtype=np.int64), np.zeros(R, dtype=np.int32)
+        for r, i in enumerate(starts):  # (the runs are independent of each other: one call each finds the invalid ones)
+            try:
+                if not np.isfinite(score[i]):
+                    raise ValueError("Invalid value.")
+                res = optimize_hyperparameters(self, cand[i][None, :], lb=lb, ub=ub, priors=pri, max_iter=max_iter, history=m,
+                                               tol_g=tol, tol_f=tol_f, device=False)
+                o_hyp[r], o_lp[r], o_stats[r] = res["hyp"][0], res["log_post"][0], res["stats"][0]
+            except ValueError:
+                o_inv[r] = 1
+        k, best_f = fit_select(float(score[order[0]]), o_lp, o_inv)
+        best_h = (o_hyp[k] if k >= 0 else cand[order[0]]).copy()
+        runs = dict(hyp=o_hyp, log_post=o_lp, stats=o_stats, invalid=o_inv)
+        opt_res = dict(hyp=best_h, log_post=best_f, candidates=cand, candidate_log_post=score,
+                       n_iterations=int(np.sum(o_stats[:, 0])), starts=starts, runs=runs)
+        if S <= 0:
+            hyp, smp_res = best_h[None, :].copy(), None
+        else:
+            r = sample_hyperparameters(self, np.tile(best_h, (S, 1)), lb=lb, ub=ub, widths=widths, priors=pri, n=1, thin=thin,
+                                       burn_in=burn, seed=seed, device=False)
+            hyp = r["samples"][:, 0, :]
+            smp_res = dict(samples=hyp, log_priors=r["log_priors"][:, 0], log_post=r["log_post"][:, 0], stats=r["stats"])
+        self.update(hyp=hyp, device=False)
         return hyp, opt_res, smp_res
 
     def predict(self, x_star, y_star=None, s2_star=0, add_noise=False, separate_samples=False, *,
