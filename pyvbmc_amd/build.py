@@ -9,6 +9,7 @@ to the GPU box with the working-tree snapshot.
 import os
 import subprocess
 import sys
+import sysconfig
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
@@ -65,6 +66,10 @@ SOURCES = [
 PROBE_SRC = CSRC / "devprobe.hip"
 PROBE_LIB = HERE / "libvbmc_devprobe.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# The native repeat lane of _neg_elcbo: a CPython extension (host C++ only) next to the library
+STEP_DEPS = [CSRC / "pyext_step.cpp", CSRC / "step_lane.h"]
+STEP_LIB = HERE / ("_step_native" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
+HOST_CXX = os.environ.get("CXX", "c++")
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -105,7 +110,7 @@ def _jobs(bdir):
 
 
 def _headers():
-    return list(CSRC.glob("*.h")) + [HERE.parent / "include" / "vbmc_hip.h"]
+    return [h for h in CSRC.glob("*.h") if h not in STEP_DEPS] + [HERE.parent / "include" / "vbmc_hip.h"]
 
 
 def _stale(lib, deps):
@@ -120,8 +125,41 @@ def _probe_stale():
     return _stale(PROBE_LIB, [PROBE_SRC] + _headers())
 
 
+def _step_stale():
+    return _step_buildable() and _stale(STEP_LIB, STEP_DEPS)
+
+
 def needs_build():
-    return _lib_stale() or _probe_stale()
+    return _lib_stale() or _probe_stale() or _step_stale()
+
+
+def _step_includes():
+    import numpy
+
+    return [sysconfig.get_paths()["include"], numpy.get_include()]
+
+
+def _step_buildable():
+    """The extension needs a host C++ compiler and the headers of this interpreter and of NumPy."""
+    import shutil
+
+    py, npy = (Path(p) for p in _step_includes())
+    return bool(shutil.which(HOST_CXX)) and (py / "Python.h").exists() and (npy / "numpy" / "arrayobject.h").exists()
+
+
+def build_step(verbose=True):
+    """The native repeat lane of _neg_elcbo (csrc/pyext_step.cpp), a CPython extension next to the library.  Without a
+    host compiler or the headers it is left out: variational_optimization then keeps its Python repeat path."""
+    if not _step_buildable():
+        print(f"{STEP_LIB.name}: no host C++ compiler or no Python / NumPy headers; the Python repeat path stays",
+              file=sys.stderr, flush=True)
+        return None
+    cmd = [HOST_CXX, "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall",
+           *(f"-I{p}" for p in _step_includes()), str(STEP_DEPS[0]), "-o", str(STEP_LIB)]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return STEP_LIB
 
 
 def build_probe(verbose=True):
@@ -135,6 +173,8 @@ def build_probe(verbose=True):
 def build(force=False, verbose=True):
     if force or _probe_stale():
         build_probe(verbose)
+    if force or _step_stale():
+        build_step(verbose)
     if not force and not _lib_stale():
         return LIB
     objs = []
@@ -179,3 +219,4 @@ if __name__ == "__main__":
     build(force="--force" in sys.argv)
     print(LIB)
     print(PROBE_LIB)
+    print(STEP_LIB)

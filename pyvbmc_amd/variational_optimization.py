@@ -281,13 +281,37 @@ def clear_fast_path():
     _fast_last[0] = None
 
 
-class _FastElbo:
+_FAST_FIELDS = ("ctx_arg", "ctx", "fc", "vp", "gp", "bnd", "Ns", "cg", "rng", "mask", "D", "K", "n_theta", "philox",
+                "lb", "ub", "tol", "wthr", "wpen", "fused_last")
+
+# The native repeat lane (csrc/pyext_step.cpp): a base type that holds _FAST_FIELDS and whose ``call`` is ``_call_py``
+# below without the interpreter.  Not built or not importable: the Python method is the repeat path.
+# VBMC_NATIVE_LANE=0 is a measurement aid that selects the Python method at import.
+_step_native = None
+if os.environ.get("VBMC_NATIVE_LANE", "1") != "0":
+    try:
+        from . import _step_native
+    except ImportError:
+        _step_native = None
+    if getattr(_step_native, "ABI", None) != 1:  # (built from another state of the source: as if absent, until rebuilt)
+        _step_native = None
+
+
+class _FastElboFields:
+    __slots__ = _FAST_FIELDS
+
+
+class _FastElbo(_FastElboFields if _step_native is None else _step_native.FastElboBase):
     """What a repeat of the last fused ``_neg_elcbo`` call needs: the argument block, and the objects and values the
     general path derived it from.  ``call`` re-checks everything that can change behind an unchanged identity and
-    returns None (the caller then takes the general path) unless all of it still holds."""
+    returns None (the caller then takes the general path) unless all of it still holds.
 
-    __slots__ = ("ctx_arg", "ctx", "fc", "vp", "gp", "bnd", "Ns", "cg", "rng", "mask", "D", "K", "n_theta", "philox",
-                 "lb", "ub", "tol", "wthr", "wpen", "fused_last")
+    ``call`` is the native base type's method where the extension is present; it hands whatever is not the plain repeat
+    to ``_call_py`` (a theta that is not an aligned contiguous float64 vector of ``n_theta`` elements, a seed that is
+    not an int) or, after its C call, to ``_finish_py`` (a return code, side effects still pending).  ``_call_py`` is the
+    statement of the behaviour, and the repeat path itself without the extension."""
+
+    __slots__ = ()
 
     def __init__(self, ctx_arg, ctx, fc, vp, gp, bnd, Ns, cg, rng, mask, D, K, n_theta, mode):
         self.ctx_arg, self.ctx, self.fc, self.vp, self.gp, self.bnd = ctx_arg, ctx, fc, vp, gp, bnd
@@ -299,8 +323,14 @@ class _FastElbo:
             self.tol, self.wthr, self.wpen = bnd["tol_con"], bnd.get("weight_threshold", 0.0), bnd.get("weight_penalty", 0.0)
             if not fc.direct:  # the bounds were copied (not float64 / not contiguous): the general path re-copies them
                 self.vp = None
+        if _step_native is not None and fc.block_call:
+            # the native lane calls the entry point through its address, taken from the loaded library once, here
+            o = fc.opts
+            self._bind_lane(C.cast(fc.fn, C.c_void_p).value, ctx._h.value, C.addressof(fc.block), fc.th, fc.dF,
+                            C.addressof(fc.F), C.addressof(fc.G), C.addressof(fc.H),
+                            C.addressof(o) + _lib.ElboOpts.seed.offset, (fc.block, o, fc.F, fc.G, fc.H, fc.fn))
 
-    def call(self, theta, seed):
+    def _call_py(self, theta, seed):
         if not _FAST_PATH:
             return None
         vp, ctx, fc, bnd = self.vp, self.ctx, self.fc, self.bnd
@@ -327,9 +357,19 @@ class _FastElbo:
         fc.side = (vp, theta, self.mask, self.K)
         try:
             rc = fc.fn(*fc.args)
+        except BaseException:
+            fc.side = None
+            raise
+        return self._finish_py(rc)
+
+    def _finish_py(self, rc):
+        """From the point after the C call: the return code, the side effects the release callback did not apply, the
+        result.  (The native ``call`` comes here with anything but return code 0 and side effects applied.)"""
+        ctx, fc = self.ctx, self.fc
+        try:
             if rc != 0:
                 if rc == _lib.W_GP_CHANGED:
-                    upload_gp(gp, ctx)
+                    upload_gp(self.gp, ctx)
                     rc = fc.fn(*fc.args)
                 if rc != 0:
                     ctx.check(rc)
@@ -338,6 +378,12 @@ class _FastElbo:
         finally:
             fc.side = None
         return fc.F.value, (fc.dF.copy() if self.cg else None), fc.G.value, fc.H.value, 0
+
+
+if _step_native is None:
+    _FastElbo.call = _FastElbo._call_py
+else:
+    _step_native.setup(globals(), vars(_lib), ctx_of, philox_seed)
 
 
 class _FusedCall:
@@ -371,8 +417,10 @@ class _FusedCall:
             _lib.ptr(self.lm), _lib.ptr(self.w), _lib.ptr(self.eta),
         )
         self.args = (ctx._h, C.byref(self.block))
+        self.block_call = True  # fn takes (handle, block): what the native repeat lane calls through fn's address
         if os.environ.get("VBMC_ELBO_CALL_BLOCK", "1") == "0":  # measurement aid: the thirteen-argument entry point
             self.fn = ctx._lib.vbmc_neg_elcbo
+            self.block_call = False
             self.args = (
                 ctx._h, _lib.ptr(self.th), n_theta, C.byref(o), C.byref(self.F), _lib.ptr(self.dF),
                 C.byref(self.G), C.byref(self.H), _lib.ptr(self.mu), _lib.ptr(self.sg), _lib.ptr(self.lm),
