@@ -1,0 +1,20 @@
+#!/usr/bin/env python
+"""A whole inference with no PyVBMC installed (needs an MI355X and the built library): a correlated 2-D normal in a box."""
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from pyvbmc_amd import VBMC  # noqa: E402
+
+P, MEAN = np.linalg.inv(np.array([[1.0, 0.6], [0.6, 0.5]])), np.array([0.5, -0.25])  # lnZ = 0
+
+
+def log_density(x):
+    return float(-0.5 * (np.ravel(x) - MEAN) @ P @ (np.ravel(x) - MEAN) - np.log(2 * np.pi) + 0.5 * np.log(np.linalg.det(P)))
+
+
+box = [np.full((1, 2), v) for v in (-10.0, 10.0, -2.0, 2.0)]  # hard bounds, then the plausible box
+vp, results = VBMC(log_density, np.zeros((1, 2)), *box, {"warp_rotoscaling": False, "max_fun_evals": 80}, seed=0).optimize()
+print("elbo %.3f +- %.3f, mean" % (results["elbo"], results["elbo_sd"]), vp.moments(rng="philox", seed=1).ravel(), results["timings"])

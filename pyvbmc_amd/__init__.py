@@ -30,10 +30,16 @@ from .entropy import entlb_vbmc, entmc_vbmc  # noqa: F401
 from .gp import GP, append_point, log_marginal_likelihood, reupdate  # noqa: F401
 from .variational_posterior import VariationalPosterior  # noqa: F401
 from .active_sample import active_sample  # noqa: F401
+from .parameter_transformer import ParameterTransformer  # noqa: F401
+from .function_logger import FunctionLogger  # noqa: F401
+from .options import Options  # noqa: F401
+from . import driver_rules  # noqa: F401
+from .vbmc import VBMC  # noqa: F401  (the inference loop over the stages above: no PyVBMC needed)
 
 __all__ = ["VariationalPosterior", "entmc_vbmc", "entlb_vbmc", "patch", "unpatch", "active_importance_sampling",
            "active_sample_proposal_pdf", "fess", "get_mcmc_opts", "renormalize_weights", "patch_active_sampling",
            "unpatch_active_sampling", "GP", "log_marginal_likelihood", "get_search_points", "search", "refine",
            "whitening", "patch_whitening", "unpatch_whitening", "active_sample", "append_point", "reupdate",
            "patch_active_sample_loop", "unpatch_active_sample_loop", "sieve", "patch_sieve", "unpatch_sieve",
-           "optimize_vp", "patch_optimize_vp", "unpatch_optimize_vp", "train_gp", "patch_train_gp", "unpatch_train_gp"]
+           "optimize_vp", "patch_optimize_vp", "unpatch_optimize_vp", "train_gp", "patch_train_gp", "unpatch_train_gp",
+           "VBMC", "Options", "FunctionLogger", "ParameterTransformer", "driver_rules"]

@@ -686,6 +686,7 @@ def kl_div_mvn(mu1, sigma1, mu2, sigma2):
     (reference pyvbmc/stats/kl_div_mvn.py:10-47)."""
     D = mu1.size
     dmu = mu2.reshape(-1, 1) - mu1.reshape(-1, 1)
+    sigma1, sigma2 = np.atleast_2d(sigma1), np.atleast_2d(sigma2)  # (D = 1: np.cov's 0-D variance, lifted as there)
     det1, det2 = np.linalg.det(sigma1), np.linalg.det(sigma2)
     if det1 == 0 or det2 == 0:
         return np.array([np.inf, np.inf])
