@@ -33,6 +33,7 @@ names so the hot-path functions accept either it or a real ``gpyreg.GP``:
   state it in NumPy.  ``get_bounds_info`` of the covariance, mean and noise classes is the package's own rule for bounds
   from the data.  pyvbmc_amd/gaussian_process_train.py builds the reference's ``train_gp`` on it.
 """
+import logging
 import math
 import ctypes as C
 import sys
@@ -378,13 +379,27 @@ def _device_build(gp, hyp, ctx, want_L):
     return alpha, L, sn2_div
 
 
-def _records(hyp, alpha, L, sW0):
+def _records(hyp, alpha, L, sW0, sn2_div=None, sn2_const=None):
+    """Records of a device build.  ``sn2_div`` (S): the scale the build used, kept exactly (``sW`` = 1 / sqrt of it does
+    not give it back); ``sn2_const`` (S): the constant noise term where the DEVICE formed it (``vbmc_gp_fit``), absent
+    where the host's noise rule gave the build its ``sn2``.  Both are what ``reinstall`` needs; the fingerprint and
+    ``upload_gp`` do not read them."""
     posts = np.empty(len(hyp), dtype=object)
     N = alpha.shape[1]
     for s in range(len(hyp)):
         posts[s] = SimpleNamespace(hyp=np.array(hyp[s], dtype=np.float64), alpha=alpha[s].reshape(-1, 1).copy(),
                                    sW=np.ones(N) * sW0[s], L=None if L is None else L[s], sn2_mult=1.0, L_chol=True)
+        if sn2_div is not None:
+            posts[s].sn2_div = float(sn2_div[s])
+        if sn2_const is not None:
+            posts[s].sn2_const = float(sn2_const[s])
     return posts
+
+
+def _carried(posts, name):
+    """The field ``name`` of every record, or None when one of them has none (records of another maker)."""
+    vals = [getattr(p, name, None) for p in posts]
+    return None if any(v is None for v in vals) else vals
 
 
 def device_posterior(gp, hyp=None, *, ctx=None, fetch=True):
@@ -412,7 +427,7 @@ def device_posterior(gp, hyp=None, *, ctx=None, fetch=True):
     if out is None:
         return False
     alpha, L, sn2_div = out
-    gp.posteriors = _records(hyp, alpha, L, 1.0 / np.sqrt(sn2_div * 1.0))
+    gp.posteriors = _records(hyp, alpha, L, 1.0 / np.sqrt(sn2_div * 1.0), sn2_div)
     _adopt(gp, ctx, dev=True)
     return True
 
@@ -434,6 +449,51 @@ def fetch_posteriors(gp, ctx=None):
             p.L = L[s]
     _adopt(gp, ctx, dev=dev)
     return posts
+
+
+def reinstall(gp, *, ctx=None):
+    """Put the posterior of a GP that comes from a pickle (or from another context) back on the device AS THE DEVICE
+    BUILT IT, so that ``append_point`` extends it with the arithmetic it would have used in the process that built it.
+
+    The records of this package carry the build's inputs: ``sn2_div``, the scale, and -- where ``vbmc_gp_fit`` formed the
+    constant noise term on the device -- ``sn2_const``.  ``vbmc_gp_posterior`` is called with them (``sn2`` = ``sn2_const``
+    + ``s2``, else the host's noise rule at the records' samples, which is what ``device_posterior`` passed) and the
+    ``alpha`` and ``L`` it returns must be ``np.array_equal`` to the records'.  Then the state is adopted as device-built,
+    the records' arrays stay the objects they are, and the call returns True.
+
+    Otherwise -- a record without ``sn2_div`` or without ``L``, the non-Cholesky branch, a shape the device refuses, a
+    build that does not reproduce the records (host-built records; a per-point-noise state extended by
+    ``vbmc_gp_append_noisy`` after a fit) -- the records are uploaded as they are (``upload_gp``: correct, but the next
+    append rebuilds), one warning says that a resumed run will not be bit-exact, and the call returns False.  Without a
+    device nothing is installed and the call returns False."""
+    ctx = _device_ctx(gp, ctx, True)
+    if ctx is None:
+        return False
+    posts = list(gp.posteriors)
+    sn2_div, sn2_const = _carried(posts, "sn2_div"), _carried(posts, "sn2_const")
+    if sn2_div is not None and all(p.L is not None and p.L_chol for p in posts):
+        X, y = _lib.f64(np.atleast_2d(gp.X)), _lib.f64(np.ravel(gp.y))
+        N, D = X.shape
+        hyp = _lib.f64(np.stack([np.ravel(p.hyp) for p in posts]))
+        s2 = _s2_column(gp)
+        if sn2_const is None:
+            sn2 = np.stack([_noise_var(gp, h[D + 1 : D + 2]) for h in hyp])
+        else:
+            sn2 = np.stack([np.full(N, c) if s2 is None else c + s2.ravel() for c in sn2_const])
+        sn2, div = _lib.f64(sn2), _lib.f64(sn2_div)
+        alpha, L = np.empty((len(posts), N)), np.empty((len(posts), N, N))
+        invalidate_gp(ctx)
+        rc = ctx._lib.vbmc_gp_posterior(ctx._h, N, D, len(posts), hyp.shape[1], mean_kind_of(gp), _lib.ptr(X), _lib.ptr(y),
+                                        _lib.ptr(sn2), _lib.ptr(div), _lib.ptr(hyp), _lib.ptr(alpha), _lib.ptr(L))
+        if rc == 0 and all(np.array_equal(alpha[s], np.ravel(p.alpha)) and np.array_equal(L[s], p.L)
+                           for s, p in enumerate(posts)):
+            _adopt(gp, ctx, dev=True)
+            return True
+    invalidate_gp(ctx)
+    upload_gp(gp, ctx)
+    logging.getLogger("GP").warning("reinstall: the device build does not reproduce the saved posterior records; they were "
+                                    "uploaded as saved, and a run resumed from them will not be bit-exact")
+    return False
 
 
 def _host_records(gp, hyp):
@@ -458,7 +518,8 @@ def _host_records(gp, hyp):
             L = -np.linalg.inv(Kxx + np.diag(sn2))
             alpha = -L @ resid
         posts[i] = SimpleNamespace(hyp=np.array(h, dtype=np.float64), alpha=alpha.reshape(-1, 1),
-                                   sW=np.ones(N) / np.sqrt(sn2_div), L=L, sn2_mult=1.0, L_chol=L_chol)
+                                   sW=np.ones(N) / np.sqrt(sn2_div), L=L, sn2_mult=1.0, L_chol=L_chol,
+                                   sn2_div=float(sn2_div))
     return posts
 
 
@@ -536,7 +597,9 @@ def append_point(gp, x_new, y_new, s2_new=None, *, ctx=None, device=True, fetch=
             gp.X, gp.y = X1, y1
             if s2_1 is not None:
                 gp.s2 = s2_1
-            gp.posteriors = _records(hyp, alpha, L, [np.ravel(p.sW)[0] for p in posts])
+            # (an append leaves the scale as it is: ``sn2_div`` and ``sn2_const`` go through unchanged)
+            gp.posteriors = _records(hyp, alpha, L, [np.ravel(p.sW)[0] for p in posts], _carried(posts, "sn2_div"),
+                                     _carried(posts, "sn2_const"))
             _adopt(gp, ctx, dev=True)
             return gp
     gp.X, gp.y, gp.s2 = X1, y1, s2_1
@@ -1169,6 +1232,7 @@ class GP:
         return SimpleNamespace(
             hyp=np.array(hyp, dtype=np.float64), alpha=alpha.reshape(-1, 1),
             sW=np.ones(N) / np.sqrt(sn2_div * sn2_mult), L=L, sn2_mult=sn2_mult, L_chol=L_chol,
+            sn2_div=float(sn2_div),
         )
 
     def update(self, X_new=None, y_new=None, s2_new=None, hyp=None, compute_posterior=True, *, device=False,
@@ -1460,7 +1524,7 @@ class GP:
                                n_iterations=int(np.sum(o_stats[:, 0])), starts=starts.astype(np.int64), runs=runs)
                 smp_res = dict(samples=hyp, log_priors=lprior, log_post=lpost, stats=stats) if S > 0 else None
                 sn2_div = noise + (0.0 if q.s2 is None else float(np.min(q.s2)))
-                self.posteriors = _records(hyp, alpha, L, 1.0 / np.sqrt(sn2_div * 1.0))
+                self.posteriors = _records(hyp, alpha, L, 1.0 / np.sqrt(sn2_div * 1.0), sn2_div, noise)
                 _adopt(self, q.ctx, dev=True)
                 return hyp, opt_res, smp_res
 

@@ -9,8 +9,14 @@ are named by their constructor strings, which ``acquisition.as_package_acq`` tur
 
 User options override the defaults; an unknown name raises ``ValueError`` (the reference's ``validate_option_names``).
 After construction an item is set only with ``options.__setitem__(key, value, force=True)``, as in the reference.
+
+Pickling.  The table holds lambdas, which plain ``pickle`` does not take, so an ``Options`` is written as its items with
+every callable that is still the table's own named by its key and looked up in ``DEFAULTS`` again on load; every other
+value is pickled as it is.  A user's callable that plain ``pickle`` refuses (a lambda, a closure) is written with ``dill``
+where ``dill`` imports, and raises a ``TypeError`` naming the option where it does not.
 """
 import copy
+import pickle
 from math import ceil
 
 import numpy as np
@@ -210,6 +216,38 @@ DEFAULTS = {
 }
 
 
+def _default_of(key, D):
+    value = DEFAULTS[key][1]
+    return value.f(D) if isinstance(value, AtD) else value
+
+
+def _import_dill():
+    try:
+        import dill
+    except ImportError:
+        return None
+    return dill
+
+
+def _restore_options(D, useroptions, is_initialized, attrs, items):
+    """Unpickling: ``items`` are ``(key, how, payload)`` in the dict's order -- ``how`` "default" (the table's callable of
+    that key), "value" (the value itself) or "dill" (a callable as ``dill.dumps`` wrote it)."""
+    new = Options.__new__(Options)
+    new.__dict__.update(attrs)
+    new.D, new.useroptions = D, set(useroptions)
+    for key, how, payload in items:
+        if how == "default":
+            payload = _default_of(key, D)
+        elif how == "dill":
+            dill = _import_dill()
+            if dill is None:
+                raise TypeError(f"option {key!r} was saved with dill, which is not installed")
+            payload = dill.loads(payload)
+        dict.__setitem__(new, key, payload)
+    new.is_initialized = is_initialized
+    return new
+
+
 class Options(dict):
     """``Options(D, user_options=None)``: the defaults at dimension ``D`` with the user's values over them."""
 
@@ -248,6 +286,41 @@ class Options(dict):
         """The option's value, called with ``evaluation_parameters`` (by keyword) when it is a callable."""
         v = self.get(key)
         return v(**evaluation_parameters) if callable(v) else v
+
+    def revise(self, new_options):
+        """Change items of a finished option set by name, with the constructor's validation (an unknown name raises
+        ``ValueError``): what ``VBMC.load(new_options=...)`` does, ``is_initialized`` toggled as in the reference."""
+        new_options = dict(new_options)
+        for key in new_options:
+            if key not in DEFAULTS:
+                raise ValueError("The option {} does not exist.".format(key))
+        self.is_initialized = False
+        try:
+            self.update(new_options)
+            self.useroptions = set(self.useroptions) | set(new_options)
+        finally:
+            self.is_initialized = True
+
+    def __reduce__(self):
+        """Plain ``pickle`` (module text): the table's own callables by key, everything else as it is."""
+        items = []
+        for key, v in self.items():
+            if callable(v):
+                if key in DEFAULTS and v is DEFAULTS[key][1]:
+                    items.append((key, "default", None))
+                    continue
+                try:
+                    pickle.dumps(v)
+                except Exception as exc:
+                    dill = _import_dill()
+                    if dill is None:
+                        raise TypeError(f"option {key!r}: its value {v!r} cannot be pickled (a lambda or a closure); make it "
+                                        "a module-level function, or install dill") from exc
+                    items.append((key, "dill", dill.dumps(v)))
+                    continue
+            items.append((key, "value", v))
+        attrs = {k: v for k, v in self.__dict__.items() if k not in ("D", "useroptions", "is_initialized")}
+        return _restore_options, (self.D, sorted(self.useroptions), self.is_initialized, attrs, items)
 
     def __copy__(self):
         new = Options.__new__(Options)

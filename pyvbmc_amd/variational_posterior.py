@@ -10,7 +10,8 @@ side effects and exceptions -- plus ``kl_div`` (:1032-1127), the Monte-Carlo con
 SURVEY.md 8f row 4 names, and ``mtv`` (:921-1030), the marginal total variation distance, whose
 density estimates, splines and integrals run on the device (csrc/kde.hip, vbmc_mtv; kde_1d itself is
 ``pyvbmc_amd.stats.kde_1d``), and ``mode`` (:810-919), whose start selection and local searches run on the
-device for all rounds at once (csrc/mode.hip, vbmc_mixture_mode).  ``plot`` is not provided.
+device for all rounds at once (csrc/mode.hip, vbmc_mixture_mode), and ``save`` / ``load`` (:1287-1343).  ``plot`` is not
+provided.
 
 Where the arithmetic runs: ``pdf``/``log_pdf`` -> HIP kernel (vbmc_mixture_pdf).
 State bookkeeping (get/set_parameters, bounds) and the closed-form K*D^2 moments are
@@ -129,6 +130,25 @@ class VariationalPosterior:
         st = self.__dict__.copy()
         st["_ctx"] = None
         return st
+
+    def save(self, file, overwrite=False):
+        """Write the posterior to ``file`` (:1287-1317): ``.pkl`` is appended to a name without a suffix,
+        ``FileExistsError`` for an existing file unless ``overwrite``; the write is atomic (pyvbmc_amd/_persist.py).  The
+        context is not part of the file."""
+        from . import _persist
+
+        _persist.save(self, file, overwrite)
+
+    @classmethod
+    def load(cls, file):
+        """The posterior ``save`` wrote (:1319-1343); it has no context until it is used or given one.  Loading a pickle
+        runs code: load only files you wrote yourself."""
+        from . import _persist
+
+        vp = _persist.load(file)
+        if not isinstance(vp, cls):
+            raise TypeError(f"{file}: holds a {type(vp).__name__}, not a {cls.__name__}")
+        return vp
 
     @property
     def ctx(self):

@@ -26,19 +26,43 @@ later -- a ``gp_hyp_sampler`` other than slicesample, a ``gp_mean_fun`` other th
 package has not, ``variable_means`` off, ``ns_ent_fast`` / ``ns_ent_fast_active`` / ``ns_ent_fast_boost`` above 0, ``k_warmup``
 or ``min_final_components`` above 128.
 
-Left out: plotting, save / load, ``__str__``; the ``varactivesample`` branch; ``_recompute_lcb_max`` (a stub in the
-reference as well); a separate ``prior`` object (``log_prior`` is taken).
+Save, load, checkpoints (:2148-2273).  ``save(file)`` writes the whole driver in one dump, atomically (_persist.py);
+``VBMC.load(file, new_options, iteration, set_random_state)`` reads it back without touching a device.
+``optimize(checkpoint=path, checkpoint_every=n)`` saves at the bottom of every n-th iteration and once more after the loop;
+iteration boundaries are the granularity (no signal handlers).  What a checkpoint promises:
+
+* An exact resume.  A run that is stopped and resumed from its checkpoint (``load`` with ``iteration=None``, then
+  ``optimize()``) is, bit for bit, the run that was never stopped: the file holds the base seed, the per-stage call counters
+  of the seeds, NumPy's global stream state at the save, the timings and the termination message; the first ``optimize()``
+  after a load continues at ``iteration + 1`` with them and first puts the live GP's posterior back on the device as the
+  device built it (``gp.reinstall``), so that the next one-point append takes the arithmetic route it took in the
+  uninterrupted run.  With a ``seed`` the run's stream is set to the saved state instead of being seeded, and the
+  caller's stream is put back on return as always; with ``seed=None`` the caller's stream is used as it is unless
+  ``set_random_state`` is given.  A driver whose ``optimize`` raised in the middle of an iteration is not resumable in
+  memory: resume from the file.
+* A valid, not exact, rewind.  ``iteration=k`` takes the posterior, the GP, the logger and the state from the history's
+  snapshots of iteration k, which are taken at different points of that iteration (the logger and the GP before the
+  warm-up trim, the state after it): a state to go on from, not the continuation of the run.
+* Nothing about the target.  The file is a pickle: a target (and a ``log_prior``) defined at module level is saved by
+  name; a lambda or a closure needs ``dill`` (used only where it imports) or cannot be saved, and whatever state a closure
+  carries -- a private ``Generator`` of a noisy target -- is the user's to save and restore.  Loading a pickle runs
+  code: load only files you wrote yourself.
+
+Left out: plotting, ``__str__``; the ``varactivesample`` branch; ``_recompute_lcb_max`` (a stub in the reference as well); a
+separate ``prior`` object (``log_prior`` is taken).
 """
 import contextlib
 import copy
 import logging
 import math
+import os
 import sys
 import time
 
 import numpy as np
 
 from . import _lib
+from . import _persist
 from . import driver_rules as rules
 from . import gp as gp_mod
 from .acquisition import as_package_acq
@@ -89,14 +113,18 @@ def stage_seed(seed, iteration, stage, n=0):
 
 
 @contextlib.contextmanager
-def _numpy_stream(seed, use):
-    """With a ``seed``: NumPy's global stream seeded for the block (``use`` 0: the constructor, 1: the run) and the
-    caller's state put back after it.  ``seed=None``: the caller's stream is used as it is."""
+def _numpy_stream(seed, use, resume_state=None):
+    """With a ``seed``: NumPy's global stream seeded for the block (``use`` 0: the constructor, 1: the run) -- or, for a
+    run resumed from a checkpoint, set to the state the checkpoint recorded -- and the caller's state put back after it.
+    ``seed=None``: the caller's stream is used as it is."""
     if seed is None:
         yield
         return
     state = np.random.get_state()
-    np.random.seed(stage_seed(seed, -1, use) % 2**32)
+    if resume_state is None:
+        np.random.seed(stage_seed(seed, -1, use) % 2**32)
+    else:
+        np.random.set_state(resume_state)
     try:
         yield
     finally:
@@ -325,6 +353,20 @@ def _refuse(D, options, optim_state):
         no(f"more than {_K_MAX} mixture components")
 
 
+class _LogJoint:
+    """``log_likelihood + log_prior`` as one target; ``noisy``: the likelihood returns ``(value, noise SD)``.  A class at
+    module level, so that a driver built from module-level functions pickles."""
+
+    def __init__(self, log_likelihood, log_prior, noisy):
+        self.log_likelihood, self.log_prior, self.noisy = log_likelihood, log_prior, noisy
+
+    def __call__(self, theta):
+        if self.noisy:
+            ll, noise_est = self.log_likelihood(theta)
+            return ll + self.log_prior(theta), noise_est
+        return self.log_likelihood(theta) + self.log_prior(theta)
+
+
 class VBMC:
     """``VBMC(log_density, x0, lower_bounds, upper_bounds, plausible_lower_bounds, plausible_upper_bounds, options=None, *,
     log_prior=None, ctx=None, rng="philox", seed=None)``; ``optimize()`` returns ``(vp, results)``.  Module docstring:
@@ -385,20 +427,26 @@ class VBMC:
             self.log_joint = log_density
         else:
             self.log_likelihood = log_density
-            if level == 2:
-                def log_joint(theta):
-                    ll, noise_est = log_density(theta)
-                    return ll + log_prior(theta), noise_est
-            else:
-                def log_joint(theta):
-                    return log_density(theta) + log_prior(theta)
-            self.log_joint = log_joint
+            self.log_joint = _LogJoint(log_density, log_prior, level == 2)
         self.function_logger = FunctionLogger(self.log_joint, D, level > 0, level, self.options["cache_size"],
                                               self.parameter_transformer)
         self.x0 = self.parameter_transformer(self.x0)
         self.iteration_history = {k: [] for k in HISTORY_KEYS}
         self.timer = StageTimer()
         self.timings = {k: 0.0 for k in STAGES}
+        # what a checkpoint carries beyond the above (module text): the calls made so far per seeded stage, the message,
+        # and -- filled in by ``save`` / ``load`` -- the stream state and whether the device held the live GP as built
+        self._stage_calls = {1: 0, 2: 0}
+        self._termination_message = ""
+        self._numpy_state = None
+        self._gp_dev_at_save = False
+        self._resume = None
+        self.checkpoint_log = []  # (iteration, seconds, bytes) of every checkpoint this process wrote
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_ctx"] = None
+        return st
 
     # ---- plumbing
     def _set_display(self):
@@ -439,12 +487,13 @@ class VBMC:
         return new
 
     def _seeded(self, fn, base, stage):
-        """``fn`` with the run's ``rng`` and context and, per call, the next seed of (iteration, stage)."""
-        count = [0]
+        """``fn`` with the run's ``rng`` and context and, per call, the next seed of (iteration, stage).  The count of a
+        stage's calls runs on across the iterations of a run and is part of a checkpoint (``_stage_calls``)."""
+        calls = self._stage_calls
 
         def call(*a, **kw):
-            count[0] += 1
-            return fn(*a, seed=stage_seed(base, self.iteration, stage, count[0]), ctx=self.ctx, **kw)
+            calls[stage] += 1
+            return fn(*a, seed=stage_seed(base, self.iteration, stage, calls[stage]), ctx=self.ctx, **kw)
 
         return call
 
@@ -454,17 +503,49 @@ class VBMC:
         return max(0, 0.5 * np.sum(kls))
 
     # ---- the loop
-    def optimize(self, on_iteration=None):
+    def optimize(self, on_iteration=None, *, checkpoint=None, checkpoint_every=1):
         """Run the inference: ``(vp, results)``.  ``on_iteration(driver)`` is called in every iteration right before the
         termination check, where the reference's tests wrap ``_check_termination_conditions``.  With a ``seed`` NumPy's
-        global stream is seeded for the run and the caller's state is put back on return."""
-        with _numpy_stream(self.seed, 1):
-            return self._optimize(on_iteration)
+        global stream is seeded for the run and the caller's state is put back on return.
 
-    def _optimize(self, on_iteration):
+        ``checkpoint``: a path; ``save(checkpoint, overwrite=True)`` at the bottom of every ``checkpoint_every``-th
+        iteration, after the history's ``random_state`` record, and once more after the loop with the final state.  On a
+        driver that ``load`` returned unfinished, the call continues the saved run (module text)."""
+        if checkpoint is not None and int(checkpoint_every) < 1:
+            raise ValueError("optimize: checkpoint_every must be at least 1")
+        resume, self._resume = self._resume, None
+        if resume is not None:
+            self._after_load(resume)
+        go_on = resume is not None and resume["go_on"]
+        with _numpy_stream(self.seed, 1, resume["numpy_state"] if go_on else None):
+            return self._optimize(on_iteration, go_on, checkpoint, int(checkpoint_every))
+
+    def _after_load(self, resume):
+        """The device side of a load, at the first ``optimize`` after it: every kept object on the driver's context, the
+        GP of a rewind re-updated where the logger's set is not the GP's, and the live GP's posterior installed again as
+        the device built it where the device held it so at the save (and after a rewind)."""
+        ctx, h = self.ctx, self.iteration_history
+        for obj in [self.vp, self.gp] + list(h["vp"]) + list(h["gp"]):
+            if obj is not None:
+                obj.ctx = ctx
+        if self.gp is None:
+            return
+        if resume["rewind"] and int(np.sum(self.function_logger.X_flag)) != self.gp.X.shape[0]:
+            self.gp = gp_mod.reupdate(self.function_logger, self.gp, ctx=ctx)
+        elif resume["rewind"] or self._gp_dev_at_save:
+            if not gp_mod.reinstall(self.gp, ctx=ctx):
+                self.logger.warning("The GP of the checkpoint could not be installed as the device had built it: the resumed "
+                                    "run is not bit-exact.")
+
+    def _optimize(self, on_iteration, resumed=False, checkpoint=None, checkpoint_every=1):
         options, timer = self.options, self.timer
-        base = int(self.seed) if self.seed is not None else int(np.random.randint(0, 2**62, dtype=np.int64))
-        self._base_seed = base
+        if resumed:  # the saved run goes on: its base seed, its call counters, its message
+            base = self._base_seed
+        else:
+            base = int(self.seed) if self.seed is not None else int(np.random.randint(0, 2**62, dtype=np.int64))
+            self._base_seed = base
+            self._stage_calls = {1: 0, 2: 0}
+            self._termination_message = ""
         self.logger.info("Beginning variational optimization assuming %s observations of the log-joint",
                          "NOISY" if self.optim_state["uncertainty_handling_level"] > 0 else "EXACT")
         if self.is_finished:
@@ -474,7 +555,7 @@ class VBMC:
             self.optim_state = _copy_state(self.iteration_history["optim_state"][-1])
         train = self._seeded(lambda *a, seed, ctx, **kw: train_gp(*a, seed=seed, ctx=ctx, **kw), base, 1)
         fit = self._seeded(lambda *a, seed, ctx, **kw: optimize_vp(*a, rng=self.rng, seed=seed, ctx=ctx, **kw), base, 2)
-        termination_message, vp_old = "", None
+        vp_old = None
 
         while not self.is_finished:
             self.iteration += 1
@@ -577,7 +658,7 @@ class VBMC:
                 on_iteration(self)
             self.is_finished, message = self._check_termination_conditions()
             if message:
-                termination_message = message
+                self._termination_message = message
             self.vp.stats["stable"] = self.iteration_history["stable"][it]
 
             # ---- still warming up? (:1309-1342)
@@ -612,6 +693,8 @@ class VBMC:
             self._record("random_state", np.random.get_state(), it)
             for k in STAGES[:4]:
                 self.timings[k] += timer.durations.get(k, 0.0)
+            if checkpoint is not None and (it + 1) % checkpoint_every == 0:
+                self._write_checkpoint(checkpoint)
 
         # ---- after the loop (:1493-1585)
         t0 = time.perf_counter()
@@ -625,12 +708,88 @@ class VBMC:
                              elbo_sd, sKL, self.vp.K, self.iteration_history["r_index"][idx_best])
         self.timings["boost"] += time.perf_counter() - t0
         success_flag = bool(self.vp.stats["stable"])
+        termination_message = self._termination_message
         self.logger.warning(termination_message)
         self.logger.warning("Estimated ELBO: {:.3f} +/-{:.3f}.".format(elbo, elbo_sd))
         if not success_flag:
             self.logger.warning("Caution: Returned variational solution may have not converged.")
         results = self._create_result_dict(idx_best, termination_message, success_flag)
+        if checkpoint is not None:
+            self._write_checkpoint(checkpoint)
         return self._copy_vp(self.vp), results
+
+    # ---- save, load, checkpoints (module text)
+    def _write_checkpoint(self, file):
+        t0 = time.perf_counter()
+        path = self.save(file, overwrite=True)
+        self.checkpoint_log.append((self.iteration, time.perf_counter() - t0, os.path.getsize(path)))
+
+    def save(self, file, overwrite=False):
+        """Write the driver to ``file`` (:2148-2184): ``.pkl`` is appended to a name without a suffix, ``FileExistsError``
+        for an existing file unless ``overwrite``.  One dump of the whole object, written atomically (_persist.py); with it
+        go NumPy's global stream state at this moment and whether the context holds the live GP's posterior as the device
+        built it.  A target that plain ``pickle`` refuses needs ``dill`` (module text).  Returns the path written."""
+        self._numpy_state = np.random.get_state()
+        ctx = self._ctx
+        dev_key = getattr(ctx, "_gp_dev", None) if ctx is not None and self.gp is not None else None
+        self._gp_dev_at_save = dev_key is not None and dev_key == gp_mod._gp_fingerprint(self.gp)[0]  # (no context: its caches stay)
+        return _persist.save(self, file, overwrite)
+
+    @classmethod
+    def load(cls, file, new_options=None, iteration=None, set_random_state=False, *, ctx=None):
+        """The driver ``save`` wrote (:2186-2273), on ``ctx`` (default: the default context, opened when first needed; the
+        load itself touches no device).  Loading a pickle runs code: load only files you wrote yourself.
+
+        ``new_options``: a dict of options to change, validated as the constructor validates them (an unknown name
+        raises ``ValueError``; what the constructor refuses is refused here) -- a larger ``max_fun_evals``, say, to go on
+        from a finished run, which ``optimize()`` then does from the last iteration's posterior.
+        ``iteration=None``: the live state of the file; an unfinished run is then resumed EXACTLY by ``optimize()`` (module
+        text).  ``iteration=k``, earlier than the last: the posterior, the GP, the logger and the state (with its
+        ``hyp_dict``) are copies of the history's snapshots of iteration k, every history list is cut to ``k + 1`` entries
+        and the posterior's ``optimize_mu`` / ``optimize_weights`` follow that state's ``warmup``.  Such a rewind is a valid
+        state to go on from, NOT the exact continuation: the snapshots are taken at different points of an iteration.
+        ``ValueError`` for a ``k`` outside ``0 .. last``.
+        ``set_random_state``: NumPy's global stream is set to the state recorded at the end of that iteration."""
+        vbmc = _persist.load(file)
+        if not isinstance(vbmc, cls):
+            raise TypeError(f"{file}: holds a {type(vbmc).__name__}, not a {cls.__name__}")
+        last = vbmc.iteration
+        if iteration is None:
+            iteration = last
+        elif not (0 <= iteration <= last):
+            raise ValueError(f"Specified iteration ({iteration}) should be >= 0 and <= last stored iteration ({last}).")
+        iteration = int(iteration)
+        h, rewind = vbmc.iteration_history, iteration < last
+        if rewind:
+            tr = vbmc.parameter_transformer
+            vbmc.vp = copy.deepcopy(h["vp"][iteration], {id(tr): tr})
+            vbmc.gp = copy.deepcopy(h["gp"][iteration])
+            vbmc.function_logger = _copy_logger(h["function_logger"][iteration])
+            vbmc.optim_state = _copy_state(h["optim_state"][iteration])
+            if vbmc.optim_state.get("hyp_dict") is not None:
+                vbmc.hyp_dict = vbmc.optim_state["hyp_dict"]
+            vbmc.iteration = iteration
+            for k in h:
+                h[k] = h[k][: iteration + 1]
+            if not vbmc.optim_state["warmup"]:  # (as the loop sets them where warm-up ends)
+                vbmc.vp.optimize_mu = vbmc.options["variable_means"]
+                vbmc.vp.optimize_weights = vbmc.options["variable_weights"]
+            vbmc.logging_action = list(h["logging_action"][iteration])
+        if new_options is not None:
+            vbmc.options.revise(new_options)
+            _refuse(vbmc.D, vbmc.options, vbmc.optim_state)
+            vbmc._set_display()
+        if set_random_state and iteration >= 0:
+            np.random.set_state(h["random_state"][iteration])
+        vbmc._ctx = ctx
+        # for the first ``optimize()``: ``go_on`` -- an unfinished run continues at ``iteration + 1`` on the saved seed,
+        # counters and stream (a finished one takes the "Continuing optimization" branch, seeded as a run of its own)
+        go_on = iteration >= 0 and not vbmc.is_finished
+        state = None
+        if go_on:
+            state = h["random_state"][iteration] if rewind or vbmc._numpy_state is None else vbmc._numpy_state
+        vbmc._resume = {"rewind": rewind, "go_on": go_on, "numpy_state": state}
+        return vbmc
 
     # ---- the decisions: driver_rules.py applied to the driver's state
     def _check_termination_conditions(self):
