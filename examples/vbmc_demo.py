@@ -32,3 +32,4 @@ else:
     vbmc = VBMC(log_density, np.zeros((1, 2)), *box, {"warp_rotoscaling": False, "max_fun_evals": 80}, seed=0)
 vp, results = vbmc.optimize(checkpoint=checkpoint)
 print("elbo %.3f +- %.3f, mean" % (results["elbo"], results["elbo_sd"]), vp.moments(rng="philox", seed=1).ravel(), results["timings"])
+print(vp.marginals(rng="philox", seed=2))  # the credible intervals per dimension (the numbers vp.plot() draws)

@@ -1092,6 +1092,31 @@ int vbmc_mtv(vbmc_ctx* ctx, int D, const vbmc_mtv_side* s1, const vbmc_mtv_side*
              const double* mu2_KxD, const double* sigma2_K, const double* lambd2_D, const double* w2_K,
              double* mtv_D, int64_t* info_2Dx2);
 
+/* ---- marginals of the variational posterior: the numbers of a corner plot ----
+ *
+ * VariationalPosterior.plot's call of corner.corner (variational_posterior.py:1191-1206): the D one-dimensional and
+ * P = D (D - 1) / 2 two-dimensional histograms of n samples, here with the order-statistic quantiles, the
+ * highest-density levels of every pair and the kde_1d curve of every column, in one call with one download.
+ * src: the samples, a vbmc_mtv_side -- VBMC_MTV_HOST: x_NxD uploaded; VBMC_MTV_MIX1: the n draws of the ctx mixture,
+ * unbalanced (vbmc_mixture_sample_t with `seed`), through transformer slot 0 when orig_flag
+ * (vbmc_mixture_sample_orig), which stay on the device; lb_D / ub_D are not read.  1 <= D <= 32, 1 <= bins <= 128,
+ * 1 <= n <= 2^22: VBMC_E_UNSUP beyond.  ranges_Dx2: (lo, hi) per dimension, lo < hi finite, or (NaN, NaN) for the
+ * column's own [min, max] ((min - 0.5, max + 0.5) when they are equal).  Binning is np.histogram's / np.histogram2d's:
+ * edges = linspace(lo, hi, bins + 1), a sample at hi in the last bin, a sample outside a dimension's range left out of
+ * that dimension's histogram and of every pair with it.  Out: edges (D x (bins + 1)), counts1 (D x bins), counts2
+ * (P x bins x bins, pair p = (i, j), i < j, row-major order; [p][a][b] = dimension i in bin a, j in bin b), inside2
+ * (P: the sum of counts2[p]), quantiles (nq x D: np.quantile's linear rule at q_nq), and per pair and level l of
+ * levels_nl: level_counts (P x nl), the count of the last cell of the shortest non-empty prefix of the cells sorted by
+ * count, descending, whose sum is >= l inside2[p], and level_mass (P x nl), the sum of the cells with at least that
+ * count over inside2[p] (NaN when inside2[p] is 0).  kde_mesh: 0, or 2^10 for kde_x, kde_density (D x 2^10) and
+ * kde_bandwidth (D): vbmc_kde_1d of every column with its range as the bounds.  stage_ms (nullable): six times between
+ * events -- samples, sort and columns, kde, bin indices, pair histograms, levels.  A non-finite sample ->
+ * VBMC_E_NONFINITE. */
+int vbmc_marginals(vbmc_ctx* ctx, int D, const vbmc_mtv_side* src, int orig_flag, int bins, const double* ranges_Dx2,
+                   int nq, const double* q_nq, int nl, const double* levels_nl, int kde_mesh, double* edges,
+                   int64_t* counts1, int64_t* counts2, int64_t* inside2, double* quantiles, int64_t* level_counts,
+                   double* level_mass, double* kde_x, double* kde_density, double* kde_bandwidth, float* stage_ms);
+
 /* ---- mode of the variational posterior (variational_posterior.py:810-919) ----
  *
  * VariationalPosterior.mode: n_opts rounds, each "n candidates (+ the K component centres in round 0), the one

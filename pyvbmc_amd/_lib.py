@@ -310,6 +310,9 @@ SIGNATURES = {
     "vbmc_kde_1d": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
     "vbmc_mtv": (C.c_int, [_vp, C.c_int, C.POINTER(MtvSide), C.POINTER(MtvSide), C.c_int, _dp, _dp, _dp, _dp, _dp,
                            C.POINTER(C.c_int64)]),
+    "vbmc_marginals": (C.c_int, [_vp, C.c_int, C.POINTER(MtvSide), C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp,
+                                 C.c_int, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp,
+                                 C.POINTER(C.c_int64), _dp, _dp, _dp, _dp, C.POINTER(C.c_float)]),
     "vbmc_mixture_mode": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int64, _dp, C.c_uint64, C.c_int, C.c_double, _dp, _dp,
                                     _dp, _dp, _dp]),
     "vbmc_warp_points": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, _dp, _dp, _dp, _dp]),

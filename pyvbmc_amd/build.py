@@ -54,6 +54,8 @@ SOURCES = [
     "sample.hip",
     "transform.hip",
     "kde.hip",
+    "marginals.hip",
+    "api_marginals.hip",
     "mode.hip",
     "warp.hip",
     "api_warp.hip",

@@ -24,6 +24,7 @@
 
 #include "colsort.h"  // kThreads, kChunk, KdeSrc, the keys, kde_sort_chunks_kernel, column_merge
 #include "common.h"
+#include "kde.h"
 #include "transform.h"
 
 namespace {
@@ -879,4 +880,47 @@ extern "C" int vbmc_mtv(vbmc_ctx* ctx, int D, const vbmc_mtv_side* s1, const vbm
     mtv_D[d] = acc;
   }
   return VBMC_OK;
+}
+
+// kde.h: the plan and the stages above for a caller outside this file (vbmc_marginals)
+KdeCols kde_cols_plan(Scratch& sc, int ncol, int nm, int64_t n) {
+  KdePlan pl;
+  pl.plan(sc, ncol, nm, n, true, false, 0);
+  KdeCols kc;
+  kc.ncol = ncol;
+  kc.nm = nm;
+  kc.pmax = pl.pmax;
+  kc.o_keys = pl.o_keys;
+  kc.o_nf = pl.o_nf;
+  kc.o_bnd = pl.o_bnd;
+  kc.o_dens = pl.o_dens;
+  kc.o_xm = pl.o_xm;
+  kc.o_colp = pl.o_colp;
+  kc.o_ga = pl.o_ga;
+  kc.o_stat = pl.o_stat;
+  kc.colp_stride = CP_N;
+  kc.colp_bw = CP_BW;
+  return kc;
+}
+
+int kde_cols_launch(vbmc_ctx* ctx, const KdeCols& kc, const double* d_x, int64_t n, int64_t rs, int64_t cs, double* base) {
+  KdePlan pl;
+  pl.ncol = kc.ncol;
+  pl.nm = kc.nm;
+  pl.pmax = kc.pmax;
+  pl.o_keys = kc.o_keys;
+  pl.o_ga = kc.o_ga;
+  pl.o_dens = kc.o_dens;
+  pl.o_xm = kc.o_xm;
+  pl.o_colp = kc.o_colp;
+  pl.o_stat = kc.o_stat;
+  pl.o_nf = kc.o_nf;
+  pl.o_bnd = kc.o_bnd;
+  KdeSrc src = {};
+  src.x[0] = src.x[1] = d_x;
+  src.n[0] = src.n[1] = n;
+  src.rs[0] = src.rs[1] = rs;
+  src.cs[0] = src.cs[1] = cs;
+  src.ncol0 = kc.ncol;
+  return launch_kde(ctx, pl, src, base, BND_KDE, true, true, true, false);
 }

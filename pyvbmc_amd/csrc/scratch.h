@@ -114,3 +114,43 @@ struct CmaState {
     total = o;
   }
 };
+
+// The scratch of vbmc_marginals (api_marginals.hip) behind the kde pieces (kde.hip's plan: the keys of the D sorted
+// columns first, which the call's own sort shares):
+//   x (n x D samples, drawn or uploaded) | selector of the draw | par = ranges (2 D), quantile levels (nq), mass
+//   levels (nl), uploaded | colinfo (D x 4: lo, hi, hi - lo, step) | idx (D x ns bytes, ns = n rounded up to 256: the bin
+//   of every sample per dimension) | the result block, downloaded in one copy: edges (D x (bins + 1)) | quantiles
+//   (nq x D) | kde_x, kde_density (D x mesh each) | colp (the kde's per-column results) | counts1 (D x bins uint64) |
+//   counts2 (P x bins x bins uint64) | inside2 (P uint64) | level_counts (P x nl int64) | level_mass (P x nl) |
+//   nonfinite (D unsigned)
+struct MargWs {
+  Piece<> x, sel, par, colinfo, edges, quant, kde_x, kde_dens, colp, level_mass;
+  Piece<unsigned char> idx;
+  Piece<unsigned long long> counts1, counts2, inside2;
+  Piece<long long> level_counts;
+  Piece<unsigned> nonfinite;
+  size_t res_begin = 0, res_end = 0;  // the result block, in doubles
+};
+inline MargWs marginals_ws(Scratch& sc, size_t n, size_t ns, size_t D, size_t bins, size_t P, size_t nq, size_t nl,
+                           size_t sel_elems, size_t mesh, size_t colp_stride) {
+  MargWs w;
+  w.x = sc.add(n * D);
+  w.sel = sc.add(sel_elems);
+  w.par = sc.add(2 * D + nq + nl);
+  w.colinfo = sc.add(4 * D);
+  w.idx = sc.add<unsigned char>(D * ns);
+  w.edges = sc.add(D * (bins + 1));
+  w.res_begin = w.edges.off;
+  w.quant = sc.add(nq * D);
+  w.kde_x = sc.add(D * mesh);
+  w.kde_dens = sc.add(D * mesh);
+  w.colp = sc.add(mesh ? D * colp_stride : 0);
+  w.counts1 = sc.add<unsigned long long>(D * bins);
+  w.counts2 = sc.add<unsigned long long>(P * bins * bins);
+  w.inside2 = sc.add<unsigned long long>(P);
+  w.level_counts = sc.add<long long>(P * nl);
+  w.level_mass = sc.add(P * nl);
+  w.nonfinite = sc.add<unsigned>(D);
+  w.res_end = sc.total;
+  return w;
+}

@@ -10,8 +10,9 @@ side effects and exceptions -- plus ``kl_div`` (:1032-1127), the Monte-Carlo con
 SURVEY.md 8f row 4 names, and ``mtv`` (:921-1030), the marginal total variation distance, whose
 density estimates, splines and integrals run on the device (csrc/kde.hip, vbmc_mtv; kde_1d itself is
 ``pyvbmc_amd.stats.kde_1d``), and ``mode`` (:810-919), whose start selection and local searches run on the
-device for all rounds at once (csrc/mode.hip, vbmc_mixture_mode), and ``save`` / ``load`` (:1287-1343).  ``plot`` is not
-provided.
+device for all rounds at once (csrc/mode.hip, vbmc_mixture_mode), and ``save`` / ``load`` (:1287-1343), and ``plot``
+(:1129-1285) over ``marginals``, the histograms, quantiles and density levels of a corner plot in one device call
+(csrc/marginals.hip, vbmc_marginals; pyvbmc_amd/marginals.py).
 
 Where the arithmetic runs: ``pdf``/``log_pdf`` -> HIP kernel (vbmc_mixture_pdf).
 State bookkeeping (get/set_parameters, bounds) and the closed-form K*D^2 moments are
@@ -666,6 +667,26 @@ class VariationalPosterior:
         if np.any(info[:, 1] & _lib.KDE_DEGENERATE):
             _raise_degenerate("mtv")
         return out.reshape(1, D)
+
+    # -- marginals and the corner plot (:1129-1285) ----------------------------------------------------
+    def marginals(self, N=int(1e6), bins=40, ranges=None, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), levels=(0.5, 0.9),
+                  orig_flag=True, samples=None, kde=True, *, rng=None, seed=None, device=True, ctx=None):
+        """The numbers of a corner plot as a ``Marginals`` object: the 1-D and pair histograms of ``N`` draws (or of
+        ``samples``), the quantiles per dimension, the highest-density levels per pair and the kde_1d curve per
+        dimension -- one device call (vbmc_marginals); ``device=False``: the same in NumPy.  The rules are stated in
+        pyvbmc_amd/marginals.py."""
+        from . import marginals as _mg
+
+        return _mg.marginals(self, N, bins, ranges, quantiles, levels, orig_flag, samples, kde, rng=rng, seed=seed,
+                             device=device, ctx=ctx)
+
+    def plot(self, n_samples=int(1e5), title=None, plot_data=False, highlight_data=None, plot_vp_centres=False,
+             plot_style=None, gp=None):
+        """Reference signature: the corner plot of ``marginals(N=n_samples)`` drawn with matplotlib (imported here;
+        ``ImportError`` without it, before any sampling).  Returns the figure."""
+        from . import marginals as _mg
+
+        return _mg.plot(self, n_samples, title, plot_data, highlight_data, plot_vp_centres, plot_style, gp)
 
 
 _IDENTITY_PT = {}
